@@ -6,6 +6,7 @@ latency that is the other half of BASELINE.json's metric.
     python bench.py --gpus N --steps K --warmup W    # N > 1 without a launcher: spawns N ranks itself (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W       # the driver's own launch: one rank per GPU over RCCL
+    python bench.py ... --dump-outputs DIR           # also writes the last timed step's outputs to DIR/*.npy (dump_outputs)
 
 A "step" is one pass of the hot path (KWSModel.forward: 40-d fbank features -> per-frame posteriors + streaming cache,
 what wekws/bin/score.py:125 calls) over one batch of synthetic 1-s utterances already resident in HBM.  Workload
@@ -191,6 +192,37 @@ def emit(out, extra, extras_out):
     assert len(line) <= MAX_LINE_BYTES, f"contract line grew to {len(line)} bytes (limit {MAX_LINE_BYTES})"
     sys.stdout.flush()
     print(line, flush=True)
+
+
+DUMP_BYTES = 64 << 20                              # --dump-outputs: at most this much in all, over every array and rank
+NPY_HEADER_BYTES = 4096                            # an upper bound of one .npy file's header (numpy writes 128 .. a few hundred)
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: what the last timed step returned to its caller, as DIR/<name>.npy (float32, as computed).  An array over
+    its share of DUMP_BYTES is replaced by a fixed, seeded sample of its rows (axis 0: the utterances of the conv backbones'
+    caches; single elements of the flattened array if even one row does not fit) -- <name>_sample.npy, with the sampled row
+    numbers in <name>_sample_index.npy (float64).  The share covers the index file and both headers.  With N ranks every rank
+    writes its own outputs, suffixed _rank<r>."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // (world * len(arrays))
+    sfx = f"_rank{rank}" if world > 1 else ""
+    written = []
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.nbytes + NPY_HEADER_BYTES > share:
+            budget = share - 2 * NPY_HEADER_BYTES                 # the sample and its index file
+            if a.nbytes // a.shape[0] + 8 > budget:
+                a = a.reshape(-1)
+            n = budget // (a.nbytes // a.shape[0] + 8)               # each row costs its bytes + one float64 index
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[0], size=n, replace=False))
+            written.append(os.path.join(dirname, f"{name}_sample_index{sfx}.npy"))
+            np.save(written[-1], idx.astype(np.float64))
+            a, name = a[idx], name + "_sample"
+        written.append(os.path.join(dirname, f"{name}{sfx}.npy"))
+        np.save(written[-1], a)
+    total = sum(os.path.getsize(f) for f in written)
+    assert total <= DUMP_BYTES // world, f"--dump-outputs wrote {total} bytes, over the {DUMP_BYTES // world} of this rank"
 
 
 def secondary(torch, init_model, pack, synth, dev, name, B, T, steps=30, score_only=False, precision="default"):
@@ -466,7 +498,12 @@ def main():
     ap.add_argument("--precision", default="default", choices=["default", "f32", "f16x3", "f16"],
                     help="matrix arithmetic of `value` (enum wekws_hip_precision); default = f16x3 with block floating "
                          "point (fp32-level accuracy at any operand scale); the f32 number is always reported beside it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (posteriors, streaming cache; seeded inputs) to DIR/<name>.npy, "
+                         "<= 64 MB in all (a seeded sample of the rows of a larger array): two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_worker:
         name, th, tt, bud = args.cpu_worker.split(",")
         return cpu_worker(name, int(th), int(tt), float(bud))
@@ -581,6 +618,8 @@ def main():
         bc_ms_max = max(float(t[1].item()) for t in allr) * 1e3
         elapsed = max(float(t[0].item()) for t in allr)       # MAX over ranks
     assert torch.isfinite(y).all()
+    if args.dump_outputs:                                     # y, cache: still the outputs of the last timed step
+        dump_outputs(args.dump_outputs, {"posteriors": y, "cache": cache}, rank, world)
 
     if rank == 0:
         value = B * world * args.steps / elapsed

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Generate tests/golden/fbank_golden.npz from the REFERENCE front-end compiled into oracle/_ref/
 (make -C oracle; needs /root/reference, so build container only).  Inputs are regenerated from seeds by
-the tests (wekws_amd.utils.synth.synth_pcm); only the reference outputs are stored.
+the tests (wekws_amd.utils.synth.synth_pcm); only the reference outputs are stored.  `stream` writes
+tests/golden/fbank_stream_golden.npz instead: the reference fed in two pushes on the seeded inputs of
+tests/test_fbank_oracle.py::test_oracle_matches_compiled_reference.
 
-    python tests/golden/make_fbank_golden.py
+    python tests/golden/make_fbank_golden.py [stream]
 """
 import os
 import sys
@@ -31,5 +33,21 @@ def main():
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+STREAM_LENGTHS = (400, 559, 560, 8000, 16000, 23456)
+
+
+def stream_input(rng, n):
+    return np.round(rng.standard_normal(n) * 2000).astype(np.float32)
+
+
+def main_stream():
+    assert fbank_oracle.have_ref(), "run `make -C oracle` in the build container first"
+    rng = np.random.default_rng(7)
+    out = {f"n{n}": fbank_oracle.ref_fbank(stream_input(rng, n), 40, 16000, first_push=n // 3) for n in STREAM_LENGTHS}
+    path = os.path.join(HERE, "fbank_stream_golden.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    main_stream() if sys.argv[1:] == ["stream"] else main()

@@ -144,3 +144,11 @@ def random_model_config(rng):
         cfg["preprocessing"] = {"type": "none"}
         cfg["input_dim"] = cfg["hidden_dim"]
     return cfg, head
+
+
+def random_config_spec(cfg):
+    """State-dict spec of a random_model_config model as the reference builds it for the live comparison: init_model without
+    the CMVN, the GlobalCMVN assigned afterwards, so its two buffers come last (the order the seeded weight stream follows)."""
+    spec = pack.model_spec(cfg)
+    cmvn = [s for s in spec if s[0].startswith("global_cmvn.")]
+    return [s for s in spec if not s[0].startswith("global_cmvn.")] + cmvn

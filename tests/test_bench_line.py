@@ -50,3 +50,40 @@ def test_emit_refuses_a_line_that_outgrew_the_tail(tmp_path):
     with pytest.raises(AssertionError):
         with redirect_stdout(io.StringIO()):
             bench.emit(out, {}, str(tmp_path / "e.json"))
+
+
+def test_dump_outputs_keeps_small_arrays_and_samples_large_ones(tmp_path):
+    """--dump-outputs: arrays within their share of the 64 MB are written whole; a larger one as a seeded sample of its rows,
+    the same rows every run, with the row numbers beside it (float64)."""
+    import numpy as np
+    import torch
+    y = torch.arange(24, dtype=torch.float32).reshape(2, 3, 4)
+    big = torch.randn(80, 1 << 17)                                   # 40 MB > a 32 MB share
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"posteriors": y, "cache": big}, 0, 1)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["cache_sample.npy", "cache_sample_index.npy", "posteriors.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BYTES
+    assert np.array_equal(np.load(tmp_path / "a" / "posteriors.npy"), y.numpy())
+    idx = np.load(tmp_path / "a" / "cache_sample_index.npy")
+    share = bench.DUMP_BYTES // 2                                    # two arrays; the sample pays for its index and headers
+    assert len(idx) == (share - 2 * bench.NPY_HEADER_BYTES) // (big[0].numel() * 4 + 8) == 63
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "cache_sample.npy"), big.numpy()[idx.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    bench.dump_outputs(str(tmp_path / "r"), {"posteriors": y}, 1, 2)
+    assert os.listdir(tmp_path / "r") == ["posteriors_rank1.npy"]
+    # one row larger than the share (3 rows of 40 MB): single elements of the flattened array, still within the cap
+    wide = torch.randn(3, 10 << 20)
+    bench.dump_outputs(str(tmp_path / "w"), {"posteriors": y, "cache": wide}, 0, 1)
+    assert sum(os.path.getsize(tmp_path / "w" / f) for f in os.listdir(tmp_path / "w")) <= bench.DUMP_BYTES
+    idx = np.load(tmp_path / "w" / "cache_sample_index.npy").astype(np.int64)
+    assert len(idx) == (share - 2 * bench.NPY_HEADER_BYTES) // 12
+    assert np.array_equal(np.load(tmp_path / "w" / "cache_sample.npy"), wide.numpy().reshape(-1)[idx])
+
+
+def test_steps_below_one_are_refused():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr

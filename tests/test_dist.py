@@ -24,6 +24,12 @@ def test_shard_range_tiles_exactly():
             assert max(sizes) - min(sizes) <= 1
 
 
+def cpu_barrier():
+    """dist.barrier() looks up the accelerator (torch._C._get_accelerator), which initialises HIP -- opens the GPU -- in every rank
+    of these CPU-only jobs; an all_reduce of a CPU tensor over gloo synchronises the ranks the same way without touching it."""
+    dist.all_reduce(torch.zeros(1))
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -54,7 +60,7 @@ def _worker(rank, world, port, q):
     y = parallel.gather_scores(y_local, 11, dst=0)
     q.put((rank, float(np.abs(blob.astype(np.float64)).sum()), blob.size,
            None if y is None else y[:, 0, 0].tolist()))
-    dist.barrier()
+    cpu_barrier()
     dist.destroy_process_group()
 
 
@@ -101,7 +107,7 @@ def _worker8(rank, world, port, q, ckpt_dir):
     y = parallel.gather_scores(y_local, n, dst=0)
     ok = None if y is None else bool(torch.equal(y[:, 0], torch.arange(n, dtype=torch.float32)))
     q.put((rank, hi - lo, float(np.abs(blob.astype(np.float64)).sum()), ok))
-    dist.barrier()
+    cpu_barrier()
     dist.destroy_process_group()
 
 

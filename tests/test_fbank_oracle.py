@@ -1,5 +1,5 @@
 """CPU: the plain-C fbank oracle against (a) the golden vectors recorded from the reference front-end and
-(b) the compiled reference itself when oracle/_ref is present."""
+(b) the reference fed in two pushes (golden vectors, and the compiled reference itself when oracle/_ref is present)."""
 import os
 
 import numpy as np
@@ -7,6 +7,7 @@ import pytest
 
 from oracle import fbank_oracle
 from tests.golden.fbank_cases import FBANK_CASES, fbank_input
+from tests.golden.make_fbank_golden import STREAM_LENGTHS, stream_input
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -28,14 +29,17 @@ def test_oracle_matches_golden(case, fgolden):
     assert float(np.abs(got - ref).max()) <= 2e-6
 
 
-@pytest.mark.skipif(not fbank_oracle.have_ref(), reason="oracle/_ref not built (reference tree absent)")
 def test_oracle_matches_compiled_reference():
+    sgolden = np.load(os.path.join(ROOT, "tests", "golden", "fbank_stream_golden.npz"))
     rng = np.random.default_rng(7)
-    for n in (400, 559, 560, 8000, 16000, 23456):
-        pcm = np.round(rng.standard_normal(n) * 2000).astype(np.float32)
-        ref = fbank_oracle.ref_fbank(pcm, 40, 16000, first_push=n // 3)
+    for n in STREAM_LENGTHS:
+        pcm = stream_input(rng, n)
         got = fbank_oracle.fbank(pcm, 40)
-        assert ref.shape == got.shape and float(np.abs(ref - got).max()) <= 2e-6
+        refs = [sgolden[f"n{n}"]]
+        if fbank_oracle.have_ref():
+            refs.append(fbank_oracle.ref_fbank(pcm, 40, 16000, first_push=n // 3))
+        for ref in refs:
+            assert ref.shape == got.shape and float(np.abs(ref - got).max()) <= 2e-6
 
 
 def test_short_input_yields_no_frames():

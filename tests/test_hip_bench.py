@@ -93,3 +93,35 @@ def test_default_run_line_fits_the_driver_tail(tmp_path):
     for k in ("f32", "also", "gru", "config4_shard", "config5", "latency", "latency_chunk80", "rooflines_other", "audio_to_posteriors"):
         assert k in extras, k
     assert d["summary"]["mdtc_h64"]["value"] == extras["also"]["value"]
+
+
+def test_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs: the last timed step's posteriors and (a seeded row sample of) its 110 MB cache, within 64 MB; the same
+    whatever the number of steps and from run to run (seeded inputs), and what the oracle computes for those inputs."""
+    import numpy as np
+    from oracle import kws_oracle
+    from wekws_amd import pack
+    from wekws_amd.utils import synth
+    runs = []
+    for i, steps in enumerate(("3", "5")):
+        out = tmp_path / f"run{i}"
+        d = run_bench("--gpus", "1", "--steps", steps, "--warmup", "1", "--preheat", "0", "--no-extras", "--no-cpu-baseline",
+                      "--dump-outputs", str(out))
+        assert d["steps"] == int(steps) and d["ms_per_step"] > 0
+        runs.append(out)
+    files = sorted(os.listdir(runs[0]))
+    assert files == sorted(os.listdir(runs[1])) == ["cache_sample.npy", "cache_sample_index.npy", "posteriors.npy"]
+    assert sum(os.path.getsize(runs[0] / f) for f in files) <= 64 << 20
+    for f in files:
+        a = np.load(runs[0] / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, np.load(runs[1] / f)), f
+    y, cs = np.load(runs[0] / "posteriors.npy"), np.load(runs[0] / "cache_sample.npy")
+    idx = np.load(runs[0] / "cache_sample_index.npy").astype(np.int64)
+    assert y.shape == (1024, 98, 2) and cs.shape[1:] == (256, 105) and len(idx) == cs.shape[0]
+    cfg = dict(synth.MODEL_CONFIGS["ds_tcn_h256"])                     # bench.py's inputs: weights seed 1234, features 100 + rank
+    sd = synth.synth_state_dict(pack.model_spec(cfg), 1234)
+    rows = idx[:: max(1, len(idx) // 16)]
+    x = synth.synth_feats(1024, 98, cfg["input_dim"], seed=100)[rows]
+    ry, rc = kws_oracle.forward(cfg, sd, x, None)
+    assert float(np.abs(y[rows] - ry).max()) <= 1e-4
+    assert float(np.abs(cs[np.searchsorted(idx, rows)] - rc).max()) <= 1e-4 * max(1.0, float(np.abs(rc).max()))

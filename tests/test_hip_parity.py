@@ -1179,25 +1179,24 @@ def test_exported_models(name):
 
 
 @pytest.mark.gpu
-def test_reference_android_asset_hip(error_report):
-    """The trained DS-TCN the reference ships as an ORT file, converted by tests/tools/make_ref_asset.py in the build
-    container (the asset itself is not in this repo): packed file -> C ABI, streamed in 80-frame chunks.  The only REAL
+def test_reference_android_asset_hip(error_report, tmp_path):
+    """The trained DS-TCN the reference ships as an ORT file (tests/golden/kws.ort), packed by wekws_amd.bin.export_packed:
+    packed file -> C ABI, streamed in 80-frame chunks against tests/golden/kws_ort_expect.npz (tests/tools/make_ref_asset.py).  The only REAL
     weights in the suite.  Two streams (make_ref_asset.py): the 3 randn + 10 noise of round 1, on which the trained model's
     posteriors are 1e-8 .. 1e-5 -- an absolute bar on them would pass for an all-zero output, so the LOGITS are compared
     (descriptor activation = identity: the value one node before the graph's Sigmoid), relative to their size --, and an
     input found by gradient ascent that sweeps the keyword posterior 0 -> 0.998 -> 0, on which the 1e-4 posterior bar
     bites.  Margins, posterior range and the spread of the trained matrices go to gpurun_out/parity_errors.json."""
-    import os
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "build", "ref_asset")
-    if not os.path.exists(os.path.join(root, "kws.wekwship")):
-        pytest.skip("build/ref_asset not prepared (python tests/tools/make_ref_asset.py where /root/reference exists)")
     import ctypes
+    import os
     from wekws_amd import _capi, pack
+    from wekws_amd.bin import export_packed
     from wekws_amd.model.kws_model import _HipHandle
-    desc, blob = pack.load_packed(os.path.join(root, "kws.wekwship"))
-    exp = np.load(os.path.join(root, "expect.npz"))
-    if "logit_kw" not in exp.files:
-        pytest.skip("build/ref_asset is from an older make_ref_asset.py: re-run it where /root/reference exists")
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    packed = str(tmp_path / "kws.wekwship")
+    export_packed.main(["--exported", os.path.join(golden, "kws.ort"), "--output", packed])
+    desc, blob = pack.load_packed(packed)
+    exp = np.load(os.path.join(golden, "kws_ort_expect.npz"))
     lib = _capi.load()
     dd = {k: int(desc[k]) for k in pack.DESC_FIELDS}
     assert dd["activation"] == 1                                # sigmoid, as the graph ends

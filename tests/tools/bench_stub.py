@@ -37,11 +37,13 @@ def main():
         model.load_state_dict({k: torch.from_numpy(v) for k, v in synth.synth_state_dict(pack.model_spec(cfg), 1234).items()})
     parallel.broadcast_weights(model, src=0, device=torch.device("cpu"))
     wsum = float(np.abs(model.packed()[1].astype(np.float64)).sum())
-    dist.barrier()
+    # the barriers are all_reduces of a CPU tensor: dist.barrier() looks up the accelerator, which would open the GPU in every rank
+    barrier = lambda: dist.all_reduce(torch.zeros(1))  # noqa: E731
+    barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         time.sleep(0.001 * (1 + rank))                       # rank 1 is slower: the line must carry the MAX
-    dist.barrier()
+    barrier()
     tt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     ws = torch.tensor([wsum], dtype=torch.float64)
@@ -53,7 +55,7 @@ def main():
                           "scaling": "weak", "vs_baseline": None, "dtype": "none", "data": "stub",
                           "config": {"workload": "launcher plumbing test (forward stubbed)"},
                           "weights_identical_on_all_ranks": abs(float(ws.item()) - wsum) < 1e-9}))
-    dist.barrier()
+    barrier()
     dist.destroy_process_group()
 
 

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Build-container only: turn the one trained model the reference ships (runtime/android/app/src/main/assets/kws.ort)
-into build/ref_asset/{kws.wekwship, expect.npz} for tests/test_hip_parity.py::test_reference_android_asset_hip.
-build/ is git-ignored but travels to the GPU box, where /root/reference does not exist.
+"""Generate tests/golden/kws_ort_expect.npz for tests/test_hip_parity.py::test_reference_android_asset_hip from the one
+trained model the reference ships (its runtime/android/app/src/main/assets/kws.ort, stored as tests/golden/kws.ort; the test
+packs it itself with wekws_amd.bin.export_packed).
 
-expect.npz = the graph run by the numpy executor (oracle/onnx_graph_oracle.py) on two seeded 3-chunk streams:
+kws_ort_expect.npz = the graph run by the numpy executor (oracle/onnx_graph_oracle.py) on two seeded 3-chunk streams:
   x / y / logit / cache            3 randn + 10 noise (round 1's input): the trained model answers with posteriors of
                                    1e-8 .. 1e-5, so only the LOGITS (one node before the Sigmoid) say anything there;
   x_kw / y_kw / logit_kw / cache_kw  an input that drives the keyword posterior THROUGH its range (round-3 review: the
@@ -22,11 +22,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from oracle import onnx_graph_oracle, torch_ref  # noqa: E402
-from wekws_amd.bin import export_packed  # noqa: E402
 from wekws_amd.model.kws_model import load_exported  # noqa: E402
 from wekws_amd.utils import onnx_model  # noqa: E402
 
-SRC = "/root/reference/runtime/android/app/src/main/assets/kws.ort"
+SRC = os.path.join(ROOT, "tests", "golden", "kws.ort")
 T, CHUNK = 240, 80
 
 
@@ -64,9 +63,6 @@ def stream(g, x, logit_name):
 
 
 def main():
-    out = os.path.join(ROOT, "build", "ref_asset")
-    os.makedirs(out, exist_ok=True)
-    export_packed.main(["--exported", SRC, "--output", os.path.join(out, "kws.wekwship")])
     g = onnx_model.load_graph(SRC)
     sig = [n for n in g.toposorted() if n.op == "Sigmoid" and n.outputs[0] == "output"]
     assert len(sig) == 1
@@ -81,8 +77,8 @@ def main():
     print("keyword input: posterior %.3f .. %.3f, logits %.2f .. %.2f; frames inside (0.05, 0.95): %d" %
           (y_kw.min(), y_kw.max(), logit_kw.min(), logit_kw.max(), int(((y_kw > 0.05) & (y_kw < 0.95)).sum())))
     assert y_kw.max() > 0.95 and y_kw.min() < 0.05 and ((y_kw > 0.05) & (y_kw < 0.95)).sum() >= 8
-    np.savez(os.path.join(out, "expect.npz"), x=x, y=y, logit=logit, cache=cache,
-             x_kw=x_kw, y_kw=y_kw, logit_kw=logit_kw, cache_kw=cache_kw)
+    out = os.path.join(ROOT, "tests", "golden", "kws_ort_expect.npz")
+    np.savez_compressed(out, x=x, y=y, logit=logit, cache=cache, x_kw=x_kw, y_kw=y_kw, logit_kw=logit_kw, cache_kw=cache_kw)
     print("wrote", out)
 
 
