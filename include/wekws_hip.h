@@ -47,6 +47,7 @@ enum wekws_hip_error {
   WEKWS_HIP_EINVAL = -1,      /* bad argument / unsupported configuration */
   WEKWS_HIP_ENOMEM = -2,      /* device allocation failed */
   WEKWS_HIP_EDEVICE = -3,     /* HIP runtime error (no device, launch failure ...) */
+  WEKWS_HIP_ECAPACITY = -5,   /* a CTC keyword stream's prefix outgrew the capacity set at creation (never truncated) */
   WEKWS_HIP_EUNSUPPORTED = -4 /* valid reference config that this build has no kernel for.  Since ABI 2 no MODEL
                                  configuration returns it: shapes beyond the specialised kernels (more than 256 channels, kernel
                                  sizes above 8 / 5, GRU hidden sizes above 128 or pooled heads on a GRU, ...) run on the
@@ -390,6 +391,70 @@ int wekws_hip_det_false_alarms(const float* scores, int B, int T, int K, int key
  */
 int wekws_hip_det_false_alarms_text(const float* scores, int B, int T, int K, int keyword, const int32_t* lengths,
                                     const double* thresholds, int n_thr, int window_shift, int32_t* alarms, void* stream);
+
+/* -------------------------------------------------------------------------------------------
+ * CTC prefix beam search and keyword detection  --  the decode that turns a CTC head's posteriors into a keyword decision,
+ * on the device, for many streams at once:
+ *   offline    wekws/model/loss.py:206-312 ctc_prefix_beam_search + the per-utterance loop of wekws/bin/score_ctc.py:183-236
+ *   streaming  wekws/bin/stream_kws_ctc.py KeyWordSpotter: the post-model part of forward (:488-514), decode_keywords,
+ *              execute_detection, is_sublist, reset / reset_all (:516-530)
+ * Every output is bit-identical to the reference given the same float32 posteriors (its arithmetic is Python floats: the
+ * kernel computes in f64).  Two deliberate deviations: exact ties inside the first-beam top-k go lower
+ * index first; a frame holding +-Inf fails its stream with WEKWS_HIP_EINVAL (NaN ranks above every number and is dropped
+ * by the 0.05 filter, as in the reference).  A stream whose status is set is left untouched by later steps until
+ * reset / reset_all.
+ * ------------------------------------------------------------------------------------------*/
+typedef struct wekws_hip_ctc_kws_desc {
+  int32_t vocab;            /* V >= 1 */
+  int32_t score_beam;       /* 1..8 (reference: 3) */
+  int32_t path_beam;        /* 1..64 (reference: 20) */
+  int32_t num_keywords;     /* >= 0 */
+  const int32_t* keyword_tokens;   /* host: the keywords' token ids, concatenated in insertion order */
+  const int32_t* keyword_offsets;  /* host: num_keywords + 1 offsets into keyword_tokens; every keyword non-empty */
+  const int32_t* token_set;        /* host: the first-beam token set (KeyWordSpotter adds blank 0 itself: so must the
+                                      caller), or NULL for none (loss.py's keywords_tokenset=None) */
+  int32_t token_set_len;
+  int32_t min_frames, max_frames, interval_frames;   /* streaming detection (reference: 5, 250, 50) */
+  int32_t downsampling;     /* >= 1: frame t of a chunk is t * downsampling + total_frames */
+  int32_t max_streams;      /* streaming slots, ids 0 .. max_streams - 1 */
+  int32_t prefix_capacity;  /* streaming: longest prefix a stream may hold (ECAPACITY beyond) */
+  int32_t device;
+  double threshold;
+} wekws_hip_ctc_kws_desc;
+
+typedef struct wekws_hip_ctc_kws_result {
+  int32_t status;   /* 0, or the stream's failure (WEKWS_HIP_EINVAL: +-Inf posterior or bad id / count; WEKWS_HIP_ECAPACITY) */
+  int32_t valid;    /* streaming: 0 = the call gave the stream no frames (the reference's `{}`, nothing changed) */
+  int32_t state;    /* streaming: 1 = activated (forward's result "state"); offline: 1 = a keyword was found */
+  int32_t keyword;  /* keyword index of the last detection (activated or not), -1 = none */
+  int32_t start, end;      /* its first / last node frame (the reference's start / end before * resolution) */
+  double score;     /* hit_score: streaming, the stream's carried value after the call's last frame (reset to 1.0 only by
+                       reset / activation / aging); offline, from 1.0 per utterance */
+} wekws_hip_ctc_kws_result;
+
+int wekws_hip_ctc_kws_create(const wekws_hip_ctc_kws_desc* desc, void** out);
+void wekws_hip_ctc_kws_destroy(void* h);
+/* Streaming step: row b of probs (B, T, V) device float32 continues stream stream_ids[b] with its first frames[b] frames
+ * (0 .. T; 0 = the `{}` case).  stream_ids / frames (B) device int32 (frames NULL = T), distinct ids in one call, any
+ * subset in any order; results (B) device.  Frame t of row b is stream time t * downsampling + total_frames. */
+int wekws_hip_ctc_kws_step(void* h, const float* probs, int B, int T, const int32_t* stream_ids, const int32_t* frames,
+                           wekws_hip_ctc_kws_result* results, void* stream);
+/* Offline search: every row a fresh utterance of lengths[b] frames (NULL = T), decoded with the descriptor's beams and
+ * token set, then score_ctc's detection.  beams: NULL, or (B) records of wekws_hip_ctc_kws_beam_bytes(h, T) bytes each
+ * receiving the final beam.  Uses a workspace of the handle (grown on demand: synchronises `stream` once). */
+int wekws_hip_ctc_kws_search(void* h, const float* probs, int B, int T, const int32_t* lengths,
+                             wekws_hip_ctc_kws_result* results, void* beams, void* stream);
+/* reset() (all = 0) or reset_all() (all = 1) of the n streams in ids (device int32); both clear a failed status. */
+int wekws_hip_ctc_kws_reset(void* h, const int32_t* ids, int n, int all, void* stream);
+/* Bytes of one beam record with prefix capacity `cap`:
+ *   int32 count, pad | int32 len[PB rounded up to even] | f64 pb[PB] | f64 pnb[PB] | int32 token[PB][cap] |
+ *   int32 frame[PB][cap] (+ 4 pad bytes if PB * cap is odd) | f64 prob[PB][cap];  rounded up to 16 bytes. */
+size_t wekws_hip_ctc_kws_beam_bytes(void* h, int cap);
+/* The beam of stream `id` (cur_hyps: prefix, pb, pnb and node token / frame / prob) into `out` (device, beam_bytes(h,
+ * prefix_capacity)). */
+int wekws_hip_ctc_kws_read_beam(void* h, int id, void* out, void* stream);
+/* The stream's sticky status (0 or WEKWS_HIP_E*) into *status_out; synchronises `stream`. */
+int wekws_hip_ctc_kws_status(void* h, int id, int32_t* status_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,18 @@ class FbankCfg(C.Structure):
                [("reserved", C.c_int32 * 3)]
 
 
+class CtcKwsDesc(C.Structure):
+    _fields_ = [("vocab", C.c_int32), ("score_beam", C.c_int32), ("path_beam", C.c_int32), ("num_keywords", C.c_int32),
+                ("keyword_tokens", C.c_void_p), ("keyword_offsets", C.c_void_p), ("token_set", C.c_void_p),
+                ("token_set_len", C.c_int32), ("min_frames", C.c_int32), ("max_frames", C.c_int32),
+                ("interval_frames", C.c_int32), ("downsampling", C.c_int32), ("max_streams", C.c_int32),
+                ("prefix_capacity", C.c_int32), ("device", C.c_int32), ("threshold", C.c_double)]
+
+
+class CtcKwsResult(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("status", "valid", "state", "keyword", "start", "end")] + [("score", C.c_double)]
+
+
 # name -> (restype, argtypes); the CPU test-suite checks every symbol of the header is exported
 SIGNATURES = {
     "wekws_hip_last_error": (C.c_char_p, []),
@@ -61,6 +73,16 @@ SIGNATURES = {
                                              C.c_int, C.c_void_p, C.c_void_p]),
     "wekws_hip_splice": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                    C.c_void_p]),
+    "wekws_hip_ctc_kws_create": (C.c_int, [C.POINTER(CtcKwsDesc), C.POINTER(C.c_void_p)]),
+    "wekws_hip_ctc_kws_destroy": (None, [C.c_void_p]),
+    "wekws_hip_ctc_kws_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "wekws_hip_ctc_kws_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "wekws_hip_ctc_kws_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "wekws_hip_ctc_kws_beam_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "wekws_hip_ctc_kws_read_beam": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "wekws_hip_ctc_kws_status": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p]),
 }
 
 OPTIONS = {"w16": 0, "mdtc16": 1, "stream": 2, "mm": 3, "head_slices": 4, "g16": 5, "envelope": 6, "gru_pipe": 7}   # enum wekws_hip_option

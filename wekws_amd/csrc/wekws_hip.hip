@@ -53,6 +53,18 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+}  // namespace
+
+namespace wekws {
+// the thread's last-error message, for entry points defined in other translation units (ctc_kws.hip)
+int set_last_error(int code, const char* msg) {
+  g_err = msg;
+  return code;
+}
+}  // namespace wekws
+
+namespace {
+
 #define HIP_TRY(expr)                                                                          \
   do {                                                                                         \
     hipError_t e_ = (expr);                                                                    \

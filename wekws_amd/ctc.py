@@ -1,12 +1,18 @@
-"""Device side of the CTC keyword decoder: the first beam prune of ``ctc_prefix_beam_search``
-(wekws/model/loss.py:236-251) -- per frame, the ``score_beam_size`` largest softmax posteriors and their token ids --
-computed from the LOGITS in one kernel (``wekws_hip_softmax_topk``), so that a streaming caller
-(wekws/bin/stream_kws_ctc.py:486-494) moves 8*k bytes per frame to the host instead of the whole posterior row.
-The prefix search itself (loss.py:253-312) is host control logic and stays in the reference's Python."""
+"""Device side of the CTC keyword decoder.
+
+- ``softmax_topk`` / ``first_beam_prune``: the first beam prune of ``ctc_prefix_beam_search`` (wekws/model/loss.py:236-251)
+  computed from the LOGITS in one kernel (``wekws_hip_softmax_topk``).
+- ``ctc_prefix_beam_search`` / ``keyword_search`` / ``StreamingKeywordSpotter``: the whole decode -- the prefix beam search
+  of loss.py:206-312, score_ctc's detection loop and the streaming ``KeyWordSpotter`` of wekws/bin/stream_kws_ctc.py --
+  on the device for a batch of utterances or thousands of streams (``wekws_hip_ctc_kws_*``, csrc/ctc_kws.hip.h), bit-identical
+  to the reference given the same float32 posteriors.  The host receives one small result record per stream and call.
+  Intended use: ``probs, cache = model.forward_softmax(chunk, cache); res = spotter.step(probs)``."""
 from __future__ import annotations
 
 import ctypes
-from typing import Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
 
 import torch
 
@@ -42,3 +48,250 @@ def first_beam_prune(logits: torch.Tensor, score_beam_size: int = 3, keywords_to
         out.append([(p, i) for p, i in zip(pr, ix)
                     if p > min_prob and i >= 0 and (keywords_tokenset is None or i in keywords_tokenset)])
     return out
+
+
+def _cuda_f32(probs: torch.Tensor, what: str) -> torch.Tensor:
+    if not isinstance(probs, torch.Tensor) or not probs.is_cuda or probs.dtype != torch.float32 or probs.dim() != 3:
+        raise ValueError(f"{what}: probs must be a (B, T, V) float32 tensor on a ROCm device (no CPU fallback)")
+    return probs.contiguous()
+
+
+def _keyword_lists(keywords) -> Tuple[List[str], List[Tuple[int, ...]]]:
+    """dict name -> token ids (insertion order), or a sequence of token-id sequences (named by their index)."""
+    if isinstance(keywords, dict):
+        names, toks = list(keywords), [tuple(int(x) for x in v) for v in keywords.values()]
+    else:
+        toks = [tuple(int(x) for x in v) for v in keywords]
+        names = list(range(len(toks)))
+    return names, toks
+
+
+class _Handle:
+    """One ``wekws_hip_ctc_kws`` object."""
+
+    def __init__(self, device: int, vocab: int, keywords: Sequence[Tuple[int, ...]], tokenset, score_beam: int,
+                 path_beam: int, threshold: float = 0.0, min_frames: int = 5, max_frames: int = 250,
+                 interval_frames: int = 50, downsampling: int = 1, max_streams: int = 0, prefix_capacity: int = 1):
+        self.lib = _capi.load()
+        self.path_beam = int(path_beam)
+        flat = np.array([t for k in keywords for t in k] or [0], np.int32)
+        offs = np.array([0] + list(np.cumsum([len(k) for k in keywords])), np.int32)
+        ts = None if tokenset is None else np.array(sorted(int(x) for x in tokenset) or [0], np.int32)
+        d = _capi.CtcKwsDesc(vocab=int(vocab), score_beam=int(score_beam), path_beam=int(path_beam),
+                             num_keywords=len(keywords), keyword_tokens=flat.ctypes.data, keyword_offsets=offs.ctypes.data,
+                             token_set=None if ts is None else ts.ctypes.data,
+                             token_set_len=0 if tokenset is None else len(tokenset), min_frames=int(min_frames),
+                             max_frames=int(max_frames), interval_frames=int(interval_frames),
+                             downsampling=int(downsampling), max_streams=int(max_streams),
+                             prefix_capacity=int(prefix_capacity), device=int(device), threshold=float(threshold))
+        h = ctypes.c_void_p()
+        _capi.check(self.lib.wekws_hip_ctc_kws_create(ctypes.byref(d), ctypes.byref(h)), "wekws_hip_ctc_kws_create")
+        self.h = h
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            self.lib.wekws_hip_ctc_kws_destroy(h)
+
+    def beam_bytes(self, cap: int) -> int:
+        return int(self.lib.wekws_hip_ctc_kws_beam_bytes(self.h, int(cap)))
+
+    def decode_beam(self, raw: np.ndarray, cap: int):
+        """One beam record -> [(prefix, pb, pnb, [(token, frame, prob), ...]), ...] in beam order."""
+        PB = self.path_beam
+        pbe = (PB + 1) & ~1
+        pc = PB * cap
+        cnt = int(raw[:4].view(np.int32)[0])
+        lens = raw[8:8 + 4 * PB].view(np.int32)
+        o = 8 + 4 * pbe
+        pb = raw[o:o + 8 * PB].view(np.float64)
+        pnb = raw[o + 8 * PB:o + 16 * PB].view(np.float64)
+        o += 16 * PB
+        tok = raw[o:o + 4 * pc].view(np.int32).reshape(PB, cap)
+        fr = raw[o + 4 * pc:o + 8 * pc].view(np.int32).reshape(PB, cap)
+        o += 8 * pc + 4 * (pc & 1)
+        pr = raw[o:o + 8 * pc].view(np.float64).reshape(PB, cap)
+        out = []
+        for e in range(cnt):
+            n = int(lens[e])
+            out.append((tuple(int(x) for x in tok[e, :n]), float(pb[e]), float(pnb[e]),
+                        [(int(tok[e, i]), int(fr[e, i]), float(pr[e, i])) for i in range(n)]))
+        return out
+
+
+def _results(res: torch.Tensor) -> np.ndarray:
+    return np.frombuffer(res.cpu().numpy().tobytes(), dtype=np.dtype([("status", "<i4"), ("valid", "<i4"), ("state", "<i4"),
+                                                                       ("keyword", "<i4"), ("start", "<i4"),
+                                                                       ("end", "<i4"), ("score", "<f8")]))
+
+
+def _search(probs, lengths, keywords, tokenset, score_beam_size, path_beam_size, want_beams: bool):
+    x = _cuda_f32(probs, "ctc decode")
+    B, T, V = x.shape
+    if V < 1:
+        raise ValueError("ctc decode: the vocabulary is empty")
+    dev = x.device
+    if lengths is None:
+        lens = torch.full((B,), T, dtype=torch.int32, device=dev)
+    else:
+        lens = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).reshape(-1)
+        if lens.numel() != B:
+            raise ValueError(f"ctc decode: {lens.numel()} lengths for {B} utterances")
+    hd = _Handle(dev.index or 0, V, keywords, tokenset, score_beam_size, path_beam_size)
+    res = torch.empty((B, 32), dtype=torch.uint8, device=dev)
+    cap = max(T, 1)
+    bb = hd.beam_bytes(cap)
+    beams = torch.empty((B, bb), dtype=torch.uint8, device=dev) if (want_beams and B) else None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    if B:
+        _capi.check(hd.lib.wekws_hip_ctc_kws_search(hd.h, x.data_ptr(), B, T, lens.data_ptr(), res.data_ptr(),
+                                                     beams.data_ptr() if beams is not None else None,
+                                                     ctypes.c_void_p(stream)), "wekws_hip_ctc_kws_search")
+    r = _results(res)
+    for b in range(B):
+        if r["status"][b] != 0:
+            raise ValueError(f"ctc decode: utterance {b} failed with status {int(r['status'][b])} "
+                             "(an infinite posterior, or a length outside 0..T)")
+    raw = beams.cpu().numpy() if beams is not None else None
+    return hd, r, raw, cap
+
+
+def ctc_prefix_beam_search(probs: torch.Tensor, lengths=None, keywords_tokenset=None, score_beam_size: int = 3,
+                           path_beam_size: int = 20):
+    """loss.py's ``ctc_prefix_beam_search`` over a batch: probs (B, T, V) posteriors on the device, lengths (B) valid
+    frames.  Returns, per utterance, the reference's n-best ``[(prefix, pb + pnb, [dict(token, frame, prob), ...]), ...]``."""
+    hd, r, raw, cap = _search(probs, lengths, [], keywords_tokenset, score_beam_size, path_beam_size, True)
+    out = []
+    for b in range(len(r)):
+        beam = hd.decode_beam(raw[b], cap)
+        out.append([(p, pb + pnb, [dict(token=t, frame=f, prob=q) for t, f, q in nodes]) for p, pb, pnb, nodes in beam])
+    return out
+
+
+def keyword_search(probs: torch.Tensor, lengths, keywords, score_beam_size: int = 3, path_beam_size: int = 20):
+    """score_ctc.py's per-utterance decision: the search with the keywords' token set (blank included), then the first
+    keyword found in the n-best.  Returns per utterance ``(keyword or None, hit_score, start frame, end frame)``."""
+    names, toks = _keyword_lists(keywords)
+    tokenset = {0} | {t for k in toks for t in k}
+    _, r, _, _ = _search(probs, lengths, toks, tokenset, score_beam_size, path_beam_size, False)
+    return [(names[int(x["keyword"])] if x["state"] else None, float(x["score"]), int(x["start"]), int(x["end"]))
+            for x in r]
+
+
+class StreamingKeywordSpotter:
+    """``KeyWordSpotter`` (wekws/bin/stream_kws_ctc.py) after the model, for ``num_streams`` streams on one device.
+
+    ``step(probs, frames=None, streams=None)``: probs (B, T, V) posteriors on the device (``forward_softmax``'s output),
+    row b continuing stream ``streams[b]`` (default: 0 .. B-1) with its first ``frames[b]`` frames (default T).  Returns,
+    per row, ``KeyWordSpotter.forward``'s result dict (``{}`` for a row without frames); a stream that failed (an infinite
+    posterior, a prefix beyond ``prefix_capacity``) returns ``{"status": code}`` until ``reset`` / ``reset_all``."""
+
+    def __init__(self, num_streams: int, keywords, threshold: float, min_frames: int = 5, max_frames: int = 250,
+                 interval_frames: int = 50, score_beam: int = 3, path_beam: int = 20, downsampling: int = 1,
+                 frame_shift_ms: float = 10, vocab: Optional[int] = None, prefix_capacity: Optional[int] = None,
+                 device=None):
+        self.names, toks = _keyword_lists(keywords)
+        self.num_streams = int(num_streams)
+        self.resolution = frame_shift_ms / 1000
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.vocab = vocab
+        self._cfg = dict(keywords=toks, tokenset={0} | {t for k in toks for t in k}, score_beam=score_beam,
+                         path_beam=path_beam, threshold=threshold, min_frames=min_frames, max_frames=max_frames,
+                         interval_frames=interval_frames, downsampling=downsampling, max_streams=num_streams,
+                         prefix_capacity=prefix_capacity or max(256, 2 * max_frames + 64))
+        self._hd = None
+        if vocab is not None:
+            self._create(vocab)
+
+    def _create(self, vocab: int):
+        c = self._cfg
+        self._hd = _Handle(self.device.index or 0, vocab, c["keywords"], c["tokenset"], c["score_beam"], c["path_beam"],
+                           c["threshold"], c["min_frames"], c["max_frames"], c["interval_frames"], c["downsampling"],
+                           c["max_streams"], c["prefix_capacity"])
+        self.vocab = vocab
+
+    def _ids(self, streams, n: int) -> torch.Tensor:
+        ids = list(range(n)) if streams is None else [int(s) for s in (streams.tolist() if hasattr(streams, "tolist") else streams)]
+        if len(ids) != n:
+            raise ValueError(f"{len(ids)} stream ids for {n} rows")
+        if len(set(ids)) != len(ids) or any(s < 0 or s >= self.num_streams for s in ids):
+            raise ValueError(f"stream ids must be distinct and in 0..{self.num_streams - 1}")
+        return torch.tensor(ids, dtype=torch.int32, device=self.device)
+
+    def step(self, probs: torch.Tensor, frames=None, streams=None) -> List[Dict]:
+        return [self._dict(r) for r in self.step_records(probs, frames, streams)]
+
+    def _dict(self, r) -> Dict:
+        if r["status"] != 0:
+            return {"status": int(r["status"])}
+        if not r["valid"]:
+            return {}
+        on = bool(r["state"])
+        return {"state": 1 if on else 0, "keyword": self.names[int(r["keyword"])] if on else None,
+                "start": int(r["start"]) * self.resolution if on else None,
+                "end": int(r["end"]) * self.resolution if on else None, "score": float(r["score"]) if on else None}
+
+    def step_records(self, probs: torch.Tensor, frames=None, streams=None) -> np.ndarray:
+        """``step`` returning the raw result records (status, valid, state, keyword, start, end, score) -- hit_score and
+        the last detection included when the stream did not activate."""
+        x = _cuda_f32(probs, "StreamingKeywordSpotter.step")
+        B, T, V = x.shape
+        if self._hd is None:
+            if V < 1:
+                raise ValueError("StreamingKeywordSpotter.step: the vocabulary is empty")
+            self._create(V)
+        if V != self.vocab:
+            raise ValueError(f"StreamingKeywordSpotter.step: vocabulary {V}, the spotter has {self.vocab}")
+        ids = self._ids(streams, B)
+        if frames is None:
+            fr = torch.full((B,), T, dtype=torch.int32, device=self.device)
+        else:
+            fr = torch.as_tensor(frames).to(device=self.device, dtype=torch.int32).reshape(-1)
+            if fr.numel() != B or bool(((fr < 0) | (fr > T)).any()):
+                raise ValueError(f"frames must be {B} counts in 0..{T}")
+        res = torch.empty((B, 32), dtype=torch.uint8, device=self.device)
+        if B:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _capi.check(self._hd.lib.wekws_hip_ctc_kws_step(self._hd.h, x.data_ptr(), B, T, ids.data_ptr(), fr.data_ptr(),
+                                                            res.data_ptr(), ctypes.c_void_p(stream)),
+                        "wekws_hip_ctc_kws_step")
+        return _results(res)
+
+    def _reset(self, streams, all_: int):
+        if self._hd is None:
+            return
+        ids = self._ids(streams, len(streams) if streams is not None else self.num_streams)
+        if ids.numel():
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _capi.check(self._hd.lib.wekws_hip_ctc_kws_reset(self._hd.h, ids.data_ptr(), ids.numel(), all_,
+                                                             ctypes.c_void_p(stream)), "wekws_hip_ctc_kws_reset")
+
+    def reset(self, streams=None):
+        """KeyWordSpotter.reset() of the given streams (default all): the beam, activation and hit_score."""
+        self._reset(streams, 0)
+
+    def reset_all(self, streams=None):
+        """KeyWordSpotter.reset_all(): reset() plus the frame offset and the last activation."""
+        self._reset(streams, 1)
+
+    def beams(self, stream: int):
+        """The stream's cur_hyps: [(prefix, pb, pnb, [(token, frame, prob), ...]), ...] in beam order."""
+        if self._hd is None:
+            return [((), 1.0, 0.0, [])]
+        if not 0 <= int(stream) < self.num_streams:
+            raise ValueError(f"stream id {stream} outside 0..{self.num_streams - 1}")
+        cap = self._cfg["prefix_capacity"]
+        buf = torch.empty(self._hd.beam_bytes(cap), dtype=torch.uint8, device=self.device)
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        _capi.check(self._hd.lib.wekws_hip_ctc_kws_read_beam(self._hd.h, int(stream), buf.data_ptr(), ctypes.c_void_p(s)),
+                    "wekws_hip_ctc_kws_read_beam")
+        return self._hd.decode_beam(buf.cpu().numpy(), cap)
+
+    def status(self, stream: int) -> int:
+        if self._hd is None:
+            return 0
+        out = ctypes.c_int32()
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        _capi.check(self._hd.lib.wekws_hip_ctc_kws_status(self._hd.h, int(stream), ctypes.byref(out), ctypes.c_void_p(s)),
+                    "wekws_hip_ctc_kws_status")
+        return int(out.value)
