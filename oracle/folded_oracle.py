@@ -1,7 +1,9 @@
 """numpy evaluator of the FOLDED weight blob (the layout include/wekws_hip.h documents)  --  TEST
 INFRASTRUCTURE, NOT PRODUCT.  It lets the CPU suite check the host packer (BatchNorm / CMVN folding, blob
 order, descriptor) against the unfolded oracle without a GPU: pack() -> this evaluator must reproduce
-oracle/kws_oracle.forward.  Conv backbones, GRU and FSMN, one-shot (empty cache) only."""
+oracle/kws_oracle.forward.  Conv backbones, GRU and FSMN; an incoming cache for the conv backbones only.  Its fp16 modes are the
+arithmetic of the single-fp16-product kernels (and of a split product with a term dropped), to show the tight parity bar of
+tests/helpers.py can tell them from exact fp32."""
 import numpy as np
 
 from oracle import kws_oracle as ko
@@ -41,18 +43,24 @@ def _fsmn(desc, r, x):
     return y
 
 
-def forward(desc, blob, x, mm_dtype=None):
+def forward(desc, blob, x, mm_dtype=None, rounds="both", in_cache=None, with_cache=False):
     """mm_dtype=np.float16 restates WEKWS_HIP_PRECISION_F16 (include/wekws_hip.h): both operands of the input Linear
     and of every pointwise convolution are rounded to fp16 before the (fp32-accumulated) product; everything else
-    stays float32.  DS-TCN / MDTC only."""
+    stays float32 (the plain TCN: the operands of its dense convolution, which dense_stack_f16.hip.h runs on the matrix
+    cores).  rounds="weights" rounds the weights of those products only: the arithmetic of an F16X3 product
+    (hi(w) hi(x) + hi(w) lo(x) + lo(w) hi(x)) that drops its lo(w) * x term.  Conv backbones only.
+    in_cache: the incoming cache of a conv backbone (B, C, sum of paddings); with_cache: return (y, out_cache)."""
     r = _Reader(blob)
     if desc["backbone"] == 4:
+        assert in_cache is None and not with_cache
         return _fsmn(desc, r, x)
-    q = (lambda a: a) if mm_dtype is None else (lambda a: np.asarray(a, F32).astype(mm_dtype).astype(F32))
-    assert mm_dtype is None or desc["backbone"] in (0, 2)
+    assert rounds in ("both", "weights")
+    qw = (lambda a: a) if mm_dtype is None else (lambda a: np.asarray(a, F32).astype(mm_dtype).astype(F32))
+    q = qw if rounds == "both" else (lambda a: a)
+    assert mm_dtype is None or desc["backbone"] in (0, 1, 2)
     C, I, K, ks = desc["hdim"], desc["idim"], desc["odim"], desc["kernel_size"]
     W, b = r.take(C, I), r.take(C)
-    h = ko.linear(q(np.asarray(x, F32)), q(W), b)
+    h = ko.linear(q(np.asarray(x, F32)), qw(W), b)
     if desc["preproc_relu"]:
         h = ko.relu(h)
     bb = desc["backbone"]
@@ -68,18 +76,21 @@ def forward(desc, blob, x, mm_dtype=None):
             dils = [1] + [2 ** j for _ in range(desc["num_stack"]) for j in range(desc["stack_size"])]
         else:
             dils = [2 ** i for i in range(desc["num_layers"])]
-        z = None
+        z, off, caches = None, 0, []
         for bi, d in enumerate(dils):
-            u, _ = ko.causal_concat(h, None, (ks - 1) * d)
+            pad = (ks - 1) * d
+            u, c_out = ko.causal_concat(h, None if in_cache is None else in_cache[:, :, off:off + pad], pad)
+            caches.append(c_out)
+            off += pad
             if bb == 0:
                 a = ko.relu(ko.depthwise_conv(u, r.take(C, 1, ks), r.take(C), d))
-                h = ko.relu(ko.pointwise_conv(q(a), q(r.take(C, C, 1)), r.take(C))) + h
+                h = ko.relu(ko.pointwise_conv(q(a), qw(r.take(C, C, 1)), r.take(C))) + h
             elif bb == 1:
-                h = ko.relu(ko.full_conv(u, r.take(C, C, ks), r.take(C), d)) + h
+                h = ko.relu(ko.full_conv(q(u), qw(r.take(C, C, ks)), r.take(C), d)) + h
             else:
                 a = ko.depthwise_conv(u, r.take(C, 1, ks), r.take(C), d)
-                a = ko.relu(ko.pointwise_conv(q(a), q(r.take(C, C, 1)), r.take(C)))
-                h = ko.relu(ko.pointwise_conv(q(a), q(r.take(C, C, 1)), r.take(C)) + h)
+                a = ko.relu(ko.pointwise_conv(q(a), qw(r.take(C, C, 1)), r.take(C)))
+                h = ko.relu(ko.pointwise_conv(q(a), qw(r.take(C, C, 1)), r.take(C)) + h)
                 if bi > 0 and (bi - 1) % desc["stack_size"] == desc["stack_size"] - 1:
                     z = h.copy() if z is None else z + h
         h = np.transpose(z if bb == 2 else h, (0, 2, 1))
@@ -93,4 +104,8 @@ def forward(desc, blob, x, mm_dtype=None):
     else:
         y = h
     assert r.p == r.b.size, "blob not fully consumed"
-    return ko.sigmoid(y) if desc["activation"] == 1 else y
+    y = ko.sigmoid(y) if desc["activation"] == 1 else y
+    if with_cache:
+        assert bb != 3
+        return y, np.concatenate(caches, axis=2)
+    return y

@@ -152,3 +152,73 @@ def random_config_spec(cfg):
     spec = pack.model_spec(cfg)
     cmvn = [s for s in spec if s[0].startswith("global_cmvn.")]
     return [s for s in spec if not s[0].startswith("global_cmvn.")] + cmvn
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The tight bar: a result against the FLOAT64 evaluation of the same function (oracle/kws_oracle.py, dtype=np.float64).
+#   * posteriors / probabilities (sigmoid or softmax outputs): absolute error;
+#   * logits, pooled heads and caches: per channel, |got - ref| <= k * S_c with S_c = max(max over the other axes of |ref| in
+#     channel c, 2^-10 * max|ref|) -- a channel that is small next to the others is held to its own magnitude, not to the
+#     largest element of the tensor.
+# One k for every exact-f32 and split-fp16 (F16X3, three fp16 products) route.  The single-fp16-product routes (precision F16)
+# keep their own comparison (F16_TOL against folded_oracle's fp16-operand emulation).  TIGHT_K is calibrated from both sides:
+#   * CPU, every row of tests/route_matrix.py (tests/test_route.py::test_tight_bar_separates_f32_from_one_fp16_product): the
+#     float32 oracle reaches 6.4e-6 (the 2599-class CTC head, whose logits cancel in some classes -- why 2^-17 is too tight for a
+#     correct float32 evaluation), ATen float32 likewise; both fp16 emulations miss by 2.9e-4 at least;
+#   * GPU, every row (tests/test_hip_route_matrix.py): at most 4.0e-6 (ds256_mm, the CTC heads), 9.7e-7 on every other family;
+#     every one-fp16-product control at least 12x the bar.
+# 2^-15 (3.05e-5): 7.6x the largest measured kernel error, 4.8x the float32 oracle's, 9.6x below the fp16 emulations.
+TIGHT_K = 2.0 ** -15
+F16_TOL = 5e-4
+CHANNEL_FLOOR = 2.0 ** -10
+
+
+def tight_error(got, ref, axis=None):
+    """max |got - ref| / S_c (axis: the channel axis) or max |got - ref| (axis None: probabilities), in float64."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    if not got.size:
+        return 0.0
+    if not np.isfinite(got).all():
+        return float("inf")
+    d = np.abs(got - ref)
+    if axis is None:
+        return float(d.max())
+    axis = axis % ref.ndim
+    other = tuple(i for i in range(ref.ndim) if i != axis)
+    a = np.abs(ref)
+    s = np.maximum(a.max(axis=other, keepdims=True), CHANNEL_FLOOR * float(a.max()))
+    s = np.where(s > 0, s, 1.0)
+    return float((d / s).max())
+
+
+def y_axis(cfg, softmax=False):
+    """The tight bar's channel axis of y: None for posteriors (sigmoid head, softmax), the class axis for logits / pooled heads."""
+    from oracle.kws_oracle import classifier_kind
+    _, act = classifier_kind(cfg)
+    return None if (softmax or act == "sigmoid" or cfg.get("_exported_softmax")) else -1
+
+
+def cache_axis(cfg):
+    """The channel axis of the cache: (L, B, H) for the GRU, (B, C, P) / (B, D, P, L) for the conv backbones and FSMN."""
+    return -1 if cfg["backbone"]["type"] == "gru" else 1
+
+
+def oracle64(cfg, sd, x, in_cache=None, chunks=None, softmax=False):
+    """The float64 oracle: one-shot or in chunks carrying the cache, like tests/test_hip_parity.py::run."""
+    from oracle import kws_oracle
+    if chunks:
+        ys, c, t = [], in_cache, 0
+        for n in chunks:
+            y, c = kws_oracle.forward(cfg, sd, x[:, t:t + n], c, softmax=softmax, dtype=np.float64)
+            ys.append(y)
+            t += n
+        return np.concatenate(ys, axis=1), c
+    return kws_oracle.forward(cfg, sd, x, in_cache, softmax=softmax, dtype=np.float64)
+
+
+def tight_errors(cfg, y, c, ry, rc, softmax=False):
+    """(y error, cache error) under the tight bar; c / rc may be None."""
+    ey = tight_error(y, ry, y_axis(cfg, softmax))
+    ec = 0.0 if c is None else tight_error(c, rc, cache_axis(cfg))
+    return ey, ec

@@ -16,8 +16,8 @@ import torch
 
 from oracle import kws_oracle
 from tests.golden.cases import GENERIC_CASES, shape_case_config
-from tests.helpers import CASES, case_in_cache, case_input, case_weights, max_abs
-from tests.test_hip_parity import build, run, tol_for
+from tests.helpers import CASES, case_in_cache, case_input, case_weights, max_abs, oracle64
+from tests.test_hip_parity import build, check_tight, run, tol_for
 from wekws_amd.utils import synth
 
 pytestmark = pytest.mark.gpu
@@ -45,11 +45,15 @@ def test_any_shape_vs_live_reference_goldens(case, generic_golden, error_report)
     error_report[f"generic/{name}/cache_rel"] = max_abs(c, gc) / max(1.0, float(np.abs(gc).max()))
     assert max_abs(y, gy) <= tol_for(gy), max_abs(y, gy)
     assert max_abs(c, gc) <= tol_for(gc), max_abs(c, gc)
+    ry, rc = oracle64(cfg, sd, x)
+    check_tight(error_report, f"generic/{name}", cfg, y, c, ry, rc)
     if case.get("split"):
         t1 = case["split"]
         ys, cs = run(model, x, chunks=[t1, case["T"] - t1])
         assert max_abs(ys, g[name + "/y_stream"]) <= tol_for(gy)
         assert max_abs(cs, g[name + "/cache_stream"]) <= tol_for(gc)
+        rys, rcs = oracle64(cfg, sd, x, None, [t1, case["T"] - t1])
+        check_tight(error_report, f"generic/{name}/stream", cfg, ys, cs, rys, rcs)
 
 
 @pytest.mark.parametrize("case", [c for c in GENERIC_CASES if c.get("split")], ids=[c["name"] for c in GENERIC_CASES if c.get("split")])

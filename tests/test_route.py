@@ -1,48 +1,24 @@
 """CPU: the routing layer (wekws_amd/csrc/route.h) -- which shape a conv model runs as (as it is / zero-padded / any-shape path) and
 which kernel family serves a call -- swept WITHOUT a GPU through the hooks library's wekws_hip_debug_conv_route.  All three defects
 the round-5 fuzz found lived in this layer and needed a GPU to show; their configurations are explicit cases here, and the fuzz
-generator's configurations are swept against the invariants of every choice.  (The GPU side -- that wekws_hip_forward takes exactly
-the family this function names: it switches on its result; every family is parity-green in tests/test_hip_parity.py.)"""
+generator's configurations are swept against the invariants of every choice.  The route matrix (tests/route_matrix.py) predicts the
+route of every tile of calls at the edges of the choice; here each prediction is checked against route.h, the matrix against every
+route a sweep reaches, and the tight parity bar against both sides of its calibration.  (The GPU side -- that wekws_hip_forward takes
+exactly the predicted route, and meets the bar there: tests/test_hip_route_matrix.py.)"""
 import copy
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 from tests.helpers import random_model_config
-from wekws_amd import _capi, pack
+from tests.route_matrix import hooks_path, route, type_hooks
 from wekws_amd.utils import synth
-
-FAMILIES = ["none", "ds256_stream", "ds256_g32", "ds256_mm", "ds256_g16", "ds256_w16", "ds64_g4", "mdtc64_stream", "mdtc64_g4",
-            "mdtc64_w16", "mdtc32_g4", "dense_stack_f16", "conv_stack_f16", "conv_stack"]
-KEYS = ("plan", "C", "ks", "family", "nt", "split", "ctx", "fast", "grid", "threads", "lds", "utts_per_wg", "cache_len", "max_pad")
 
 
 @pytest.fixture(scope="module")
 def hooks():
-    path = os.path.join(os.path.dirname(_capi.lib_path()), "libwekws_hip_hooks.so")
-    lib = C.CDLL(path)
-    lib.wekws_hip_debug_conv_route.restype = C.c_int
-    lib.wekws_hip_debug_conv_route.argtypes = [C.POINTER(_capi.Desc), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                               C.c_char_p, C.c_int]
-    return lib
-
-
-def route(lib, cfg, B, T, has_in=False, has_out=True, precision="default", x16=1, cache16=1, cus=256, ntiles=1, opts=None):
-    cfg = dict(cfg)
-    cfg["_precision"] = precision
-    d = _capi.make_desc(dict(pack.parse_config(cfg), abi_version=_capi.ABI_VERSION))
-    call = (C.c_int * 8)(B, T, ntiles, int(has_in), int(has_out), x16, cache16, cus)
-    out = (C.c_int * 14)()
-    why = C.create_string_buffer(256)
-    o = (C.c_int * 9)(*opts) if opts is not None else None
-    assert lib.wekws_hip_debug_conv_route(C.byref(d), o, call, out, why, 256) == 0
-    r = dict(zip(KEYS, list(out)))
-    r["family"] = FAMILIES[r["family"]]
-    r["plan"] = ["as_is", "padded", "generic"][r["plan"]]
-    r["why"] = why.value.decode()
-    return r
+    return type_hooks(C.CDLL(hooks_path()))
 
 
 M = synth.MODEL_CONFIGS
@@ -141,3 +117,127 @@ def test_fuzz_configurations_keep_the_invariants_of_every_choice(hooks, seed):
             assert r["ctx"] and r["nt"] >= 4 and head == "linear", what
         seen.add(r["family"])
     assert len(seen) >= 4
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the route matrix (tests/route_matrix.py)
+from tests import route_matrix as rm  # noqa: E402
+from tests.helpers import TIGHT_K, tight_errors  # noqa: E402
+
+ROW_IDS = [r["id"] for r in rm.ROWS]
+
+
+@pytest.mark.parametrize("row", rm.ROWS, ids=ROW_IDS)
+def test_route_matrix_predictions_are_route_h(hooks, row):
+    """Every tile's predicted route is what route.h chooses for the call the forward makes; the F16 rerun of a split row says one
+    fp16 product (split 0) exactly on the families that have that variant."""
+    assert rm.predict(hooks, row) == rm.EXPECT[row["id"]]
+    if rm.is_split_row(row):
+        _, f16 = rm.predict(hooks, row, "f16")
+        for t in (t for ch in f16 for t in ch):
+            assert not t.startswith("none") and t.endswith("split0") == (t.split()[0] in rm.ONE_PRODUCT), f16
+
+
+def _reachable(lib):
+    """Every (family, nt, ctx, fast, split, persistent) route.h reaches: the recipes over the calls at the edges of the choice, and
+    the fuzz generator's configurations (the sweep of test_fuzz_configurations_keep_the_invariants_of_every_choice)."""
+    import itertools
+    seen = {}
+    conv = [n for n, c in M.items() if c["backbone"]["type"] in ("tcn", "mdtc")]
+    cus = rm.CUS
+    for name in conv:
+        for B, T, hi, ho, p, x16, c16, nti in itertools.product((1, 2, 3, cus - 1, cus, cus + 1, 2 * cus + 1), (1, 16, 17, 32, 33, 64, 65, 112),
+                                                              (0, 1), (0, 1), ("default", "f32", "f16"), (0, 1), (0, 1), (1, 2)):
+            if nti == 2 and not ho:
+                continue
+            r = route(lib, M[name], B, T, has_in=hi, has_out=ho, precision=p, x16=x16, cache16=c16, ntiles=nti)
+            if r["family"] != "none":
+                seen.setdefault(rm.route_tuple(rm.route_str(r, B)), (name, B, T, hi, ho, p, x16, c16, nti))
+    for seed in range(40):
+        rng = np.random.default_rng([0x207E, seed])
+        for _ in range(120):
+            cfg, head = random_model_config(rng)
+            if cfg["backbone"]["type"] == "gru":
+                continue
+            B = int(rng.choice([1, 2, 3, 9, 260, 1024, 5000]))
+            kw = dict(B=B, T=int(rng.integers(1, 113)), has_in=bool(rng.integers(0, 2)))
+            kw.update(has_out=bool(rng.integers(0, 2)) or kw["has_in"], precision=str(rng.choice(["default", "f32", "f16"])),
+                      x16=int(rng.integers(0, 4) > 0), cache16=int(rng.integers(0, 4) > 0), cus=256)
+            r = route(lib, cfg, **kw)
+            if r["family"] != "none":
+                seen.setdefault(rm.route_tuple(rm.route_str(r, B)), (cfg, kw))
+    return seen
+
+
+def test_route_matrix_covers_every_reachable_route(hooks):
+    """A route.h change that adds a variant fails here until the matrix has a row that runs it on the GPU."""
+    have = set()
+    for row in rm.ROWS:
+        have.update(rm.route_tuple(t) for ch in rm.EXPECT[row["id"]][1] for t in ch)
+        if rm.is_split_row(row):                       # (the F16 negative control of the GPU test runs these rows once more)
+            have.update(rm.route_tuple(t) for ch in rm.predict(hooks, row, "f16")[1] for t in ch)
+    reach = _reachable(hooks)
+    missing = {t: reach[t] for t in reach if t not in have}
+    assert not missing, missing
+    assert len(reach) >= 140
+    plans = {rm.EXPECT[r["id"]][0] for r in rm.ROWS}
+    assert plans == {"as_is", "padded", "generic"}
+
+
+def test_route_matrix_rows_cover_the_edges():
+    rows = rm.ROWS
+    firsts = {r["chunks"][0] for r in rows} | {t for r in rows for t in r["chunks"]}
+    assert {1, 16, 17, 32, 33, 64, 65, 112, 113, 225} <= firsts
+    assert {rm.CUS - 1, rm.CUS, rm.CUS + 1, 2 * rm.CUS + 1} <= {r["B"] for r in rows}
+    assert any(r["B"] == 1 for r in rows)
+    upw = [(r["B"], t) for r in rows for ch in rm.EXPECT[r["id"]][1] for t in ch if "upw1" not in t]
+    assert any(B % 2 == 1 for B, _ in upw), upw
+    assert any(r["x_off"] for r in rows) and any(r["c_off"] and r["cache"] for r in rows)
+    assert {"ds_tcn_h256_ctc300", "ds_tcn_h256_ctc"} <= {r["model"] for r in rows}
+    assert any(r["cache"] for r in rows) and any(len(r["chunks"]) > 1 for r in rows)
+
+
+def _calibration_case(row, Bmax=4):
+    """The row's model, input (at most Bmax utterances: the bar is per element) and incoming cache."""
+    cfg = rm.row_config(row)
+    sd = rm.row_weights(row, cfg)
+    x = rm.row_input(row, cfg)[:Bmax]
+    c0 = rm.row_cache(row, cfg)
+    return cfg, sd, x, (None if c0 is None else c0[:Bmax])
+
+
+@pytest.mark.parametrize("row", rm.ROWS, ids=ROW_IDS)
+def test_tight_bar_separates_f32_from_one_fp16_product(row):
+    """The tight bar (tests/helpers.py::TIGHT_K), calibrated from both sides on every row's model, chunks and cache: the float32
+    numpy oracle and ATen float32 (oracle/torch_ref.py, where it has the model's head) PASS it against the float64 oracle; the
+    fp16-operand emulation (one fp16 product: precision F16) and the emulation that rounds only the weights of the input Linear and
+    the matrix convolutions to fp16 (an F16X3 product with its lo(w) * x term dropped) FAIL it."""
+    import torch
+    from oracle import folded_oracle, kws_oracle, torch_ref
+    from tests.helpers import oracle64
+    from wekws_amd import pack
+    cfg, sd, x, c0 = _calibration_case(row)
+    chunks = row["chunks"]
+    ry, rc = oracle64(cfg, sd, x, c0, chunks)
+    y32, c32 = kws_oracle.forward_streaming(cfg, sd, x, chunks, c0)
+    e32 = max(tight_errors(cfg, y32, c32, ry, rc))
+    assert e32 <= TIGHT_K / 4, e32                        # (the float32 oracle, with a margin of 4)
+    if "classifier" not in cfg:
+        tsd = {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}
+        ys, c, t = [], None if c0 is None else torch.from_numpy(c0), 0
+        with torch.no_grad():
+            for n in chunks:
+                y, c = torch_ref.forward(cfg, tsd, torch.from_numpy(x[:, t:t + n].copy()), c)
+                ys.append(y)
+                t += n
+        et = max(tight_errors(cfg, torch.cat(ys, 1).numpy(), c.numpy(), ry, rc))
+        assert et <= TIGHT_K / 4, et
+    desc, blob = pack.pack(cfg, sd)
+    for rounds in ("both", "weights"):
+        ys, c, t = [], c0, 0
+        for n in chunks:
+            y, c = folded_oracle.forward(desc, blob, x[:, t:t + n], mm_dtype=np.float16, rounds=rounds, in_cache=c, with_cache=True)
+            ys.append(y)
+            t += n
+        e16 = max(tight_errors(cfg, np.concatenate(ys, 1), c, ry, rc))
+        assert e16 > 4 * TIGHT_K, (rounds, e16)

@@ -153,7 +153,11 @@ inline Route select_conv_route(const wekws_hip_desc& d, const RouteFlags& f, con
   const bool pooled = d.head == WEKWS_HIP_HEAD_GLOBAL || d.head == WEKWS_HIP_HEAD_LAST;
   auto fail = [&](const char* why) { r = Route{}; r.why_not = why; return r; };
   auto done = [&](int family, int nt_, bool ctx, bool fast, int grid, int threads, int lds, int upw) {
-    r.family = family; r.nt = nt_; r.split = o.split; r.ctx = ctx; r.fast = fast; r.grid = grid; r.threads = threads; r.lds_bytes = lds;
+    // split 0 (one fp16 product) only where the family HAS that variant: ds256_mm, dense_stack_f16 and conv_stack_f16 run their
+    // three products whatever the precision asks (tests/test_hip_route_matrix.py's F16 control tells the two apart on the device)
+    const bool one_product = family == ROUTE_DS256_STREAM || family == ROUTE_DS256_G16 || family == ROUTE_DS256_W16 || family == ROUTE_DS64_G4 ||
+                             family == ROUTE_MDTC64_STREAM || family == ROUTE_MDTC64_G4 || family == ROUTE_MDTC64_W16 || family == ROUTE_MDTC32_G4;
+    r.family = family; r.nt = nt_; r.split = o.split || !one_product; r.ctx = ctx; r.fast = fast; r.grid = grid; r.threads = threads; r.lds_bytes = lds;
     r.utts_per_wg = upw;
     return r;
   };

@@ -399,6 +399,15 @@ static bool nf_fix_all() {
   return v;
 }
 static thread_local wekws::Route g_last_route{};             // the route of this thread's last conv launch (tests: hooks build)
+#ifdef WEKWS_TEST_HOOKS
+// the route of EVERY tile of this thread's last forward (wekws_hip_debug_route_trace; hooks build only)
+enum : int { kTraceOther = 0, kTraceConv = 1, kTraceAnyShape = 2, kTraceMaxTiles = 256 };
+struct RouteTrace {
+  int path = kTraceOther, ntiles = 0;
+  wekws::Route tile[kTraceMaxTiles];
+};
+static thread_local RouteTrace g_route_trace;
+#endif
 static wekws::RouteOptions route_options(const wekws_hip_model* m) {
   wekws::RouteOptions o;
   o.w16_ok = m->w16_ok; o.g16_ok = m->g16_ok; o.g16_ctx = m->g16_ctx; o.g16_one_pass = m->g16_one_pass; o.stream_ok = m->stream_ok;
@@ -1644,6 +1653,24 @@ extern "C" int wekws_hip_debug_last_route(int* out) {
   out[8] = r.utts_per_wg;
   return WEKWS_HIP_OK;
 }
+// the route of every tile of the calling thread's last forward: out[0] = path (0: no conv kernel ran -- GRU / FSMN, or no forward
+// yet; 1: the conv routes of route.h; 2: the any-shape path of generic.hip.h), out[1] = tiles of the call, then per tile (at most
+// max_tiles, and the first 256 of a call) the 9 values of wekws_hip_debug_last_route.  out holds 2 + 9 * max_tiles ints.  Returns
+// the number of tile records written.
+extern "C" int wekws_hip_debug_route_trace(int* out, int max_tiles) {
+  if (!out || max_tiles < 0) return WEKWS_HIP_EINVAL;
+  const RouteTrace& t = g_route_trace;
+  out[0] = t.path; out[1] = t.ntiles;
+  int n = t.ntiles < kTraceMaxTiles ? t.ntiles : kTraceMaxTiles;
+  n = n < max_tiles ? n : max_tiles;
+  for (int i = 0; i < n; ++i) {
+    const wekws::Route& r = t.tile[i];
+    int* o = out + 2 + 9 * i;
+    o[0] = r.family; o[1] = r.nt; o[2] = r.split; o[3] = r.ctx; o[4] = r.fast; o[5] = r.grid; o[6] = r.threads; o[7] = r.lds_bytes;
+    o[8] = r.utts_per_wg;
+  }
+  return n;
+}
 extern "C" int wekws_hip_debug_hog(int device, int blocks, int ms, void* stream_) {
   DeviceGuard guard(device);
   const int busy = ms < 0;
@@ -1669,6 +1696,10 @@ int wekws_hip_forward(wekws_hip_model* m, const float* x, int B, int T, const fl
   if (!guard.ok) return fail(WEKWS_HIP_EDEVICE, "hipSetDevice(%d)", m->device);
   const wekws_hip_desc& d = m->desc;
   const bool per_frame = d.head == WEKWS_HIP_HEAD_LINEAR || d.head == WEKWS_HIP_HEAD_IDENTITY;
+#ifdef WEKWS_TEST_HOOKS
+  g_route_trace.path = m->generic ? kTraceAnyShape : kTraceOther;
+  g_route_trace.ntiles = 0;
+#endif
 
   if (m->generic) {
     char* base = stream_workspace(m, stream, workspace_need(m, B, T));
@@ -1822,6 +1853,11 @@ int wekws_hip_forward(wekws_hip_model* m, const float* x, int B, int T, const fl
                                                           int(wekws::mdtc64_stream_lds_bytes(m->cache_len)));
       if (route.family == wekws::ROUTE_NONE) return fail(WEKWS_HIP_EUNSUPPORTED, "no kernel for this call: %s", route.why_not ? route.why_not : "?");
       g_last_route = route;
+#ifdef WEKWS_TEST_HOOKS
+      g_route_trace.path = kTraceConv;
+      if (g_route_trace.ntiles < kTraceMaxTiles) g_route_trace.tile[g_route_trace.ntiles] = route;
+      ++g_route_trace.ntiles;
+#endif
       const bool split = route.split != 0;
       const int nt = route.nt;
       const int grid_cus = m->g16_one_pass ? (1 << 30) : m->fsmn_cus;   // persistent kernels: the largest grid
