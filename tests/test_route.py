@@ -99,7 +99,7 @@ def test_fuzz_configurations_keep_the_invariants_of_every_choice(hooks, seed):
         assert (r["plan"] == "padded") == (r["C"] != C0 or r["ks"] != ks0), what
         # every shape wekws_hip_create takes has a kernel for every call
         assert r["family"] != "none", what
-        assert r["nt"] in (1, 2, 4, 7) and 16 * r["nt"] >= T and 0 <= r["lds"] <= 160 * 1024 and r["threads"] in (128, 256, 512, 1024), what
+        assert r["nt"] in (1, 2, 4, 7) and 16 * r["nt"] >= T and 0 < r["lds"] <= 160 * 1024 and r["threads"] in (128, 256, 512, 1024), what
         assert r["grid"] >= 1 and r["grid"] * r["utts_per_wg"] >= min(B, r["grid"] * r["utts_per_wg"]), what
         if r["grid"] * r["utts_per_wg"] < B:                     # fewer workgroups than utterances: a persistent kernel
             assert r["family"] in ("ds256_g16", "ds256_g32") and r["fast"] and r["grid"] == 256, what

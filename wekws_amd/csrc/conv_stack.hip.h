@@ -35,13 +35,14 @@
 
 #include "nonfinite.hip.h"
 #include "pk_safe.hip.h"
+#include "route.h"
 
 namespace wekws {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is needed once per (kernel, device).  A launcher keeps one static
-// DynLdsGrant: the bytes already granted per device ordinal.  Thread-safe (two racing first calls both set the same
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is needed once per (kernel, device).  launch_dyn<kern> keeps one static
+// DynLdsGrant per kernel: the bytes already granted per device ordinal.  Thread-safe (two racing first calls both set the same
 // attribute, which is idempotent) and correct for a process that drives several GPUs -- a plain `static bool` is neither.
 constexpr int kMaxDevices = 64;
 struct DynLdsGrant {
@@ -57,6 +58,30 @@ inline int grant_dynamic_lds(K kern, int bytes, DynLdsGrant& g) {
   g.bytes[dev].store(bytes, std::memory_order_release);
   return 0;
 }
+
+// Launches `kern` as the route says: r.grid (x gy) workgroups of r.threads, r.lds_bytes of dynamic LDS (granted once per
+// kernel and device).  threads / lds: the kernel's own; a route that disagrees with them is refused (-4, an internal error).
+template <auto kern, class... Args>
+inline int launch_dyn(const Route& r, int threads, size_t lds, int gy, hipStream_t stream, const Args&... args) {
+  if (r.threads != threads || size_t(r.lds_bytes) != lds) return -4;
+  static DynLdsGrant grant;
+  if (grant_dynamic_lds(kern, int(lds), grant)) return -3;
+  hipLaunchKernelGGL(kern, dim3(r.grid, gy), dim3(r.threads), lds, stream, args...);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// Compile-time fan-out: f(std::integral_constant<int, V>) for the V in Vs equal to v (-4 when none is), f(std::bool_constant<b>).
+// Launchers pick a kernel variant with `if constexpr` on these, so only the variants a route can name are instantiated.
+template <int... Vs, class F>
+inline int with_int(int v, F&& f) {
+  int rc = -4;
+  (void)((v == Vs && (rc = f(std::integral_constant<int, Vs>{}), true)) || ...);
+  return rc;
+}
+template <class F>
+inline int with_nt(int nt, F&& f) { return with_int<1, 2, 4, 7>(nt, f); }   // frame tiles: route_nt()
+template <class F>
+inline int with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 enum : int { KIND_DS = 0, KIND_TCN = 1, KIND_MDTC = 2 };
 enum : int { HEAD_LINEAR = 0, HEAD_GLOBAL = 1, HEAD_LAST = 2, HEAD_IDENTITY = 3 };
@@ -786,47 +811,31 @@ static __global__ __attribute__((unused)) void softmax_rows_kernel(float* y, int
   if (K4 + lane < K) p[K4 + lane] = __expf(p[K4 + lane] - gm) * inv;
 }
 
-// launcher implemented per KIND in conv_stack_{ds,tcn,mdtc}.hip
+// Runs the conv_stack route of a KIND backbone with C channels.  Defined below, instantiated once per KIND in
+// conv_stack_{ds,tcn,mdtc}.hip (the units compile in parallel).
 template <int KIND>
-int launch_conv_stack(int C, int nt, const StackParams& P, const CallArgs& A, hipStream_t stream);
-template <> int launch_conv_stack<KIND_DS>(int, int, const StackParams&, const CallArgs&, hipStream_t);
-template <> int launch_conv_stack<KIND_TCN>(int, int, const StackParams&, const CallArgs&, hipStream_t);
-template <> int launch_conv_stack<KIND_MDTC>(int, int, const StackParams&, const CallArgs&, hipStream_t);
+int launch_conv_stack_kind(const Route& r, int C, const StackParams& P, const CallArgs& A, hipStream_t stream);
+extern template int launch_conv_stack_kind<KIND_DS>(const Route&, int, const StackParams&, const CallArgs&, hipStream_t);
+extern template int launch_conv_stack_kind<KIND_TCN>(const Route&, int, const StackParams&, const CallArgs&, hipStream_t);
+extern template int launch_conv_stack_kind<KIND_MDTC>(const Route&, int, const StackParams&, const CallArgs&, hipStream_t);
 
-template <int KIND, int C, int NT>
-inline int launch_one(const StackParams& P, const CallArgs& A, hipStream_t stream) {
-  using G = Geom<KIND, C, NT>;
-  constexpr int KS = (KIND == KIND_MDTC) ? 5 : 8;  // the kernel sizes of the reference recipes (tcn.yaml / mdtc.yaml)
-  if (P.ksize != KS) return -4;
-  static DynLdsGrant grant;
-  auto kern = conv_stack_kernel<KIND, C, NT, KS>;
-  if (grant_dynamic_lds(kern, int(G::LDS_BYTES), grant)) return -3;
-  const int grid = (A.B + G::U - 1) / G::U;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), G::LDS_BYTES, stream, P, A);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+// kind: KIND_* (= the descriptor's WEKWS_HIP_BACKBONE_* of the conv backbones)
+inline int launch_conv_stack(const Route& r, int kind, int C, const StackParams& P, const CallArgs& A, hipStream_t stream) {
+  return kind == KIND_DS    ? launch_conv_stack_kind<KIND_DS>(r, C, P, A, stream)
+         : kind == KIND_TCN ? launch_conv_stack_kind<KIND_TCN>(r, C, P, A, stream)
+                            : launch_conv_stack_kind<KIND_MDTC>(r, C, P, A, stream);
 }
 
-#define WEKWS_DISPATCH_NT(KIND, CC)                                            \
-  switch (nt) {                                                                \
-    case 1: return launch_one<KIND, CC, 1>(P, A, stream);                      \
-    case 2: return launch_one<KIND, CC, 2>(P, A, stream);                      \
-    case 4: return launch_one<KIND, CC, 4>(P, A, stream);                      \
-    case 7: return launch_one<KIND, CC, 7>(P, A, stream);                      \
-    default: return -1;                                                        \
-  }
-
-// hidden dims with a compiled kernel: the reference recipes use 32 / 64 / 256 (128 for GRU);
-// MDTC keeps a second full-width tile in LDS, which does not fit at C = 256.
-#define WEKWS_DEFINE_LAUNCHER(KIND, WITH256)                                   \
-  template <>                                                                  \
-  int launch_conv_stack<KIND>(int C, int nt, const StackParams& P, const CallArgs& A, hipStream_t stream) { \
-    switch (C) {                                                               \
-      case 32: WEKWS_DISPATCH_NT(KIND, 32)                                     \
-      case 64: WEKWS_DISPATCH_NT(KIND, 64)                                     \
-      case 128: WEKWS_DISPATCH_NT(KIND, 128)                                   \
-      case 256: if constexpr (WITH256) { WEKWS_DISPATCH_NT(KIND, 256) } else return -4; \
-      default: return -4;                                                      \
-    }                                                                          \
-  }
+template <int KIND>
+int launch_conv_stack_kind(const Route& r, int C, const StackParams& P, const CallArgs& A, hipStream_t stream) {
+  constexpr int KS = KIND == KIND_MDTC ? 5 : 8;   // the kernel sizes of the reference recipes (tcn.yaml / mdtc.yaml)
+  return with_int<32, 64, 128, 256>(C, [&](auto c) {
+    return with_nt(r.nt, [&](auto nt) {
+      // MDTC keeps a second full-width tile in LDS, which does not fit at C = 256
+      if constexpr (KIND == KIND_MDTC && c == 256) return -4;
+      else return launch_dyn<conv_stack_kernel<KIND, c, nt, KS>>(r, kThreads, Geom<KIND, c, nt>::LDS_BYTES, 1, stream, P, A);
+    });
+  });
+}
 
 }  // namespace wekws

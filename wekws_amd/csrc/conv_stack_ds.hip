@@ -2,5 +2,5 @@
 // translation units compile in parallel).  See conv_stack.hip.h.
 #include "conv_stack.hip.h"
 namespace wekws {
-WEKWS_DEFINE_LAUNCHER(KIND_DS, true)
+template int launch_conv_stack_kind<KIND_DS>(const Route&, int, const StackParams&, const CallArgs&, hipStream_t);
 }  // namespace wekws

@@ -656,48 +656,30 @@ __global__ __launch_bounds__(kThreads, 2) void conv_stack_f16_kernel(const Stack
   conv_stack_head<KIND, C, NT>(P, A, hbuf, reinterpret_cast<float*>(slab), b0);
 }
 
+// Runs the conv_stack_f16 route of a KIND backbone with C channels; instantiated once per KIND in conv_stack_f16_{ds,tcn,mdtc}.hip.
 template <int KIND>
-int launch_conv_stack_f16(int C, int nt, const StackParams& P, const CallArgs& A, hipStream_t stream);
-template <> int launch_conv_stack_f16<KIND_DS>(int, int, const StackParams&, const CallArgs&, hipStream_t);
-template <> int launch_conv_stack_f16<KIND_TCN>(int, int, const StackParams&, const CallArgs&, hipStream_t);
-template <> int launch_conv_stack_f16<KIND_MDTC>(int, int, const StackParams&, const CallArgs&, hipStream_t);
+int launch_conv_stack_f16_kind(const Route& r, int C, const StackParams& P, const CallArgs& A, hipStream_t stream);
+extern template int launch_conv_stack_f16_kind<KIND_DS>(const Route&, int, const StackParams&, const CallArgs&, hipStream_t);
+extern template int launch_conv_stack_f16_kind<KIND_TCN>(const Route&, int, const StackParams&, const CallArgs&, hipStream_t);
+extern template int launch_conv_stack_f16_kind<KIND_MDTC>(const Route&, int, const StackParams&, const CallArgs&, hipStream_t);
 
-template <int KIND, int C, int NT>
-inline int launch_one_f16(const StackParams& P, const CallArgs& A, hipStream_t stream) {
-  using G = Geom<KIND, C, NT>;
-  constexpr int KS = (KIND == KIND_MDTC) ? 5 : 8;
-  if (P.ksize != KS) return -4;
-  if constexpr (KIND == KIND_TCN && C < 64) {
-    return -4;  // K = 8*C needs a double-buffered slab that does not fit Geom<> at C = 32; served by dense_stack_f16
-  } else {
-  static DynLdsGrant grant;
-  auto kern = conv_stack_f16_kernel<KIND, C, NT, KS>;
-  if (grant_dynamic_lds(kern, int(G::LDS_BYTES), grant)) return -3;
-  const int grid = (A.B + G::U - 1) / G::U;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), G::LDS_BYTES, stream, P, A);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-  }
+inline int launch_conv_stack_f16(const Route& r, int kind, int C, const StackParams& P, const CallArgs& A, hipStream_t stream) {
+  return kind == KIND_DS    ? launch_conv_stack_f16_kind<KIND_DS>(r, C, P, A, stream)
+         : kind == KIND_TCN ? launch_conv_stack_f16_kind<KIND_TCN>(r, C, P, A, stream)
+                            : launch_conv_stack_f16_kind<KIND_MDTC>(r, C, P, A, stream);
 }
 
-#define WEKWS_DISPATCH_NT_F16(KIND, CC)                                        \
-  switch (nt) {                                                                \
-    case 1: return launch_one_f16<KIND, CC, 1>(P, A, stream);                  \
-    case 2: return launch_one_f16<KIND, CC, 2>(P, A, stream);                  \
-    case 4: return launch_one_f16<KIND, CC, 4>(P, A, stream);                  \
-    case 7: return launch_one_f16<KIND, CC, 7>(P, A, stream);                  \
-    default: return -1;                                                        \
-  }
-
-#define WEKWS_DEFINE_LAUNCHER_F16(KIND, WITH256)                               \
-  template <>                                                                  \
-  int launch_conv_stack_f16<KIND>(int C, int nt, const StackParams& P, const CallArgs& A, hipStream_t stream) { \
-    switch (C) {                                                               \
-      case 32: WEKWS_DISPATCH_NT_F16(KIND, 32)                                 \
-      case 64: WEKWS_DISPATCH_NT_F16(KIND, 64)                                 \
-      case 128: WEKWS_DISPATCH_NT_F16(KIND, 128)                               \
-      case 256: if constexpr (WITH256) { WEKWS_DISPATCH_NT_F16(KIND, 256) } else return -4; \
-      default: return -4;                                                      \
-    }                                                                          \
-  }
+template <int KIND>
+int launch_conv_stack_f16_kind(const Route& r, int C, const StackParams& P, const CallArgs& A, hipStream_t stream) {
+  constexpr int KS = KIND == KIND_MDTC ? 5 : 8;
+  return with_int<32, 64, 128, 256>(C, [&](auto c) {
+    return with_nt(r.nt, [&](auto nt) {
+      // not built: MDTC at C = 256 (no room for its second tile); TCN at C = 32, where K = 8 C needs a double-buffered slab
+      // that does not fit Geom<> (dense_stack_f16 runs those)
+      if constexpr ((KIND == KIND_MDTC && c == 256) || (KIND == KIND_TCN && c < 64)) return -4;
+      else return launch_dyn<conv_stack_f16_kernel<KIND, c, nt, KS>>(r, kThreads, Geom<KIND, c, nt>::LDS_BYTES, 1, stream, P, A);
+    });
+  });
+}
 
 }  // namespace wekws

@@ -2,5 +2,5 @@
 // See conv_stack_f16.hip.h.
 #include "conv_stack_f16.hip.h"
 namespace wekws {
-WEKWS_DEFINE_LAUNCHER_F16(KIND_MDTC, false)
+template int launch_conv_stack_f16_kind<KIND_MDTC>(const Route&, int, const StackParams&, const CallArgs&, hipStream_t);
 }  // namespace wekws

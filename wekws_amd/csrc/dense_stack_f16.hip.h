@@ -431,42 +431,7 @@ __global__ __launch_bounds__(kThreads, 2) void dense_stack_f16_kernel(const Dens
   }
 }
 
-template <int KIND>
-int launch_dense_stack_f16(int C, int nt, const DenseParams& P, const CallArgs& A, hipStream_t stream);
-template <> int launch_dense_stack_f16<KIND_TCN>(int, int, const DenseParams&, const CallArgs&, hipStream_t);
-
-template <int KIND, int C, int NT>
-inline int launch_dense_one(const DenseParams& P, const CallArgs& A, hipStream_t stream) {
-  using D = DenseGeom<KIND, C, NT>;
-  constexpr int KS = 8;
-  if (P.ksize != KS) return -4;
-  if (D::LDS_BYTES > 160 * 1024) return -4;
-  static DynLdsGrant grant;
-  auto kern = dense_stack_f16_kernel<KIND, C, NT, KS>;
-  if (grant_dynamic_lds(kern, int(D::LDS_BYTES), grant)) return -3;
-  const int grid = (A.B + D::U - 1) / D::U;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), D::LDS_BYTES, stream, P, A);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-#define WEKWS_DISPATCH_NT_DENSE(KIND, CC)                                      \
-  switch (nt) {                                                                \
-    case 1: return launch_dense_one<KIND, CC, 1>(P, A, stream);                \
-    case 2: return launch_dense_one<KIND, CC, 2>(P, A, stream);                \
-    case 4: return launch_dense_one<KIND, CC, 4>(P, A, stream);                \
-    case 7: return launch_dense_one<KIND, CC, 7>(P, A, stream);                \
-    default: return -1;                                                        \
-  }
-
-#define WEKWS_DEFINE_LAUNCHER_DENSE(KIND)                                      \
-  template <>                                                                  \
-  int launch_dense_stack_f16<KIND>(int C, int nt, const DenseParams& P, const CallArgs& A, hipStream_t stream) { \
-    switch (C) {                                                               \
-      case 32: WEKWS_DISPATCH_NT_DENSE(KIND, 32)                               \
-      case 64: WEKWS_DISPATCH_NT_DENSE(KIND, 64)                               \
-      case 128: WEKWS_DISPATCH_NT_DENSE(KIND, 128)                             \
-      default: return -4;                                                      \
-    }                                                                          \
-  }
+// Runs the dense_stack_f16 route (TCN, C = 32 / 64 / 128); defined in dense_stack_f16_tcn.hip.
+int launch_dense_stack_f16(const Route& r, int C, const DenseParams& P, const CallArgs& A, hipStream_t stream);
 
 }  // namespace wekws

@@ -1,18 +1,16 @@
 // Instantiations of the register-resident DS-TCN h256 kernel.  See ds256_g16.hip.h.
 #include "ds256_g16.hip.h"
 namespace wekws {
-template <int NT>
-static int launch_nt(bool split, const StackParams& P, const CallArgs& A, hipStream_t stream, int cus) {
-  return split ? launch_ds256_g16_nts<NT, true>(P, A, stream, cus) : launch_ds256_g16_nts<NT, false>(P, A, stream, cus);
-}
-int launch_ds256_g16(int nt, bool split, const StackParams& P, const CallArgs& A, hipStream_t stream, int cus) {
-  if (P.ksize != 8) return -4;
-  switch (nt) {
-    case 1: return launch_nt<1>(split, P, A, stream, cus);
-    case 2: return launch_nt<2>(split, P, A, stream, cus);
-    case 4: return launch_nt<4>(split, P, A, stream, cus);
-    case 7: return launch_nt<7>(split, P, A, stream, cus);
-    default: return -1;
-  }
+int launch_ds256_g16(const Route& r, const StackParams& P, const CallArgs& A, hipStream_t stream) {
+  return with_nt(r.nt, [&](auto nt) {
+    return with_bool(r.split, [&](auto split) {
+      return with_bool(r.fast, [&](auto fast) {
+        return with_bool(r.ctx, [&](auto ctx) {
+          if constexpr (ctx && (!fast || nt < 4)) return -4;   // (no such context variant)
+          else return launch_dyn<ds256_g16_kernel<nt, split, fast, ctx>>(r, kW16Threads, W16Geom<nt>::LDS_BYTES, 1, stream, P, A);
+        });
+      });
+    });
+  });
 }
 }  // namespace wekws

@@ -721,32 +721,9 @@ __global__ __launch_bounds__(kW16Threads) void ds256_g16_kernel(const StackParam
   G16_PH_DUMP;                                               // (stamp builds: sums over this workgroup's utterances)
 }
 
-template <int NT, bool SPLIT, bool FAST, bool CTX = false>
-inline int launch_ds256_g16_ntsf(const StackParams& P, const CallArgs& A, hipStream_t stream, int grid) {
-  using G = W16Geom<NT>;
-  static DynLdsGrant grant;
-  auto kern = ds256_g16_kernel<NT, SPLIT, FAST, CTX>;
-  if (grant_dynamic_lds(kern, int(G::LDS_BYTES), grant)) return -3;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kW16Threads), G::LDS_BYTES, stream, P, A);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-template <int NT, bool SPLIT>
-inline int launch_ds256_g16_nts(const StackParams& P, const CallArgs& A, hipStream_t stream, int cus) {
-  const bool fast = P.head == HEAD_LINEAR && P.odim <= 2 && P.kpre16 <= 64 && 8 * 16 * NT <= kW16Threads &&
-                    P.idim % 8 == 0 && (reinterpret_cast<uintptr_t>(A.x) & 15) == 0 && A.xs_b % 4 == 0;   // = w16_x_vec_ok
-  if (A.in_cache) {                                          // a later chunk of a stream: the context variant, where one is built
-    if constexpr (NT >= 4) {
-      if (fast) return launch_ds256_g16_ntsf<NT, SPLIT, true, true>(P, A, stream, A.B < cus ? A.B : cus);
-    }
-    return -4;                                               // (other heads / feature layouts / shorter tiles: ds256_w16)
-  }
-  return fast ? launch_ds256_g16_ntsf<NT, SPLIT, true>(P, A, stream, A.B < cus ? A.B : cus)
-              : launch_ds256_g16_ntsf<NT, SPLIT, false>(P, A, stream, A.B);
-}
-
-// Calls whose blocks all have dilation 1, 2, 4 or 8 (the host checks; everything else: launch_ds256_w16): without an incoming
-// cache, or -- keyword heads, tiles of >= 64 columns -- with one (returns -4 where no context variant is built).  split: three fp16 products per MAC on hi/lo operands (F16X3) or one on the hi halves (F16).
-// cus: compute units of the device = the largest grid (persistent workgroups).
-int launch_ds256_g16(int nt, bool split, const StackParams& P, const CallArgs& A, hipStream_t stream, int cus);
+// Runs the ds256_g16 route: r.fast the keyword configuration (FAST above), r.ctx the context variant for a later chunk of a
+// stream (built for keyword heads and >= 4 tiles), split as in launch_ds256_w16.  A persistent grid (r.grid < B) loops over
+// utterances where FAST.  Defined in ds256_g16.hip.
+int launch_ds256_g16(const Route& r, const StackParams& P, const CallArgs& A, hipStream_t stream);
 
 }  // namespace wekws

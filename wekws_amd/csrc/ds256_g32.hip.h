@@ -308,8 +308,8 @@ __global__ __launch_bounds__(kW16Threads) void ds256_g32_kernel(const StackParam
   G16_PH_DUMP;
 }
 
-// nt: frame tiles (1 / 2 / 4 / 7); cus: compute units = the largest grid.  Returns -4 when the call is not one this kernel
-// takes (the caller then runs conv_stack_kernel).
-int launch_ds256_g32(int nt, const StackParams& P, const CallArgs& A, hipStream_t stream, int cus);
+// Runs the ds256_g32 route (built for the keyword configuration without an incoming cache; r.grid < B: persistent).
+// Defined in ds256_g32.hip.
+int launch_ds256_g32(const Route& r, const StackParams& P, const CallArgs& A, hipStream_t stream);
 
 }  // namespace wekws

@@ -1,14 +1,12 @@
 // Instantiations of the all-matrix-core DS-TCN h256 kernel.  See ds256_mm.hip.h.
 #include "ds256_mm.hip.h"
 namespace wekws {
-int launch_ds256_mm(int nt, const StackParams& P, const CallArgs& A, uint32_t head_a16, hipStream_t stream) {
-  if (P.ksize != 8) return -4;
-  switch (nt) {
-    case 1: return launch_ds256_mm_nt<1>(P, A, head_a16, stream);
-    case 2: return launch_ds256_mm_nt<2>(P, A, head_a16, stream);
-    case 4: return launch_ds256_mm_nt<4>(P, A, head_a16, stream);
-    case 7: return launch_ds256_mm_nt<7>(P, A, head_a16, stream);
-    default: return -1;
-  }
+int launch_ds256_mm(const Route& r, const StackParams& P, uint32_t head_a16, const CallArgs& A, hipStream_t stream) {
+  const int gy = A.head_slices > 1 ? A.head_slices : 1;
+  return with_nt(r.nt, [&](auto nt) {
+    return with_bool(r.ctx, [&](auto ctx) {
+      return launch_dyn<ds256_mm_kernel<nt, ctx>>(r, kW16Threads, MmGeom<nt>::LDS_BYTES, gy, stream, P, A, head_a16);
+    });
+  });
 }
 }  // namespace wekws

@@ -448,24 +448,7 @@ __global__ __launch_bounds__(kW16Threads) void ds256_mm_kernel(const StackParams
   }
 }
 
-template <int NT, bool HAS_CACHE>
-inline int launch_ds256_mm_ntc(const StackParams& P, const CallArgs& A, uint32_t head_a16, hipStream_t stream) {
-  using G = MmGeom<NT>;
-  static DynLdsGrant grant;
-  auto kern = ds256_mm_kernel<NT, HAS_CACHE>;
-  if (grant_dynamic_lds(kern, int(G::LDS_BYTES), grant)) return -3;
-  hipLaunchKernelGGL(kern, dim3(A.B, A.head_slices > 1 ? A.head_slices : 1), dim3(kW16Threads), G::LDS_BYTES, stream, P, A,
-                     head_a16);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-template <int NT>
-inline int launch_ds256_mm_nt(const StackParams& P, const CallArgs& A, uint32_t head_a16, hipStream_t stream) {
-  return A.in_cache ? launch_ds256_mm_ntc<NT, true>(P, A, head_a16, stream)
-                    : launch_ds256_mm_ntc<NT, false>(P, A, head_a16, stream);
-}
-
-// usable when: kernel size 8, every block's padding <= 56 frames, per-frame linear head with odim <= 16 (host checks)
-int launch_ds256_mm(int nt, const StackParams& P, const CallArgs& A, uint32_t head_a16, hipStream_t stream);
+// Runs the ds256_mm route; A.head_slices > 1 workgroups per utterance (gridDim.y) share a CTC-sized head.  Defined in ds256_mm.hip.
+int launch_ds256_mm(const Route& r, const StackParams& P, uint32_t head_a16, const CallArgs& A, hipStream_t stream);
 
 }  // namespace wekws

@@ -301,17 +301,7 @@ inline size_t ds256_stream_lds_bytes(int cache_len) {       // slab 16 KB + chun
   return size_t(8 * 2 * W16Geom<1>::PB) + size_t(W16Geom<1>::H_FLOATS) * 4 + size_t(256) * cache_len * 4;
 }
 
-template <bool SPLIT>
-inline int launch_ds256_stream_s(const StackParams& P, const CallArgs& A, hipStream_t stream) {
-  static DynLdsGrant grant;
-  const size_t lds = ds256_stream_lds_bytes(P.cache_len);
-  auto kern = ds256_stream_kernel<SPLIT>;
-  if (grant_dynamic_lds(kern, int(lds), grant)) return -3;
-  hipLaunchKernelGGL(kern, dim3(A.B), dim3(kW16Threads), lds, stream, P, A);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-// usable when: kernel size 8, A.T <= 16, the stream's cache fits LDS beside the chunk (host checks)
-int launch_ds256_stream(bool split, const StackParams& P, const CallArgs& A, hipStream_t stream);
+// Runs the ds256_stream route (a chunk of <= 16 frames, the stream's cache in LDS).  Defined in ds256_stream.hip.
+int launch_ds256_stream(const Route& r, const StackParams& P, const CallArgs& A, hipStream_t stream);
 
 }  // namespace wekws

@@ -408,26 +408,8 @@ __global__ __launch_bounds__(kW16Threads) void ds256_w16_kernel(const StackParam
 
 }
 
-template <int NT, bool HAS_CACHE, bool SPLIT>
-inline int launch_ds256_w16_ntc(const StackParams& P, const CallArgs& A, hipStream_t stream) {
-  using G = W16Geom<NT>;
-  static DynLdsGrant grant;
-  auto kern = ds256_w16_kernel<NT, HAS_CACHE, SPLIT>;
-  if (grant_dynamic_lds(kern, int(G::LDS_BYTES), grant)) return -3;
-  hipLaunchKernelGGL(kern, dim3(A.B), dim3(kW16Threads), G::LDS_BYTES, stream, P, A);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-template <int NT>
-inline int launch_ds256_w16_nt(bool split, const StackParams& P, const CallArgs& A, hipStream_t stream) {
-  if (split)
-    return A.in_cache ? launch_ds256_w16_ntc<NT, true, true>(P, A, stream)
-                      : launch_ds256_w16_ntc<NT, false, true>(P, A, stream);
-  return A.in_cache ? launch_ds256_w16_ntc<NT, true, false>(P, A, stream)
-                    : launch_ds256_w16_ntc<NT, false, false>(P, A, stream);
-}
-
-// split: three fp16 products per MAC on hi/lo operands (F16X3) or one on the hi halves (F16)
-int launch_ds256_w16(int nt, bool split, const StackParams& P, const CallArgs& A, hipStream_t stream);
+// Runs the ds256_w16 route (r.split: three fp16 products per MAC on hi/lo operands (F16X3) or one on the hi halves (F16);
+// r.ctx: an incoming cache).  Defined in ds256_w16.hip.
+int launch_ds256_w16(const Route& r, const StackParams& P, const CallArgs& A, hipStream_t stream);
 
 }  // namespace wekws

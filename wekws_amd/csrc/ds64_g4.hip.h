@@ -321,9 +321,7 @@ __global__ __launch_bounds__(kG4Threads, 4) void ds64_g4_kernel(const StackParam
   }
 }
 
-// Usable when (the host checks the model side: DS-TCN, hidden_dim 64, kernel size 8, dilations 1 / 2 / 4 / 8): no incoming
-// cache, features of <= 96 dims in whole aligned 8-float items, a per-frame linear head with one or two outputs.  Returns -4
-// otherwise (the caller then runs the generic kernel).
-int launch_ds64_g4(int nt, bool split, const StackParams& P, const CallArgs& A, hipStream_t stream);
+// Runs the ds64_g4 route (built for the keyword configuration; r.ctx: the context variant, >= 4 tiles).  Defined in ds64_g4.hip.
+int launch_ds64_g4(const Route& r, const StackParams& P, const CallArgs& A, hipStream_t stream);
 
 }  // namespace wekws

@@ -527,12 +527,8 @@ __global__ __launch_bounds__(C * 4, 4) void mdtc_g4_kernel(const StackParams P, 
   }
 }
 
-// Usable when (the host checks the model side: hidden_dim 64, kernel size 5, dilations 1 / 2 / 4 / 8, pads 4 d): no incoming
-// cache, features of <= 96 dims in whole aligned 8-float items, a per-frame linear head with one or two outputs or a pooled
-// (Global / Last) head whose hidden layer fits the LDS left over.
-// Returns -4 otherwise (the caller then runs mdtc64_w16).
-int launch_mdtc64_g4(int nt, bool split, const StackParams& P, const CallArgs& A, hipStream_t stream);
-// ... and hidden_dim 32 (mdtc_small.yaml): features of <= 64 dims
-int launch_mdtc32_g4(int nt, bool split, const StackParams& P, const CallArgs& A, hipStream_t stream);
+// Runs the mdtc64_g4 (C = 64) and mdtc32_g4 (C = 32) routes: keyword heads, or pooled (Global / Last) heads without an incoming
+// cache; r.ctx: the context variant (keyword heads, >= 4 tiles).  Defined in mdtc64_g4.hip.
+int launch_mdtc_g4(const Route& r, int C, const StackParams& P, const CallArgs& A, hipStream_t stream);
 
 }  // namespace wekws

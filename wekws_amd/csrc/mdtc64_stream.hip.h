@@ -17,7 +17,7 @@
 //   Three barriers per block.  Each role derives only the scales it needs from the LDS maxima cells.
 //
 // Usable when every block has dilation 1 / 2 / 4 / 8 (the reference recipes: stack_size 4, mdtc.py:181-198), kernel size
-// 5, <= 128 input features in whole 16-byte aligned octets; anything else runs the batch kernel on the chunk (host decides).
+// 5, <= 128 input features in whole 16-byte aligned octets; anything else runs the batch kernel on the chunk (route.h decides).
 #pragma once
 #include "mdtc64_w16.hip.h"
 
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kW16Threads) void mdtc64_stream_kernel(const StackP
   //      (one 8-feature item per thread: item = (stream, K step, k-octet, frame); a wave's items belong to one stream),
   //      the preprocessing fragments and the first block's constants
   const int nk = P.kpre16 / 32;                              // K steps of the input (40-d: 2, 80-d MFCC: 3; host: <= 4)
-  const int n4 = (C * Pc) >> 2, tot = U * n4;                // C * Pc % 4 == 0 (host checks)
+  const int n4 = (C * Pc) >> 2, tot = U * n4;                // C * Pc % 4 == 0 (route.h checks)
   const f32x4* csrc = reinterpret_cast<const f32x4*>(A.in_cache + int64_t(b0) * C * Pc);
   constexpr int kInFlight = 8;
   float cm[U] = {0.f, 0.f};
@@ -367,18 +367,7 @@ __global__ __launch_bounds__(kW16Threads) void mdtc64_stream_kernel(const StackP
 
 inline size_t mdtc64_stream_lds_bytes(int cache_len) { return MdtcStreamGeom::lds_bytes(cache_len); }
 
-template <bool SPLIT>
-inline int launch_mdtc64_stream_s(const StackParams& P, const CallArgs& A, hipStream_t stream) {
-  static DynLdsGrant grant;
-  const size_t lds = mdtc64_stream_lds_bytes(P.cache_len);
-  auto kern = mdtc64_stream_kernel<SPLIT>;
-  if (grant_dynamic_lds(kern, int(lds), grant)) return -3;
-  hipLaunchKernelGGL(kern, dim3((A.B + 1) / 2), dim3(kW16Threads), lds, stream, P, A);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-// streaming step (A.T <= 16) with both streams' caches resident in LDS.  The host checks (wekws_hip.hip): kernel size 5,
-// every dilation in {1, 2, 4, 8}, <= 128 input features, 64 * cache_len % 4 == 0, the caches fit into LDS.
-int launch_mdtc64_stream(bool split, const StackParams& P, const CallArgs& A, hipStream_t stream);
+// Runs the mdtc64_stream route (a chunk of <= 16 frames, both streams' caches in LDS).  Defined in mdtc64_stream.hip.
+int launch_mdtc64_stream(const Route& r, const StackParams& P, const CallArgs& A, hipStream_t stream);
 
 }  // namespace wekws

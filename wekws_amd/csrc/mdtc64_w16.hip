@@ -1,14 +1,13 @@
 // Instantiations of the 16-wave MDTC h64 kernel.  See mdtc64_w16.hip.h.
 #include "mdtc64_w16.hip.h"
 namespace wekws {
-int launch_mdtc64_w16(int nt, bool split, const StackParams& P, const CallArgs& A, hipStream_t stream) {
-  if (P.ksize != 5) return -4;
-  switch (nt) {
-    case 1: return launch_mdtc64_w16_nt<1>(split, P, A, stream);
-    case 2: return launch_mdtc64_w16_nt<2>(split, P, A, stream);
-    case 4: return launch_mdtc64_w16_nt<4>(split, P, A, stream);
-    case 7: return launch_mdtc64_w16_nt<7>(split, P, A, stream);
-    default: return -1;
-  }
+int launch_mdtc64_w16(const Route& r, const StackParams& P, const CallArgs& A, hipStream_t stream) {
+  return with_nt(r.nt, [&](auto nt) {
+    return with_bool(r.ctx, [&](auto ctx) {
+      return with_bool(r.split, [&](auto split) {
+        return launch_dyn<mdtc64_w16_kernel<nt, ctx, split>>(r, kW16Threads, M16Geom<nt>::LDS_BYTES, 1, stream, P, A);
+      });
+    });
+  });
 }
 }  // namespace wekws

@@ -443,26 +443,7 @@ __global__ __launch_bounds__(kW16Threads) void mdtc64_w16_kernel(const StackPara
   conv_stack_head<KIND_MDTC, 64, NT, kW16Threads, SS>(P, A, hbuf, reinterpret_cast<float*>(slab), b0);
 }
 
-template <int NT, bool HAS_CACHE, bool SPLIT>
-inline int launch_mdtc64_w16_ntc(const StackParams& P, const CallArgs& A, hipStream_t stream) {
-  using G = M16Geom<NT>;
-  static DynLdsGrant grant;
-  auto kern = mdtc64_w16_kernel<NT, HAS_CACHE, SPLIT>;
-  if (grant_dynamic_lds(kern, int(G::LDS_BYTES), grant)) return -3;
-  hipLaunchKernelGGL(kern, dim3((A.B + 1) / 2), dim3(kW16Threads), G::LDS_BYTES, stream, P, A);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-template <int NT>
-inline int launch_mdtc64_w16_nt(bool split, const StackParams& P, const CallArgs& A, hipStream_t stream) {
-  if (split)
-    return A.in_cache ? launch_mdtc64_w16_ntc<NT, true, true>(P, A, stream)
-                      : launch_mdtc64_w16_ntc<NT, false, true>(P, A, stream);
-  return A.in_cache ? launch_mdtc64_w16_ntc<NT, true, false>(P, A, stream)
-                    : launch_mdtc64_w16_ntc<NT, false, false>(P, A, stream);
-}
-
-// usable when: hidden_dim 64, kernel size 5 (host checks); split as in launch_ds256_w16
-int launch_mdtc64_w16(int nt, bool split, const StackParams& P, const CallArgs& A, hipStream_t stream);
+// Runs the mdtc64_w16 route (split and ctx as in launch_ds256_w16).  Defined in mdtc64_w16.hip.
+int launch_mdtc64_w16(const Route& r, const StackParams& P, const CallArgs& A, hipStream_t stream);
 
 }  // namespace wekws

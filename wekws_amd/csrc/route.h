@@ -1,18 +1,14 @@
-// WHICH KERNEL RUNS A CALL -- one pure function (round 6; VERDICT r5 "make routing testable and smaller").
-//
-// Until round 5 the choice lived in two places: a 70-line conditional chain in wekws_hip_forward and the "return -4" conditions
-// inside every launcher, tried one after the other.  All three defects the round-5 fuzz found were in that layer (a fifth
-// DS-TCN h256 block whose hand-over the 16-wave kernel did not cover, hidden_dim 32 taken for a built width, ...), in code that
-// could only be exercised with a GPU.  Now:
+// WHICH KERNEL RUNS A CALL -- one pure function, and the only place the choice is made.
 //   * conv_route_flags()  what a conv model can run on, from its (built-shape) descriptor alone -- wekws_hip_create stores it;
-//   * select_conv_route() (flags, options, call) -> {family, tile count, split, context variant, persistent grid, LDS bytes},
-//     with the invariants of the choice checked (built widths, LDS within the CU's 160 KiB, the hand-over covering the
-//     longest padding, alignment preconditions);
-//   * wekws_hip_forward switches on the family; a launcher that refuses what the route chose is an internal error, not a
-//     fall-through.
+//   * select_conv_route() (flags, options, call) -> Route {family, tile count, split, context variant, fast, grid, threads, LDS
+//     bytes, utterances per workgroup}, with the invariants of the choice checked (built widths, LDS within the CU's 160 KiB, the
+//     hand-over covering the longest padding, alignment preconditions).
+// wekws_hip_forward hands the Route to its family's launcher, which executes it: the kernel variant from nt / split / ctx / fast,
+// the grid, threads and LDS from the Route.  A launcher tests no eligibility of its own; it only refuses (-4, an internal error)
+// a Route whose threads or LDS bytes are not its kernel's or that names a variant it does not build.  So the LDS sizes below
+// restate every kernel header's geometry, and the route the hooks trace records is the launch that ran.
 // Plain C++ (no HIP): tests/test_route.py sweeps the fuzz generator's configurations through it on the CPU via the hooks
-// library (wekws_hip_debug_conv_route); the GPU suite (every family parity-green against the oracle) runs through the same
-// switch.
+// library (wekws_hip_debug_conv_route); tests/test_hip_route_matrix.py checks each tile's Route on the device.
 #pragma once
 #include <stdint.h>
 
@@ -166,16 +162,17 @@ inline Route select_conv_route(const wekws_hip_desc& d, const RouteFlags& f, con
   const int ks_built = d.backbone == WEKWS_HIP_BACKBONE_MDTC ? 5 : 8;
   if (ks != ks_built) return fail("kernel size is not the built one: wekws_hip_create pads or takes the any-shape path");
 
-  // LDS of the tile kernels (conv_stack.hip.h Geom, ds256_w16.hip.h W16Geom, conv_stack_f16.hip.h)
-  const int SS = (nt % 2) ? 16 * nt : 16 * nt + 16;
-  const int U = C >= 128 ? 1 : 128 / C;
-  auto conv_f32_lds = [&]() {
-    const int KC = C >= 64 ? 32 : 16;
-    const int R = d.backbone == WEKWS_HIP_BACKBONE_MDTC ? (C > 2 * KC ? C : 2 * KC) : 2 * KC;
-    return (U * C * SS + U * R * SS) * 4;
-  };
-  const int tt = 16 * nt;
-  auto w16_lds = [](int ntk) { return 1280 * 16 * ntk + 4096; };   // W16Geom<NT>::LDS_BYTES: 4 operand planes of 64 TT bytes + 256 rows of TT + 4 floats
+  // LDS bytes of every family, its header's geometry restated (a launcher refuses a route whose LDS is not its kernel's)
+  const int tt = 16 * nt, SS = (nt % 2) ? tt : tt + 16;             // frames of the tile; Geom<>'s row stride
+  const int U = C >= 128 ? 1 : 128 / C, KC = C >= 64 ? 32 : 16;
+  const int R = d.backbone == WEKWS_HIP_BACKBONE_MDTC ? (C > 2 * KC ? C : 2 * KC) : 2 * KC;
+  const int tile_lds = (U * C * SS + U * R * SS) * 4;                // Geom<>: conv_stack and conv_stack_f16
+  auto w16_lds = [](int ntk) { return 1280 * 16 * ntk + 4096; };      // W16Geom<NT>: 4 operand planes of 64 TT bytes + 256 rows of TT + 4 floats
+  const int mm_lds = 1280 * tt + 2 * 8 * 56 * 16;                    // MmGeom<NT>: the same planes and slab + 2 left-context planes
+  const int m16_lds = (2 * 64 * SS * (nt <= 2 ? 2 : 1) + 2 * 64 * (tt + 4)) * 4;   // M16Geom<NT>: Geom<MDTC, 64>'s slab (twice for <= 2 tiles) + 2 x 64 rows
+  const int dense_lds = U * (2 * (C / 8) * (56 + tt) * 16 + 2 * 4 * tt * 16);     // DenseGeom<>: hi / lo planes of h + 2 staged K steps of x
+  const int nt_g4 = has_in && nt <= 4 ? 4 : nt;                     // *_g4: the context variant's tile is one 16-lane row, >= 4 tiles
+  const int g4_lds = 2 * (C / 8) * 16 * nt_g4 * 16;                  // 2 Plane<C, 16 NT>
 
   switch (d.backbone) {
     case WEKWS_HIP_BACKBONE_DS_TCN: {
@@ -189,12 +186,12 @@ inline Route select_conv_route(const wekws_hip_desc& d, const RouteFlags& f, con
       const bool fast = linear2 && f.kpre16 <= 64 && x_items;
       if (!f16) {
         if (reg_ok && !has_in && fast) return done(ROUTE_DS256_G32, nt, false, true, c.B < c.cus || o.g16_one_pass ? c.B : c.cus, 1024, w16_lds(nt), 1);
-        if (conv_f32_lds() > 160 * 1024) return fail("conv_stack: tile beyond the LDS");
-        return done(ROUTE_CONV_F32, nt, has_in, false, (c.B + U - 1) / U, 512, conv_f32_lds(), U);
+        if (tile_lds > 160 * 1024) return fail("conv_stack: tile beyond the LDS");
+        return done(ROUTE_CONV_F32, nt, has_in, false, (c.B + U - 1) / U, 512, tile_lds, U);
       }
       if (o.mm_ok) {
         if (!f.mm_eligible) return fail("ds256_mm on a model it is not built for");
-        return done(ROUTE_DS256_MM, nt, has_in, false, c.B, 1024, 0, 1);
+        return done(ROUTE_DS256_MM, nt, has_in, false, c.B, 1024, mm_lds, 1);
       }
       if (reg_ok && (!has_in || (o.g16_ctx && nt >= 2))) {
         const int ntk = has_in && nt < 4 ? 4 : nt;                   // the context tile is one 16-lane row: >= 4 tiles
@@ -208,14 +205,14 @@ inline Route select_conv_route(const wekws_hip_desc& d, const RouteFlags& f, con
       }
       if (C == 64 && o.g16_ok && d.num_layers <= 4 && f.dils_1248 && (!has_in || (o.g16_ctx && nt >= 2)) && linear2 && f.kpre16 <= 96 && x_items) {
         if (has_in && !(nt <= 4 || nt == 7)) return fail("ds64_g4 context variant: 4 or 7 tiles");
-        return done(ROUTE_DS64_G4, has_in && nt <= 4 ? 4 : nt, has_in, true, c.B, 256, 2 * (64 / 8) * tt * 16, 1);
+        return done(ROUTE_DS64_G4, nt_g4, has_in, true, c.B, 256, g4_lds, 1);
       }
-      return done(ROUTE_CONV_F16, nt, has_in, false, (c.B + U - 1) / U, 512, 0, U);
+      return done(ROUTE_CONV_F16, nt, has_in, false, (c.B + U - 1) / U, 512, tile_lds, U);
     }
     case WEKWS_HIP_BACKBONE_TCN:
-      if (!f16) return done(ROUTE_CONV_F32, nt, has_in, false, (c.B + U - 1) / U, 512, conv_f32_lds(), U);
-      if (f.dense_ok) return done(ROUTE_DENSE_F16, nt, has_in, false, (c.B + U - 1) / U, 512, 0, U);
-      return done(ROUTE_CONV_F16, nt, has_in, false, (c.B + U - 1) / U, 512, 0, U);
+      if (!f16) return done(ROUTE_CONV_F32, nt, has_in, false, (c.B + U - 1) / U, 512, tile_lds, U);
+      if (f.dense_ok) return done(ROUTE_DENSE_F16, nt, has_in, false, (c.B + U - 1) / U, 512, dense_lds, U);
+      return done(ROUTE_CONV_F16, nt, has_in, false, (c.B + U - 1) / U, 512, tile_lds, U);
     case WEKWS_HIP_BACKBONE_MDTC: {
       const bool m16 = f16 && o.mdtc16_ok && f.mdtc16_eligible;
       if (m16 && f.mdtc_stream_eligible && o.stream_ok && c.ntiles == 1 && c.T <= 16 && (c.has_in || c.has_out) && c.cache16 && x_items)
@@ -223,17 +220,17 @@ inline Route select_conv_route(const wekws_hip_desc& d, const RouteFlags& f, con
       const bool head_ok = linear2 || (pooled && d.head_hidden <= 448);
       if (m16 && o.g16_ok && f.mdtc_stream_eligible && (!has_in || (o.g16_ctx && nt >= 2 && (c.B > 2 || nt < 7))) && head_ok && f.kpre16 <= 96 &&
           x_items && (!has_in || linear2))
-        return done(ROUTE_MDTC64_G4, has_in && nt <= 4 ? 4 : nt, has_in, true, c.B, 256, 2 * (64 / 8) * tt * 16, 1);
-      if (m16) return done(ROUTE_MDTC64_W16, nt, has_in, false, (c.B + 1) / 2, 1024, 0, 2);
+        return done(ROUTE_MDTC64_G4, nt_g4, has_in, true, c.B, 256, g4_lds, 1);
+      if (m16) return done(ROUTE_MDTC64_W16, nt, has_in, false, (c.B + 1) / 2, 1024, m16_lds, 2);
       if (f16 && C == 32 && o.g16_ok && d.stack_size <= 4 && f.dils_1248 && (!has_in || (o.g16_ctx && nt >= 2)) && head_ok && f.kpre16 <= 64 && x_items &&
           (!has_in || linear2))
-        return done(ROUTE_MDTC32_G4, has_in && nt <= 4 ? 4 : nt, has_in, true, c.B, 128, 2 * (32 / 8) * tt * 16, 1);
+        return done(ROUTE_MDTC32_G4, nt_g4, has_in, true, c.B, 128, g4_lds, 1);
       if (f16) {
         if (C > 128) return fail("MDTC wider than 128 channels does not fit the LDS tile: any-shape path");
-        return done(ROUTE_CONV_F16, nt, has_in, false, (c.B + U - 1) / U, 512, 0, U);
+        return done(ROUTE_CONV_F16, nt, has_in, false, (c.B + U - 1) / U, 512, tile_lds, U);
       }
-      if (conv_f32_lds() > 160 * 1024) return fail("conv_stack: tile beyond the LDS");
-      return done(ROUTE_CONV_F32, nt, has_in, false, (c.B + U - 1) / U, 512, conv_f32_lds(), U);
+      if (tile_lds > 160 * 1024) return fail("conv_stack: tile beyond the LDS");
+      return done(ROUTE_CONV_F32, nt, has_in, false, (c.B + U - 1) / U, 512, tile_lds, U);
     }
     default:
       return fail("not a conv backbone");

@@ -1858,37 +1858,26 @@ int wekws_hip_forward(wekws_hip_model* m, const float* x, int B, int T, const fl
       if (g_route_trace.ntiles < kTraceMaxTiles) g_route_trace.tile[g_route_trace.ntiles] = route;
       ++g_route_trace.ntiles;
 #endif
-      const bool split = route.split != 0;
-      const int nt = route.nt;
-      const int grid_cus = m->g16_one_pass ? (1 << 30) : m->fsmn_cus;   // persistent kernels: the largest grid
+      const wekws::StackParams& sp = m->sp;
       switch (route.family) {
-        case wekws::ROUTE_DS256_STREAM: rc = wekws::launch_ds256_stream(split, m->sp, a, stream); break;
-        case wekws::ROUTE_DS256_G32: rc = wekws::launch_ds256_g32(nt, m->sp, a, stream, grid_cus); break;
-        case wekws::ROUTE_DS256_MM: rc = wekws::launch_ds256_mm(nt, m->sp, a, m->dp.head_a16, stream); break;
-        case wekws::ROUTE_DS256_G16: rc = wekws::launch_ds256_g16(nt, split, m->sp, a, stream, grid_cus); break;
-        case wekws::ROUTE_DS256_W16: rc = wekws::launch_ds256_w16(nt, split, m->sp, a, stream); break;
-        case wekws::ROUTE_DS64_G4: rc = wekws::launch_ds64_g4(nt, split, m->sp, a, stream); break;
-        case wekws::ROUTE_MDTC64_STREAM: rc = wekws::launch_mdtc64_stream(split, m->sp, a, stream); break;
-        case wekws::ROUTE_MDTC64_G4: rc = wekws::launch_mdtc64_g4(nt, split, m->sp, a, stream); break;
-        case wekws::ROUTE_MDTC64_W16: rc = wekws::launch_mdtc64_w16(nt, split, m->sp, a, stream); break;
-        case wekws::ROUTE_MDTC32_G4: rc = wekws::launch_mdtc32_g4(nt, split, m->sp, a, stream); break;
-        case wekws::ROUTE_DENSE_F16: rc = wekws::launch_dense_stack_f16<wekws::KIND_TCN>(C, nt, m->dp, a, stream); break;
-        case wekws::ROUTE_CONV_F16:
-          rc = d.backbone == WEKWS_HIP_BACKBONE_DS_TCN ? wekws::launch_conv_stack_f16<wekws::KIND_DS>(C, nt, m->sp, a, stream)
-               : d.backbone == WEKWS_HIP_BACKBONE_TCN  ? wekws::launch_conv_stack_f16<wekws::KIND_TCN>(C, nt, m->sp, a, stream)
-                                                        : wekws::launch_conv_stack_f16<wekws::KIND_MDTC>(C, nt, m->sp, a, stream);
-          break;
-        default:
-          rc = d.backbone == WEKWS_HIP_BACKBONE_DS_TCN ? wekws::launch_conv_stack<wekws::KIND_DS>(C, nt, m->sp, a, stream)
-               : d.backbone == WEKWS_HIP_BACKBONE_TCN  ? wekws::launch_conv_stack<wekws::KIND_TCN>(C, nt, m->sp, a, stream)
-                                                        : wekws::launch_conv_stack<wekws::KIND_MDTC>(C, nt, m->sp, a, stream);
-          break;
+        case wekws::ROUTE_DS256_STREAM: rc = wekws::launch_ds256_stream(route, sp, a, stream); break;
+        case wekws::ROUTE_DS256_G32: rc = wekws::launch_ds256_g32(route, sp, a, stream); break;
+        case wekws::ROUTE_DS256_MM: rc = wekws::launch_ds256_mm(route, sp, m->dp.head_a16, a, stream); break;
+        case wekws::ROUTE_DS256_G16: rc = wekws::launch_ds256_g16(route, sp, a, stream); break;
+        case wekws::ROUTE_DS256_W16: rc = wekws::launch_ds256_w16(route, sp, a, stream); break;
+        case wekws::ROUTE_DS64_G4: rc = wekws::launch_ds64_g4(route, sp, a, stream); break;
+        case wekws::ROUTE_MDTC64_STREAM: rc = wekws::launch_mdtc64_stream(route, sp, a, stream); break;
+        case wekws::ROUTE_MDTC64_G4: case wekws::ROUTE_MDTC32_G4: rc = wekws::launch_mdtc_g4(route, C, sp, a, stream); break;
+        case wekws::ROUTE_MDTC64_W16: rc = wekws::launch_mdtc64_w16(route, sp, a, stream); break;
+        case wekws::ROUTE_DENSE_F16: rc = wekws::launch_dense_stack_f16(route, C, m->dp, a, stream); break;
+        case wekws::ROUTE_CONV_F16: rc = wekws::launch_conv_stack_f16(route, d.backbone, C, sp, a, stream); break;
+        default: rc = wekws::launch_conv_stack(route, d.backbone, C, sp, a, stream); break;
       }
       // (a launcher that refuses what the route chose: the two have drifted apart -- an internal error, never a silent fall-through)
       if (rc == -4)
-        return fail(WEKWS_HIP_EUNSUPPORTED, "internal: kernel family %s refused the call the route chose for it (C=%d nt=%d T=%d cache %d/%d)",
-                    wekws::route_family_name(route.family), C, nt, Tt, rcall.has_in, rcall.has_out);
-      if (rc) return fail(rc, "conv-stack launch failed (C=%d nt=%d): %s", C, nt, hipGetErrorString(hipGetLastError()));
+        return fail(WEKWS_HIP_EUNSUPPORTED, "internal: kernel family %s has no kernel for the route (C=%d nt=%d T=%d cache %d/%d threads %d LDS %d)",
+                    wekws::route_family_name(route.family), C, route.nt, Tt, rcall.has_in, rcall.has_out, route.threads, route.lds_bytes);
+      if (rc) return fail(rc, "conv-stack launch failed (C=%d nt=%d): %s", C, route.nt, hipGetErrorString(hipGetLastError()));
       if (nf_fix_all()) {                                    // (measurement aid only: the non-finite pass as its own launch)
         hipLaunchKernelGGL(conv_nf_fix_kernel, dim3(B), dim3(256), 0, stream, a, d.idim, C * m->cache_len);
         if (hipGetLastError() != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "non-finite pass: launch failed");
