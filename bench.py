@@ -7,6 +7,11 @@ latency that is the other half of BASELINE.json's metric.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W       # the driver's own launch: one rank per GPU over RCCL
     python bench.py ... --dump-outputs DIR           # also writes the last timed step's outputs to DIR/*.npy (dump_outputs)
+    python bench.py ... --full                       # also everything else the benchmark measures (below), ~2 minutes more
+
+A plain run does only what the headline needs: set up, `--preheat`, W warm-up steps, the K timed steps, `--dump-outputs`,
+the contract line.  Everything else -- `value_no_preheat`, `step_ms`, `cpu_baseline`, the secondary workloads and the
+side file -- is measured only with `--full`; the K timed steps and the fields they give are the same either way.
 
 A "step" is one pass of the hot path (KWSModel.forward: 40-d fbank features -> per-frame posteriors + streaming cache,
 what wekws/bin/score.py:125 calls) over one batch of synthetic 1-s utterances already resident in HBM.  Workload
@@ -18,25 +23,25 @@ Timing: `--preheat` seconds (default 0.5) of the same forward to bring the GPU o
 MI355X runs its first ~0.25 s of work at lower clocks: 0.293 ms per step right after 10 steps, 0.244 ms after 1000 --,
 then W warm-up steps, then EXACTLY K steps between barrier + torch.cuda.synchronize() on both sides, wall clock, MAX
 over ranks -> `value`, `ms_per_step`.  The K steps also sit between two HIP events on the launch stream: that time / K is
-the average launch duration the roofline uses (`roofline.kernel_ms`).  `step_ms` = median / p10 / p90 of >= 50 samples
-taken right after the timed region, each the mean of 4 back-to-back steps between two HIP events (an event pair around
-every single launch adds ~7 us to it and to the job).
+the average launch duration the roofline uses (`roofline.kernel_ms`).  `step_ms` (--full) = median / p10 / p90 of >= 50
+samples taken right after the timed region, each the mean of 4 back-to-back steps between two HIP events (an event pair
+around every single launch adds ~7 us to it and to the job).
 
 Rank 0 prints the contract as ONE compact JSON line, LAST on stdout (< 6 KB: the driver keeps an 8 KB tail): the contract
-fields, `config`, `roofline`, `cpu_baseline`, `value_no_preheat`, `step_ms` and a `summary` of the secondary workloads.  Everything
-else -- the verbose records below -- goes to `gpurun_out/bench_extras.json` (`--extras-out`) and to EARLIER stdout lines of
-the form `extras <key> = <json>` (which do not start with '{').
+fields, `config` and `roofline`; with --full also `cpu_baseline`, `value_no_preheat`, `step_ms` and a `summary` of the
+secondary workloads.  With --full everything else -- the verbose records below -- goes to a side file (`--extras-out`; the
+default is in emit()) and to EARLIER stdout lines of the form `extras <key> = <json>` (which do not start with '{').
   roofline        dominant kernel of `value` (default precision: ds256 register-resident kernel, 3 x fp16 MFMA per MAC on
                   block-floating hi/lo operands, so the peak for ALGORITHMIC flops is 2500 / 3 TF).  `kernel` and `traffic` (HBM
                   bytes per launch from rocprofv3 PMC passes: 2 x FETCH_SIZE + WRITE_SIZE, MI355X_MICROARCH.md's gfx950
                   correction) are reported only when profiles/pmc_traffic.json was taken with the very library file this run
                   loads (sha-256 match) on this workload -- else null.
-  value_no_preheat   the contract's W + K steps taken FIRST, on the idle GPU, before any preheat (`--preheat 0` gives the same
-                  as `value`): both readings of "W warm-up steps" exist in one line.
-  cpu_baseline    the reference's CPU path (PyTorch CPU operator sequence, oracle/torch_ref.py) on this box's host cores; the
+  value_no_preheat   (--full) the contract's W + K steps taken FIRST, on the idle GPU, before any preheat (`--preheat 0` gives
+                  the same as `value`): both readings of "W warm-up steps" exist in one line.
+  cpu_baseline    (--full) the reference's CPU path (PyTorch CPU operator sequence, oracle/torch_ref.py) on this box's host cores; the
                   best of: all hardware threads, one core, a thread sweep, one pinned OpenMP thread per physical core, and
                   P processes x 4 pinned threads (utterances split as over GPU ranks); rows in extras `cpu_baseline_detail`.
-extras (side file):
+extras (--full, side file):
   value_single_output_buffer   the same steps with the result dropped at once (one 110 MB cache buffer recycled).
   f32             the same batch with precision F32 (exact-f32 MFMA kernel), roofline against the 157.3 TF f32 matrix peak.
   also / score_only / gru / small_recipes   MDTC h64 (BASELINE config 2's model), posteriors only, GRU 2x128, DS-TCN h64, MDTC small.
@@ -188,6 +193,11 @@ def emit(out, extra, extras_out):
         out["extras_file"] = f"not written: {e}"[:120]
     for k, v in extra.items():
         print(f"extras {k} = {json.dumps(v)}")
+    print_line(out)
+
+
+def print_line(out):
+    """The one compact JSON line of the contract, LAST on stdout (a plain run prints nothing else)."""
     line = json.dumps(out)
     assert len(line) <= MAX_LINE_BYTES, f"contract line grew to {len(line)} bytes (limit {MAX_LINE_BYTES})"
     sys.stdout.flush()
@@ -487,9 +497,14 @@ def main():
     ap.add_argument("--preheat", type=float, default=0.5,
                     help="seconds of the same forward before the W warm-up steps: an idle MI355X runs its first ~0.25 s "
                          "of work at lower clocks (measured: 0.293 ms per step after 10 steps, 0.244 ms after 1000)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything else: the W + K steps on the idle GPU (value_no_preheat), the step-time "
+                         "spread, the CPU baseline, the secondary workloads and streaming latency, with the verbose records "
+                         "in the side file (--extras-out); a plain run times the K steps alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)   # model,threads,T,seconds: see cpu_pinned_rows
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary workloads (the contract line is the same)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the secondary workloads (the contract line is the same)")
     ap.add_argument("--extras-out", default=None, help="where the extras go (default gpurun_out/bench_extras.json)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="PLUMBING TEST ONLY (tests/test_hip_bench.py on a 1-GPU box): all ranks use cuda:0 and talk over gloo, so "
@@ -549,24 +564,25 @@ def main():
     prec = {"default": "f16x3"}.get(args.precision, args.precision)
 
     x = torch.from_numpy(synth.synth_feats(B, T, idim, seed=100 + rank)).to(dev)
-    # The contract's W + K steps as the idle GPU runs them, BEFORE any preheat (`value_no_preheat`: the literal reading of
-    # "W warm-up steps, then K timed steps"; the clocks are still ramping, so it is the lower of the two readings).
-    for _ in range(args.warmup):
-        y, cache = model(x)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        y, cache = model(x)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    cold = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=comm_dev)
-    if world > 1:
-        dist.all_reduce(cold, op=dist.ReduceOp.MAX)
-    cold_s = float(cold.item())
+    if args.full:
+        # The contract's W + K steps as the idle GPU runs them, BEFORE any preheat (`value_no_preheat`: the literal reading
+        # of "W warm-up steps, then K timed steps"; the clocks are still ramping, so it is the lower of the two readings).
+        for _ in range(args.warmup):
+            y, cache = model(x)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            y, cache = model(x)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        cold = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=comm_dev)
+        if world > 1:
+            dist.all_reduce(cold, op=dist.ReduceOp.MAX)
+        cold_s = float(cold.item())
     # bring the GPU out of its idle power state (clock ramp) with the workload itself; then the contract's W + K steps
     t_pre, n_pre = time.perf_counter(), 0
     while time.perf_counter() - t_pre < args.preheat:
@@ -592,16 +608,17 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kern_ms = ev0.elapsed_time(ev1) / args.steps              # average launch duration over the timed region
-    # spread of the step time, outside the timed region: >= 50 samples, each GROUP launches between two HIP events
-    keep = {}
+    if args.full:
+        # spread of the step time, outside the timed region: >= 50 samples, each GROUP launches between two HIP events
+        keep = {}
 
-    def one_step():                       # outputs stay bound across the next call, as `y, cache = model(x)` above and
-        keep["o"] = model(x)              # `logits, _ = model(feats)` in score.py:125 do: the caching allocator then
+        def one_step():                   # outputs stay bound across the next call, as `y, cache = model(x)` above and
+            keep["o"] = model(x)          # `logits, _ = model(feats)` in score.py:125 do: the caching allocator then
                                           # alternates two 110 MB cache buffers (dropping the result at once recycles ONE
                                           # buffer, whose rewrites hit the memory-side cache: 0.24 instead of 0.28 ms)
-    step_ms = time_steps(torch, one_step, max(50, args.steps), 0)
-    # the same steps with the result dropped at once (one output buffer recycled by the caching allocator)
-    step_ms_single = time_steps(torch, lambda: model(x), max(50, args.steps), 0)
+        step_ms = time_steps(torch, one_step, max(50, args.steps), 0)
+        # the same steps with the result dropped at once (one output buffer recycled by the caching allocator)
+        step_ms_single = time_steps(torch, lambda: model(x), max(50, args.steps), 0)
     rank_rates, bc_ms_max = [B * args.steps / elapsed], t_bc * 1e3
     props = torch.cuda.get_device_properties(dev)
     place = {"rank": rank, "local_rank": local, "device": f"cuda:{local}", "name": props.name,
@@ -638,19 +655,22 @@ def main():
                        "batch_per_gpu": B, "frames": T, "feat_dim": idim, "precision": prec,
                        "preheat_s": args.preheat, "preheat_steps": n_pre,
                        "parallelism": f"utterance-parallel x{world}"},
-            "value_no_preheat": round(B * world * args.steps / cold_s, 1),
-            "ms_per_step_no_preheat": round(cold_s / args.steps * 1e3, 4),
-            "step_ms": dict(pct(step_ms), samples=len(step_ms), launches_per_sample=GROUP),
         }
-        # everything that is not the contract goes to the side file / earlier stdout lines (see emit())
-        extra = {"lib_sha16": lib_sha16(), "value_single_output_buffer": {
-            "value": round(B * world / float(np.median(step_ms_single)) * 1e3, 1), "unit": "utts/s",
-            "step_ms": pct(step_ms_single),
-            "note": "result dropped at once: ONE 110 MB cache buffer is recycled and its rewrites hit the 256 MB "
-                    "memory-side cache; `value` / `step_ms` keep the result bound across the next call (two buffers "
-                    "alternate), as score.py:125 does"},
-            "value_no_preheat_note": f"the same {args.warmup} + {args.steps} steps taken first, on the idle GPU, before the preheat "
-                                     "(wall clock, barriers + synchronize on both sides, MAX over ranks)"}
+        # everything that is not the contract goes to the side file / earlier stdout lines (see emit()); --full only
+        extra = {}
+        if args.full:
+            extra["lib_sha16"] = lib_sha16()
+            out["value_no_preheat"] = round(B * world * args.steps / cold_s, 1)
+            out["ms_per_step_no_preheat"] = round(cold_s / args.steps * 1e3, 4)
+            out["step_ms"] = dict(pct(step_ms), samples=len(step_ms), launches_per_sample=GROUP)
+            extra["value_single_output_buffer"] = {
+                "value": round(B * world / float(np.median(step_ms_single)) * 1e3, 1), "unit": "utts/s",
+                "step_ms": pct(step_ms_single),
+                "note": "result dropped at once: ONE 110 MB cache buffer is recycled and its rewrites hit the 256 MB "
+                        "memory-side cache; `value` / `step_ms` keep the result bound across the next call (two buffers "
+                        "alternate), as score.py:125 does"}
+            extra["value_no_preheat_note"] = (f"the same {args.warmup} + {args.steps} steps taken first, on the idle GPU, before "
+                                              "the preheat (wall clock, barriers + synchronize on both sides, MAX over ranks)")
         if world > 1:
             out["comm"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                            "collectives_in_timed_region": 0, "broadcast_bytes": bc_bytes,
@@ -671,7 +691,7 @@ def main():
             attach_profile(roof, args.model, B, prec)
             extra["roofline_verbose"] = roof
             out["roofline"] = compact_roofline(roof)
-        extras = world == 1 and args.model == "ds_tcn_h256" and not args.no_extras
+        extras = args.full and world == 1 and args.model == "ds_tcn_h256" and not args.no_extras
         if extras:
             if prec != "f32":        # the same batch at the reference's own arithmetic
                 ts = time_steps(torch, lambda m=build_model(torch, init_model, pack, synth, args.model, dev, "f32")[2]: m(x), 30, 5)
@@ -765,13 +785,16 @@ def main():
                 "latency_chunk80": {n: {b: l80[n][b]["median"] for b in ("B1", "B256")} for n in ("ds_tcn_h64", "ds_tcn_h256", "mdtc_h64")},
                 "hbm_bound": {o["kernel"]: {"ms": o["step_ms"]["median"], "frac": o["frac"]} for o in extra["rooflines_other"]},
                 "audio_to_posteriors": extra["audio_to_posteriors"]["value"]}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"], extra["cpu_baseline_detail"] = cpu_baseline(cfg, sd, T, idim, args.model)
             if extras:
                 for name in ("gru_2x128", "ds_tcn_h256", "mdtc_h64"):
                     c2 = dict(synth.MODEL_CONFIGS[name])
                     extra["latency"][name]["cpu"] = cpu_stream_latency(c2, synth.synth_state_dict(pack.model_spec(c2), 1234))
-        emit(out, extra, args.extras_out)
+        if args.full:
+            emit(out, extra, args.extras_out)
+        else:
+            print_line(out)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -87,3 +87,15 @@ def test_steps_below_one_are_refused():
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
     assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
+
+def test_full_option_and_the_plain_line():
+    """A plain run measures the headline alone; everything else is behind --full, which every caller that needs it passes."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
+    assert r.returncode == 0 and "--full" in r.stdout
+    buf = io.StringIO()
+    out, _ = _line()
+    with redirect_stdout(buf):
+        bench.print_line(out)
+    assert buf.getvalue().splitlines() == [json.dumps(out)]

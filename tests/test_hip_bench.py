@@ -1,9 +1,10 @@
-"""GPU: bench.py prints the one JSON line the driver parses, with every field of the contract and the two extra objects
-(`roofline`, `cpu_baseline`) -- run small, but through the real code path."""
+"""GPU: bench.py prints the one JSON line the driver parses: a plain run the contract fields and `roofline` alone, `--full`
+also the extra objects (`cpu_baseline`, `value_no_preheat`, `step_ms`, `summary`) -- run small, but through the real code path."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -32,7 +33,7 @@ def run_bench(*flags, extras_out=None):
 
 def test_contract_line_small_run(tmp_path):
     ex = str(tmp_path / "extras.json")
-    d = run_bench("--gpus", "1", "--steps", "4", "--warmup", "2", "--preheat", "0.05", "--no-extras", extras_out=ex)
+    d = run_bench("--gpus", "1", "--steps", "4", "--warmup", "2", "--preheat", "0.05", "--full", "--no-extras", extras_out=ex)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "step_ms"):
         assert k in d, k
@@ -65,13 +66,39 @@ def test_contract_line_small_run(tmp_path):
     assert d["value"] > 10 * c["value"]
 
 
+def test_plain_run_is_lean(tmp_path):
+    """A plain run (the driver's command, no --full) does only what its headline needs: its stdout is the contract line alone,
+    without the CPU baseline or any other measurement, no side file is written, and the whole process spends at most 30 s
+    outside its W + K steps."""
+    ex = tmp_path / "extras.json"
+    t0 = time.perf_counter()
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--extras-out", str(ex)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    wall = time.perf_counter() - t0
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith('{"metric"'), p.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["n_gpus"] == 1 and d["higher_is_better"] is True
+    assert abs(d["value"] - d["config"]["batch_per_gpu"] / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+    assert d["roofline"]["bound"] == "mfma" and 0.0 < d["roofline"]["frac"] < 1.0
+    for k in ("cpu_baseline", "value_no_preheat", "step_ms", "summary", "extras_file"):
+        assert k not in d, k
+    assert not ex.exists()
+    outside = wall - (20 + 5) * d["ms_per_step"] * 1e-3
+    assert outside <= 30.0, f"{outside:.1f} s outside the steps"
+
+
 def test_multi_rank_statements_run_on_a_gpu():
     """No session and no driver run ever had more than one GPU, so the N > 1 statements of bench.py (rank rendezvous, weight
     broadcast into rank > 0's module, barriers, MAX over ranks, per-rank placement, `comm`) had only ever run in the CPU stub.
     `--share-gpu` lets two ranks share cuda:0 over gloo: every one of those statements executes, with the real forward, on the GPU
     box.  The number is meaningless (two processes time-share one device) and the line says so."""
-    d = run_bench("--gpus", "2", "--steps", "4", "--warmup", "2", "--preheat", "0.05", "--no-extras", "--no-cpu-baseline",
-                  "--share-gpu")
+    d = run_bench("--gpus", "2", "--steps", "4", "--warmup", "2", "--preheat", "0.05", "--full", "--no-extras",
+                  "--no-cpu-baseline", "--share-gpu")
     assert d["n_gpus"] == 2 and d["steps"] == 4 and "test_mode" in d
     assert d["comm"]["world_size"] == 2 and d["comm"]["collectives_in_timed_region"] == 0 and d["comm"]["broadcast_bytes"] > 1_000_000
     assert [p.split(":")[0] for p in d["comm"]["ranks"]] == ["r0", "r1"] and len(d["per_rank_utts_per_s"]["all"]) == 2
@@ -81,10 +108,10 @@ def test_multi_rank_statements_run_on_a_gpu():
 
 
 def test_default_run_line_fits_the_driver_tail(tmp_path):
-    """The driver's own command (BENCH_r0N.json `cmd`), every secondary workload included: the last stdout line is the compact
-    contract line with `roofline`, `cpu_baseline` and the `summary` of the extras; the extras are in the side file."""
+    """The driver's own command (BENCH_r0N.json `cmd`) with `--full`, every secondary workload included: the last stdout line
+    is the compact contract line with `roofline`, `cpu_baseline` and the `summary` of the extras; the extras are in the side file."""
     ex = str(tmp_path / "extras.json")
-    d = run_bench("--gpus", "1", "--steps", "20", "--warmup", "5", extras_out=ex)
+    d = run_bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", extras_out=ex)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline", "summary", "value_no_preheat"):
         assert k in d, k

@@ -34,6 +34,6 @@ cp profiles/pmc_traffic.json $out/${tag}_pmc_traffic.json
 python tools/prof_summary.py $(find $out -path "*prof_strm*" -name "*_results.db" | sort) > $out/${tag}_stream_kernels.txt
 rm -rf $out/prof_*
 # the bench line (reads the PMC traffic file written above: same library build) and the secondary configs
-python bench.py --extras-out $out/${tag}_bench_extras.json 2> $out/${tag}_bench.err | tail -1 > $out/${tag}_bench.json
+python bench.py --full --extras-out $out/${tag}_bench_extras.json 2> $out/${tag}_bench.err | tail -1 > $out/${tag}_bench.json
 python tools/bench_configs.py > $out/${tag}_configs.jsonl 2> $out/${tag}_configs.err
 ls -la $out | tail -20
