@@ -197,15 +197,17 @@ enum wekws_hip_option {
   WEKWS_HIP_OPT_MM = 3,         /* DS-TCN hidden 256: the all-matrix-core kernel -- -1 (default) for CTC-sized heads only, 0 never, 1 whenever eligible */
   WEKWS_HIP_OPT_HEAD_SLICES = 4,/* workgroups sharing a CTC-sized last layer on small calls: -1 (default) automatic, 0 / 1 none, n exactly n */
   WEKWS_HIP_OPT_G16 = 5,        /* calls without an incoming cache: 1 (default) the register-resident kernels -- DS-TCN hidden 256: ds256_g16.hip.h (split fp16 / fp16) and ds256_g32.hip.h (precision F32), MDTC hidden 64: mdtc64_g4.hip.h --, 0 the LDS-tile kernels, 2 like 1 but one workgroup per utterance instead of persistent ones, 3 like 1 but calls WITH an incoming cache (later chunks of 17 .. 112 frames) keep the LDS-tile kernels instead of the register-resident kernels' context variants (measurement aids) */
-  WEKWS_HIP_OPT_GRU_PIPE = 7,   /* GRU: 1 (default) the layer wavefront -- one launch, the stages of all layers running at the same time on different CUs (gru_pipe.hip.h) -- up to eight rounds of stream tiles per resident slot (B <= 128 x CUs / (2 x layers)), the layer-major kernels (gru_f16.hip.h) beyond; 2 the wavefront always; 0 never; bit-identical results */
+  WEKWS_HIP_OPT_GRU_PIPE = 7,   /* GRU: 1 (default) the layer wavefront -- one launch, the stages of all layers running at the same time on different CUs (gru_pipe.hip.h) -- up to eight rounds of stream tiles per resident slot (B <= 128 x CUs / (2 x layers)), the layer-major kernels (gru_f16.hip.h) beyond; 2 the wavefront wherever it fits (at least 2 x layers CUs); 0 never; bit-identical results (csrc/route.h: select_gru_route) */
   WEKWS_HIP_OPT_ENVELOPE = 6    /* weights outside the split-fp16 envelope (wekws_hip_weight_spread_log2): 1 (default) run the exact-f32 kernels, 0 keep the split-fp16 kernels (to MEASURE where the envelope ends; accuracy is then not promised) */
 };
 int wekws_hip_set_option(wekws_hip_model* m, int option, int value);
 
 /*
  * The arithmetic a model's calls REALLY run in (an enum wekws_hip_precision, never DEFAULT; negative error code for a NULL
- * model): desc.precision is a request, and not every backbone has a kernel for every mode -- F16 is honoured by the
- * 16-wave DS-TCN / MDTC kernels only (FSMN and every other shape run F16X3: more accurate than asked), a GRU without an fp16
+ * model): desc.precision is a request, and not every backbone has a kernel for every mode -- F16 is reported when some call of
+ * the model, under its current options, takes a kernel with a one-product variant (the DS-TCN h256 / h64 and MDTC h64 / h32
+ * kernels of csrc/route.h; calls those kernels do not serve, and FSMN and every other shape, run F16X3: more accurate than
+ * asked), a GRU without an fp16
  * kernel for its shape runs F32, every model on the any-shape path (csrc/generic.hip.h: shapes beyond the specialised
  * kernels; FSMN with precision F32 or with weights outside the split-fp16 envelope) runs F32 whatever was asked.  A caller
  * that needs exact-f32 reference rounding (a parity baseline) checks this instead of trusting the request.  Reflects the

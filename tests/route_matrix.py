@@ -26,7 +26,8 @@ CUS = 256
 TILE = 112                     # WEKWS_HIP_TILE_FRAMES
 FAMILIES = ["none", "ds256_stream", "ds256_g32", "ds256_mm", "ds256_g16", "ds256_w16", "ds64_g4", "mdtc64_stream", "mdtc64_g4",
             "mdtc64_w16", "mdtc32_g4", "dense_stack_f16", "conv_stack_f16", "conv_stack"]
-KEYS = ("plan", "C", "ks", "family", "nt", "split", "ctx", "fast", "grid", "threads", "lds", "utts_per_wg", "cache_len", "max_pad")
+KEYS = ("plan", "C", "ks", "family", "nt", "split", "ctx", "fast", "grid", "threads", "lds", "utts_per_wg", "cache_len", "max_pad", "head_slices",
+        "eff")
 TRACE_KEYS = ("family", "nt", "split", "ctx", "fast", "grid", "threads", "lds", "utts_per_wg")
 
 
@@ -40,6 +41,9 @@ def type_hooks(lib):
                                                C.c_char_p, C.c_int]
     lib.wekws_hip_debug_route_trace.restype = C.c_int
     lib.wekws_hip_debug_route_trace.argtypes = [C.POINTER(C.c_int), C.c_int]
+    for f in (lib.wekws_hip_debug_gru_route, lib.wekws_hip_debug_fsmn_route):
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(_capi.Desc), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.c_char_p, C.c_int]
     return lib
 
 
@@ -49,15 +53,77 @@ def route(lib, cfg, B, T, has_in=False, has_out=True, precision="default", x16=1
     cfg["_precision"] = precision
     d = _capi.make_desc(dict(pack.parse_config(cfg), abi_version=_capi.ABI_VERSION))
     call = (C.c_int * 8)(B, T, ntiles, int(has_in), int(has_out), x16, cache16, cus)
-    out = (C.c_int * 14)()
+    out = (C.c_int * len(KEYS))()
     why = C.create_string_buffer(256)
     o = (C.c_int * 9)(*opts) if opts is not None else None
     assert lib.wekws_hip_debug_conv_route(C.byref(d), o, call, out, why, 256) == 0
     r = dict(zip(KEYS, list(out)))
     r["family"] = FAMILIES[r["family"]]
     r["plan"] = ["as_is", "padded", "generic"][r["plan"]]
+    r["eff"] = PRECISIONS[r["eff"]]
     r["why"] = why.value.decode()
     return r
+
+
+PLANS = ["as_is", "padded", "generic"]
+PRECISIONS = ["default", "f32", "f16x3", "f16"]                 # enum wekws_hip_precision
+GRU_FAMILIES = ["none", "gru_f32", "gru_f16", "gru_pipe"]
+# the 9 ints of a GRU trace record (wekws_hip.hip: route_record), then what only the CPU entry point reports
+GRU_REC = ("family", "nn", "spw", "tchunk", "nchunks", "slots", "tiles", "grid", "bits")
+GRU_KEYS = ("plan", "C") + GRU_REC + ("stages", "slots_p", "lds", "chunked", "plain", "gran", "res_plain", "res_gran", "eff")
+FSMN_REC = ("tile_frames", "nt", "u", "head_slices", "grid", "lds", "ntiles", "_0", "_1")
+FSMN_KEYS = ("plan", "max_nt") + FSMN_REC + ("ws", "eff")
+
+
+def _desc(cfg, precision):
+    cfg = dict(cfg)
+    cfg["_precision"] = precision
+    return _capi.make_desc(dict(pack.parse_config(cfg), abi_version=_capi.ABI_VERSION))
+
+
+def _opts(opts):
+    pairs = [v for k, val in (opts or {}).items() for v in (_capi.OPTIONS[k], int(val))]
+    return (C.c_int * max(1, len(pairs)))(*pairs), len(pairs) // 2
+
+
+def gru_route(lib, cfg, B, T, precision="default", x16=1, cus=CUS, reserve=False, opts=None):
+    """route.h's choice for one GRU call, on the CPU (wekws_hip_debug_gru_route); opts: {option name: value}."""
+    d = _desc(cfg, precision)
+    o, n = _opts(opts)
+    out = (C.c_int64 * 20)()
+    why = C.create_string_buffer(256)
+    assert lib.wekws_hip_debug_gru_route(C.byref(d), o, n, (C.c_int * 5)(B, T, x16, cus, int(reserve)), out, why, 256) == 0
+    r = dict(zip(GRU_KEYS, list(out)))
+    r.update(plan=PLANS[r["plan"]], family=GRU_FAMILIES[r["family"]], eff=PRECISIONS[r["eff"]], why=why.value.decode())
+    r.update(pk=r["bits"] & 1, k2=(r["bits"] >> 1) & 1, nf_in_kernel=(r["bits"] >> 2) & 1)
+    return r
+
+
+def fsmn_route(lib, cfg, B, T, tile=0, precision="default", cus=CUS, opts=None):
+    """route.h's choice for tile `tile` of one FSMN call, on the CPU (wekws_hip_debug_fsmn_route)."""
+    d = _desc(cfg, precision)
+    o, n = _opts(opts)
+    out = (C.c_int64 * 16)()
+    why = C.create_string_buffer(256)
+    assert lib.wekws_hip_debug_fsmn_route(C.byref(d), o, n, (C.c_int * 4)(B, T, tile, cus), out, why, 256) == 0
+    r = dict(zip(FSMN_KEYS, list(out)))
+    r.update(plan=PLANS[r["plan"]], eff=PRECISIONS[r["eff"]], why=why.value.decode())
+    return r
+
+
+def gru_record(r):
+    return [r[k] for k in GRU_REC]
+
+
+def fsmn_record(r):
+    return [r[k] for k in FSMN_REC]
+
+
+# GRU and FSMN calls of the recipes (tools/bench_configs.py): batches of 98 frames (FSMN-CTC: 32 / 64 spliced frames) and
+# 10-frame streaming chunks.  tests/test_route.py pins route.h's routes for them; tests/test_hip_route_gru_fsmn.py checks that the
+# forward's trace on the device is that route.
+GRU_CALLS = [("gru_2x128", B, T) for B, T in ((1, 10), (1, 98), (256, 10), (256, 98), (1024, 98), (16384, 98))]
+FSMN_CALLS = [("fsmn_ctc", B, T) for B, T in ((1, 10), (256, 10), (1024, 32), (1024, 64), (4096, 32))]
 
 
 def route_str(r, B):

@@ -1069,20 +1069,25 @@ def test_fsmn_f32_request_runs_exact_f32():
     assert m32.effective_precision() == "f32" and build(cfg, sd).effective_precision() == "f16x3"
 
 
-def test_effective_precision_reports_what_runs():
-    """desc.precision is a request; wekws_hip_effective_precision is the truth a parity baseline can rely on."""
+def test_effective_precision_reports_the_products_that_run():
+    """desc.precision is a request; wekws_hip_effective_precision is the truth a parity baseline can rely on.  F16 is reported
+    where the model's routes (route.h) include a one-product kernel: DS-TCN h64 (ds64_g4) and MDTC h32 (mdtc32_g4) run one
+    fp16 product at precision F16 -- tests/test_hip_route_matrix.py's F16 control shows it on the device -- and report f16."""
     from wekws_amd import pack
     want = {("ds_tcn_h256", "default"): "f16x3", ("ds_tcn_h256", "f32"): "f32", ("ds_tcn_h256", "f16"): "f16",
-            ("ds_tcn_h64", "f16"): "f16x3", ("ds_tcn_h64", "f32"): "f32", ("mdtc_h64", "f16"): "f16",
-            ("mdtc_small", "f16"): "f16x3", ("gru_2x128", "f32"): "f32", ("gru_2x128", "default"): "f16x3",
+            ("ds_tcn_h64", "f16"): "f16", ("ds_tcn_h64", "f32"): "f32", ("mdtc_h64", "f16"): "f16",
+            ("mdtc_small", "f16"): "f16", ("gru_2x128", "f32"): "f32", ("gru_2x128", "default"): "f16x3",
             ("gru_2x128", "f16"): "f16x3", ("tcn_h64", "f16x3"): "f16x3", ("fsmn_small", "f16"): "f16x3"}
     for (name, prec), eff in want.items():
         cfg = dict(synth.MODEL_CONFIGS[name])
         m = build(cfg, synth.synth_state_dict(pack.model_spec(cfg), 3)).set_precision(prec)
         assert m.effective_precision() == eff, (name, prec)
-    cfg = dict(synth.MODEL_CONFIGS["ds_tcn_h256"])
-    m = build(cfg, synth.synth_state_dict(pack.model_spec(cfg), 3)).set_precision("f16").set_option("w16", 0)
-    assert m.effective_precision() == "f16x3"           # the generic kernel has no one-product mode
+    # options that take the one-product kernels away report f16x3: the LDS-tile kernels have no one-product mode
+    for name, opt, eff in (("ds_tcn_h256", "w16", "f16x3"), ("ds_tcn_h64", "g16", "f16x3"), ("mdtc_small", "g16", "f16x3"),
+                           ("mdtc_h64", "g16", "f16")):       # (MDTC h64 keeps mdtc64_w16 / the streaming kernel: one product)
+        cfg = dict(synth.MODEL_CONFIGS[name])
+        m = build(cfg, synth.synth_state_dict(pack.model_spec(cfg), 3)).set_precision("f16").set_option(opt, 0)
+        assert m.effective_precision() == eff, (name, opt)
 
 
 def test_weight_update_repacks():

@@ -241,3 +241,154 @@ def test_tight_bar_separates_f32_from_one_fp16_product(row):
             t += n
         e16 = max(tight_errors(cfg, np.concatenate(ys, 1), c, ry, rc))
         assert e16 > 4 * TIGHT_K, (rounds, e16)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# GRU and FSMN (route.h: gru_shape_plan / select_gru_route / gru_reserve_bytes, fsmn_shape_plan / select_fsmn_route), through
+# wekws_hip_debug_gru_route / wekws_hip_debug_fsmn_route.  GRU records: family, nn, spw, tchunk (0: one launch), nchunks, slots,
+# tiles, grid, pk | k2 << 1 | nf_in_kernel << 2.  FSMN records: tile frames, nt, utterances per workgroup, head slices, grid, LDS,
+# tiles of the call.
+GRU_EXPECT = {
+    (1, 10): ["gru_pipe", 0, 1, 0, 0, 1, 1, 33, 7],         # streaming chunk: time-packed, the non-finite pass in the kernel
+    (1, 98): ["gru_pipe", 0, 16, 0, 0, 1, 1, 33, 6],
+    (256, 10): ["gru_pipe", 0, 4, 0, 0, 64, 64, 256, 3],     # 64 slots x 4 stages fill the device: the separate non-finite launch
+    (256, 98): ["gru_pipe", 0, 16, 0, 0, 16, 16, 80, 6],
+    (1024, 98): ["gru_pipe", 0, 16, 0, 0, 64, 64, 256, 2],
+    (16384, 98): ["gru_f16", 2, 32, 0, 1, 0, 512, 512, 0],   # 8 rounds of slots or more: the layer-major kernels, two tiles each
+}
+FSMN_EXPECT = {
+    (1, 10): [64, 1, 1, 8, 1, 45056, 1, 0, 0],              # one utterance: the CTC head over 8 workgroups
+    (256, 10): [64, 1, 1, 1, 256, 45056, 1, 0, 0],
+    (1024, 32): [64, 2, 2, 1, 512, 153600, 1, 0, 0],         # two utterances per workgroup
+    (1024, 64): [64, 4, 1, 1, 1024, 149504, 1, 0, 0],
+    (4096, 32): [64, 2, 2, 1, 2048, 153600, 1, 0, 0],
+}
+
+
+@pytest.mark.parametrize("name,B,T", rm.GRU_CALLS)
+def test_gru_recipes_take_the_route_they_were_built_for(hooks, name, B, T):
+    r = rm.gru_route(hooks, M[name], B, T)
+    assert r["plan"] == "as_is" and rm.gru_record(r) == GRU_EXPECT[(B, T)], r
+    assert r["eff"] == "f16x3"
+    assert rm.gru_route(hooks, M[name], B, T, precision="f32")["family"] == "gru_f32"
+    assert rm.gru_route(hooks, M[name], B, T, opts={"gru_pipe": 0})["family"] == "gru_f16"
+
+
+@pytest.mark.parametrize("name,B,T", rm.FSMN_CALLS)
+def test_fsmn_recipes_take_the_route_they_were_built_for(hooks, name, B, T):
+    r = rm.fsmn_route(hooks, M[name], B, T)
+    assert r["plan"] == "as_is" and rm.fsmn_record(r) == FSMN_EXPECT[(B, T)] and r["ws"] == 0 and r["eff"] == "f16x3", r
+    assert rm.fsmn_route(hooks, M[name], B, T, precision="f32")["plan"] == "generic"
+
+
+def _gru_cfg(layers=2, hidden=128):
+    cfg = copy.deepcopy(M["gru_2x128"])
+    cfg["backbone"]["num_layers"] = layers
+    cfg["hidden_dim"] = hidden
+    return cfg
+
+
+def test_gru_shape_plan(hooks):
+    assert rm.gru_route(hooks, _gru_cfg(hidden=64), 3, 20)["plan"] == "padded"
+    for cfg in (_gru_cfg(layers=5), _gru_cfg(hidden=160)):
+        r = rm.gru_route(hooks, cfg, 3, 20)
+        assert r["plan"] == "generic" and r["why"], r
+
+
+@pytest.mark.parametrize("layers,hidden", [(1, 128), (2, 128), (2, 64), (4, 128)])
+def test_gru_reservation_covers_every_smaller_call(hooks, layers, hidden):
+    """wekws_hip_reserve(B, T) must hold every call of b <= B streams and t <= T frames, although a call's scratch is not
+    monotonic in (B, T) (gru_f16_spw, the wavefront's slots): every (B, T) of the grid against the maxima over all smaller calls."""
+    cfg = _gru_cfg(layers, hidden)
+    Bmax, Tmax = 4200, 40
+    need = np.zeros((Bmax, Tmax, 2), np.int64)
+    res = np.zeros((Bmax, Tmax, 2), np.int64)
+    for B in range(1, Bmax + 1):
+        for T in range(1, Tmax + 1):
+            r = rm.gru_route(hooks, cfg, B, T, reserve=True)
+            need[B - 1, T - 1] = r["plain"], r["gran"]
+            res[B - 1, T - 1] = r["res_plain"], r["res_gran"]
+    cover = np.maximum.accumulate(np.maximum.accumulate(need, axis=0), axis=1)
+    short = np.argwhere(res < cover)
+    assert short.size == 0, [(int(b) + 1, int(t) + 1, "plain gran".split()[k]) for b, t, k in short[:10]]
+    assert (need[:, :16] != cover[:, :16]).any()                  # (the non-monotonic case is in the grid)
+
+
+def test_gru_wavefront_invariants(hooks):
+    """The wavefront runs only where gru_pipe_geom admits it; its non-finite pass runs inside the launch only where every tile has a
+    slot of its own (tiles <= slots) and the extra workgroups find CUs beside the stages.  At the MI355X partition sizes (32 .. 256
+    CUs) the tiles <= slots bound never decides -- the CU bound alone gives the same answer for every B up to 70,000 --; at 384 CUs
+    it does."""
+    decides = {}
+    for layers in (1, 2, 3, 4):
+        cfg = _gru_cfg(layers)
+        for cus in (32, 64, 128, 256, 384):
+            for T in (10, 98):
+                n = 0
+                for B in range(1, 70001):
+                    r = rm.gru_route(hooks, cfg, B, T, cus=cus)
+                    if r["family"] != "gru_pipe":
+                        assert r["family"] == "gru_f16" and not r["nf_in_kernel"] and B > 8 * min(cus // (2 * layers), 128), (B, cus)
+                        continue
+                    smax = min(cus // r["stages"], 128)
+                    assert r["stages"] == 2 * layers and 1 <= r["slots"] <= smax and r["slots"] == min(r["tiles"], smax)
+                    assert r["tiles"] <= 8 * r["slots"] and r["slots_p"] % 8 == 0 and r["slots_p"] >= r["slots"]
+                    fits = (r["stages"] + 1) * r["slots"] <= cus
+                    if r["nf_in_kernel"]:
+                        assert r["tiles"] <= r["slots"] and fits
+                    n += fits and not r["nf_in_kernel"]
+                    assert r["grid"] == r["stages"] * r["slots_p"] + (r["slots"] if r["nf_in_kernel"] else 0)
+                decides[(layers, cus, T)] = n
+    assert all(n == 0 for (_, cus, _), n in decides.items() if cus <= 256), decides
+    assert any(n for (_, cus, _), n in decides.items() if cus == 384), decides
+
+
+def test_fsmn_route_invariants(hooks):
+    """Over the FSMN recipes and longer memories: LDS within kFsmnLdsLimit, nt u <= 4, tiles chained through the workspace exactly
+    when a call is longer than one tile; memories beyond the kernel's taps take the any-shape path."""
+    cfgs = [M[n] for n in M if M[n]["backbone"]["type"] == "fsmn"]
+    assert len(cfgs) >= 3
+    for base in list(cfgs):
+        for lo in (20, 40):
+            cfg = copy.deepcopy(base)
+            cfg["backbone"]["left_order"] = lo
+            cfgs.append(cfg)
+    generic = 0
+    for cfg in cfgs:
+        for B in (1, 2, 255, 256, 513, 1024, 4096):
+            for T in (1, 16, 17, 32, 33, 64, 65, 130):
+                r = rm.fsmn_route(hooks, cfg, B, T)
+                if r["plan"] == "generic":
+                    assert r["why"]
+                    generic += 1
+                    continue
+                assert 1 <= r["max_nt"] <= 4 and r["tile_frames"] == 16 * r["max_nt"] and r["ntiles"] == -(-T // r["tile_frames"])
+                assert r["u"] in (1, 2, 4) and r["nt"] * r["u"] <= 4 and r["nt"] * r["u"] <= r["max_nt"] or r["u"] == 1
+                assert 0 < r["lds"] <= 160 * 1024 - 2048 and r["grid"] == -(-B // r["u"]) and r["head_slices"] >= 1
+                assert (r["ws"] > 0) == (r["ntiles"] > 1)
+                last = rm.fsmn_route(hooks, cfg, B, T, tile=r["ntiles"] - 1)
+                assert 16 * last["nt"] >= T - (r["ntiles"] - 1) * r["tile_frames"] and 0 < last["lds"] <= 160 * 1024 - 2048
+    assert generic
+
+
+@pytest.mark.parametrize("seed", range(10))
+def test_effective_precision_agrees_with_the_routes(hooks, seed):
+    """F16 exactly when some call of the model under its options takes a one-product route (split 0)."""
+    rng = np.random.default_rng([0xEF, seed])
+    for _ in range(60):
+        cfg, _ = random_model_config(rng)
+        if cfg["backbone"]["type"] in ("gru", "fsmn"):
+            continue
+        opts = [int(rng.integers(0, 2)), 1, 1, 0, int(rng.integers(0, 2)), int(rng.integers(0, 2)), -1, 0, 0]
+        r0 = route(hooks, cfg, 1, 1, precision="f16", opts=opts)
+        if r0["plan"] == "generic":
+            continue
+        split0 = False
+        for B in (1, 3, 257):
+            for T in (1, 16, 17, 33, 65, 112):
+                for hi, ho, x16, c16, nti in ((0, 1, 1, 1, 1), (1, 1, 1, 1, 1), (0, 1, 0, 1, 1), (1, 1, 0, 0, 1), (1, 1, 1, 1, 2), (0, 0, 1, 1, 1)):
+                    r = route(hooks, cfg, B, T, has_in=hi, has_out=ho, precision="f16", x16=x16, cache16=c16, ntiles=nti, opts=opts)
+                    split0 |= r["family"] != "none" and r["split"] == 0
+        assert r0["eff"] == ("f16" if split0 else "f16x3"), (cfg, opts)
+        assert route(hooks, cfg, 1, 1, precision="f32")["eff"] == "f32"
+        assert route(hooks, cfg, 1, 1, precision="default")["eff"] == "f16x3"

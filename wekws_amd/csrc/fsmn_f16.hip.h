@@ -38,11 +38,8 @@ namespace wekws {
 
 constexpr int kFsmnThreads = 512;
 constexpr int kFsmnWaves = kFsmnThreads / 64;
-constexpr int kFsmnMaxLayers = 16;
 constexpr int kFsmnHeldK = 5;       // layers with <= this many k-steps keep a whole o-tile pair of weights in registers
-constexpr int kFsmnMaxTaps = 32;
-constexpr int kFsmnTileFrames = 64;
-constexpr int kFsmnLdsLimit = 160 * 1024 - 2048;   // (the maxima cells are static LDS beside the dynamic tile)
+// (kFsmnMaxLayers, kFsmnMaxTaps, kFsmnTileFrames, kFsmnLdsLimit: route.h, which plans the tiles)
 
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 struct __attribute__((packed, aligned(4))) F32x4U { float v[4]; };   // 16-byte store that only needs dword alignment
@@ -101,7 +98,8 @@ static __device__ __attribute__((noinline, unused)) void nf_repair_fsmn_call(con
   nf_repair_fsmn(nf, x, xs_b, ic, oc, y, ys_b, T, b);
 }
 
-// LDS plan for a tile of TT frames = U utterances x TT / U frames (bytes); shared by host (capacity check) and device
+// LDS plan for a tile of TT frames = U utterances x TT / U frames (bytes); the device's, and the launcher's check of the route
+// (route.h's fsmn_lds_bytes restates bytes())
 struct FsmnLds {
   int ss, seg, r0, r1, m_off;
   __host__ __device__ static inline FsmnLds make(const FsmnParams& P, int TT, int U) {
@@ -504,17 +502,18 @@ __global__ __launch_bounds__(kFsmnThreads) void fsmn_f16_kernel(const FsmnParams
 }
 
 template <int NT, int U>
-inline int launch_fsmn_nt(const FsmnParams& P, const FsmnArgs& A, hipStream_t stream) {
+inline int launch_fsmn_nt(const FsmnRoute& r, const FsmnParams& P, const FsmnArgs& A, hipStream_t stream) {
   const int lds = FsmnLds::make(P, 16 * NT, U).bytes();
-  if (lds > kFsmnLdsLimit) return -4;
+  if (lds > kFsmnLdsLimit || lds != r.lds_bytes || r.grid != (A.B + U - 1) / U || A.head_slices != r.head_slices) return -4;
   static DynLdsGrant grant;
   auto kern = fsmn_f16_kernel<NT, U>;
   if (grant_dynamic_lds(kern, lds, grant)) return -3;
-  hipLaunchKernelGGL(kern, dim3((A.B + U - 1) / U, A.head_slices > 1 ? A.head_slices : 1), dim3(kFsmnThreads), lds, stream, P, A);
+  hipLaunchKernelGGL(kern, dim3(r.grid, r.head_slices > 1 ? r.head_slices : 1), dim3(kFsmnThreads), lds, stream, P, A);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-// nt frame tiles per utterance, u utterances per workgroup (u in {1, 2, 4}, nt * u <= 4)
-int launch_fsmn_f16(int nt, int u, const FsmnParams& P, const FsmnArgs& A, hipStream_t stream);
+// runs a tile's route of select_fsmn_route (route.h): r.nt frame tiles per utterance, r.u utterances per workgroup (u in
+// {1, 2, 4}, nt * u <= 4); A.head_slices is the route's
+int launch_fsmn_f16(const FsmnRoute& r, const FsmnParams& P, const FsmnArgs& A, hipStream_t stream);
 
 }  // namespace wekws

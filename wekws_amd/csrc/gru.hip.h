@@ -21,11 +21,9 @@
 #include <stdint.h>
 
 #include "conv_stack.hip.h"
+#include "route.h"
 
 namespace wekws {
-
-constexpr int kGruMaxLayers = 4;
-constexpr int kGruH = 128;
 
 struct GruLayer {
   uint32_t a_ih, a_hh;  // packed A of W_ih, W_hh: [3H/16][H/16][64][4]
@@ -223,26 +221,25 @@ __global__ __launch_bounds__(kThreads, 2) void gru_kernel(const GruParams P, con
 }
 
 template <int NN>
-inline int launch_gru_nn(const GruParams& P, const float* x, int B, int T, const float* h0, float* y, float* hn,
+inline int launch_gru_nn(const GruRoute& r, const GruParams& P, const float* x, int B, int T, const float* h0, float* y, float* hn,
                          hipStream_t stream) {
   using G = GruGeom<NN>;
   const size_t lds = G::lds_bytes(P.kpre, P.nlayers);
-  if (lds > 160 * 1024) return -4;
+  if (lds != size_t(r.lds_bytes) || r.grid != (B + G::MB - 1) / G::MB) return -4;
   auto kern = gru_kernel<NN>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) !=
       hipSuccess)
     return -3;
-  const int grid = (B + G::MB - 1) / G::MB;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, stream, P, x, B, T, h0, y, hn);
+  hipLaunchKernelGGL(kern, dim3(r.grid), dim3(kThreads), lds, stream, P, x, B, T, h0, y, hn);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-inline int launch_gru(const GruParams& P, const float* x, int B, int T, const float* h0, float* y, float* hn,
+// runs a GRU_F32 route of select_gru_route (route.h)
+inline int launch_gru(const GruRoute& r, const GruParams& P, const float* x, int B, int T, const float* h0, float* y, float* hn,
                       hipStream_t stream) {
-  if (P.kpre > 128) return -4;
-  // 64-stream tiles amortise the per-step weight stream 4x better but need B large enough to fill the chip
-  const bool big = B >= 64 * 256 && GruGeom<4>::lds_bytes(P.kpre, P.nlayers) <= 160 * 1024;
-  return big ? launch_gru_nn<4>(P, x, B, T, h0, y, hn, stream) : launch_gru_nn<1>(P, x, B, T, h0, y, hn, stream);
+  if (r.family != GRU_F32 || P.kpre > 128) return -4;
+  return r.nn == 4 ? launch_gru_nn<4>(r, P, x, B, T, h0, y, hn, stream)
+         : r.nn == 1 ? launch_gru_nn<1>(r, P, x, B, T, h0, y, hn, stream) : -4;
 }
 
 // GRU: one workgroup per stream, behind the GRU kernels of the call (their loads sanitise, see nf_clean): a stream whose

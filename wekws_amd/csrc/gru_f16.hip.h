@@ -28,9 +28,6 @@
 #pragma once
 #include "conv_stack_f16.hip.h"
 #include "gru.hip.h"
-#ifndef WEKWS_GRU_MAX_PACKED_WGS
-#define WEKWS_GRU_MAX_PACKED_WGS 128
-#endif
 
 namespace wekws {
 
@@ -61,10 +58,12 @@ struct GruF16Geom {
   static constexpr int CS = 4;                              // steps of a layer input staged in LDS at a time (pass I)
   static constexpr int LDS_BYTES = 2 * CS * SEQ_STEP;       // pass I: two staging buffers; pass R re-uses the start
                                                             // for its two [hi | lo] plane buffers of h
-  static size_t seq_bytes(int tiles, int T) { return size_t(tiles) * T * SEQ_STEP; }       // tiles = workgroups of the call
-  static size_t gi_floats(int tiles, int T) { return size_t(tiles) * T * GI_STEP; }
-  static size_t sc_floats(int tiles, int T) { return size_t(tiles) * T * 16; }             // per step: 1 (tile) or 16 (columns)
 };
+// (route.h restates these sizes for the scratch bytes and LDS of a GRU route)
+static_assert(GruF16Geom<1>::SEQ_STEP == gru_f16_seq_step(1) && GruF16Geom<2>::SEQ_STEP == gru_f16_seq_step(2) &&
+              GruF16Geom<1>::GI_STEP == gru_f16_gi_step(1) && GruF16Geom<2>::GI_STEP == gru_f16_gi_step(2) &&
+              GruF16Geom<1>::CS == kGruF16Cs && GruF16Geom<2>::CS == kGruF16Cs && GruF16Geom<1>::LDS_BYTES == gru_f16_lds_bytes(1) &&
+              GruF16Geom<2>::LDS_BYTES == gru_f16_lds_bytes(2), "route.h: GruF16Geom sizes");
 
 __device__ __forceinline__ void gru_mfma1(f32x4& acc, const F16Frag& a, const f16x8& bh, const f16x8& bl) {
   acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.h, bh, acc, 0, 0, 0);
@@ -612,20 +611,6 @@ __global__ __launch_bounds__(kThreads) void gru_f16_kernel(const GruF16Params Q,
   }
 }
 
-// Streams per workgroup of a streaming chunk (T <= 16, single launch).  A workgroup's time does not depend on how many of
-// its 16 MFMA columns are real, but the time-parallel passes pack (step, stream) pairs into the columns when it owns <= 8
-// streams (gru_f16_kernel: TIME-PACKED mode) -- so with CUs to spare, fewer streams per workgroup is less work per
-// workgroup: 256 streams as 128 workgroups of 2 instead of 16 of 16.  Capped at kGruMaxPackedWgs workgroups: every one
-// streams the layers' 1.6 MB of weights from L2.
-constexpr int kGruMaxPackedWgs = WEKWS_GRU_MAX_PACKED_WGS;
-inline int gru_f16_spw(int B, int T, int cus) {
-  if (T > 16 || B <= 1) return 16;
-  const int wgs = cus < kGruMaxPackedWgs ? cus : kGruMaxPackedWgs;
-  int spw = 1;
-  while (spw < 16 && spw * wgs < B) spw *= 2;
-  return spw;
-}
-
 template <int NN, int MODE>
 inline int launch_gru_f16_mode(const GruF16Params& Q, const GruF16Workspace& ws, const float* x, int B, int T,
                                const float* h0, float* y, float* hn, int lsel, int tchunk, int nchunks,
@@ -641,50 +626,30 @@ inline int launch_gru_f16_mode(const GruF16Params& Q, const GruF16Workspace& ws,
 }
 
 template <int NN>
-inline int launch_gru_f16_nn(const GruF16Params& Q, const GruF16Workspace& ws, const float* x, int B, int T,
-                             const float* h0, float* y, float* hn, int cus, hipStream_t stream) {
+inline int launch_gru_f16_nn(const GruRoute& r, const GruF16Params& Q, const GruF16Workspace& ws, const float* x, int B, int T,
+                             const float* h0, float* y, float* hn, hipStream_t stream) {
   using G = GruF16Geom<NN>;
-  const int tiles = (B + G::MB - 1) / G::MB;
-  // few stream tiles and a long input: run the time-parallel passes over (tile x time chunk) so every CU works
-  if (2 * tiles <= cus && T >= 32) {
-    int nchunks = (2 * cus + tiles - 1) / tiles;
-    int tchunk = ((T + nchunks - 1) / nchunks + G::CS - 1) / G::CS * G::CS;
-    if (tchunk < 2 * G::CS) tchunk = 2 * G::CS;
-    nchunks = (T + tchunk - 1) / tchunk;
-    int rc = launch_gru_f16_mode<NN, 1>(Q, ws, x, B, T, h0, y, hn, 0, tchunk, nchunks, stream);
+  if (r.lds_bytes != G::LDS_BYTES) return -4;
+  // the time-parallel passes over (tile x time chunk), the recurrence per layer over the tiles
+  if (r.chunked) {
+    if (r.spw != G::MB) return -4;
+    int rc = launch_gru_f16_mode<NN, 1>(Q, ws, x, B, T, h0, y, hn, 0, r.tchunk, r.nchunks, stream);
     for (int l = 0; l < Q.base.nlayers && !rc; ++l) {
-      rc = launch_gru_f16_mode<NN, 2>(Q, ws, x, B, T, h0, y, hn, l, tchunk, nchunks, stream);
+      rc = launch_gru_f16_mode<NN, 2>(Q, ws, x, B, T, h0, y, hn, l, r.tchunk, r.nchunks, stream);
       if (!rc) rc = launch_gru_f16_mode<NN, 3>(Q, ws, x, B, T, h0, y, hn, l, T, 1, stream);
     }
-    if (!rc) rc = launch_gru_f16_mode<NN, 4>(Q, ws, x, B, T, h0, y, hn, 0, tchunk, nchunks, stream);
+    if (!rc) rc = launch_gru_f16_mode<NN, 4>(Q, ws, x, B, T, h0, y, hn, 0, r.tchunk, r.nchunks, stream);
     return rc;
   }
-  return launch_gru_f16_mode<NN, 0>(Q, ws, x, B, T, h0, y, hn, 0, T, 1, stream, NN == 1 ? gru_f16_spw(B, T, cus) : G::MB);
+  return launch_gru_f16_mode<NN, 0>(Q, ws, x, B, T, h0, y, hn, 0, T, 1, stream, r.spw);
 }
 
-inline bool gru_f16_supported(const GruF16Params& Q) { return Q.kpre16 <= 128 && Q.base.odim <= 128; }
-// stream tiles per workgroup: one (16 streams) until every CU has a workgroup, then two
-inline int gru_f16_nn(int B) { return B > 16 * 256 ? 2 : 1; }
-// workspace sizes of one call (bytes): each of the two sequence buffers, and the gate pre-activations
-inline void gru_f16_workspace_bytes(int B, int T, int cus, size_t* seq_bytes, size_t* gi_bytes, size_t* sc_bytes) {
-  if (gru_f16_nn(B) == 2) {
-    const int tiles = (B + 31) / 32;
-    *seq_bytes = GruF16Geom<2>::seq_bytes(tiles, T);
-    *gi_bytes = GruF16Geom<2>::gi_floats(tiles, T) * sizeof(float);
-    *sc_bytes = GruF16Geom<2>::sc_floats(tiles, T) * sizeof(float);
-  } else {
-    const int spw = gru_f16_spw(B, T, cus), tiles = (B + spw - 1) / spw;
-    *seq_bytes = GruF16Geom<1>::seq_bytes(tiles, T);
-    *gi_bytes = GruF16Geom<1>::gi_floats(tiles, T) * sizeof(float);
-    *sc_bytes = GruF16Geom<1>::sc_floats(tiles, T) * sizeof(float);
-  }
-}
-
-inline int launch_gru_f16(const GruF16Params& Q, const GruF16Workspace& ws, const float* x, int B, int T,
-                          const float* h0, float* y, float* hn, int cus, hipStream_t stream) {
-  if (!gru_f16_supported(Q)) return -4;
-  return gru_f16_nn(B) == 2 ? launch_gru_f16_nn<2>(Q, ws, x, B, T, h0, y, hn, cus, stream)
-                            : launch_gru_f16_nn<1>(Q, ws, x, B, T, h0, y, hn, cus, stream);
+// runs a GRU_F16 route of select_gru_route (route.h)
+inline int launch_gru_f16(const GruRoute& r, const GruF16Params& Q, const GruF16Workspace& ws, const float* x, int B, int T,
+                          const float* h0, float* y, float* hn, hipStream_t stream) {
+  if (r.family != GRU_F16 || Q.kpre16 > 128 || Q.base.odim > 128) return -4;
+  return r.nn == 2 ? launch_gru_f16_nn<2>(r, Q, ws, x, B, T, h0, y, hn, stream)
+         : r.nn == 1 ? launch_gru_f16_nn<1>(r, Q, ws, x, B, T, h0, y, hn, stream) : -4;
 }
 
 }  // namespace wekws

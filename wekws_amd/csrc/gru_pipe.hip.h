@@ -88,11 +88,10 @@
 namespace wekws {
 
 constexpr int kGruPipeStages = 2 * kGruMaxLayers;
-constexpr int kGruPipeMaxSlots = 128;
-// Granule buffers are RINGS of kGruPipeRing steps per slot (round 4: with one buffer position per step of the call, B = 1024 x
-// 98 frames wrote 504 MB and fetched 524 MB per launch -- PMC -- i.e. 5 TB/s of HBM traffic for intermediates that live a few
-// microseconds; a ring of 16 steps is 1.25 MB per slot and stays in L2 / the memory-side cache).
-constexpr int kGruPipeRingLog = 4, kGruPipeRing = 1 << kGruPipeRingLog;
+// (kGruPipeMaxSlots, kGruPipeRing, kGruPipeGiStep, kGruPipeHStep: route.h, which sizes a call's buffers.)  Granule buffers are
+// RINGS of kGruPipeRing steps per slot (round 4: with one buffer position per step of the call, B = 1024 x 98 frames wrote
+// 504 MB and fetched 524 MB per launch -- PMC -- i.e. 5 TB/s of HBM traffic for intermediates that live a few microseconds; a
+// ring of 16 steps is 1.25 MB per slot and stays in L2 / the memory-side cache).
 // control words (their own allocation per stream, zero when made, never re-allocated): [0] epoch, [1] workgroups done, [2] error,
 // [16 + 2 (slot * stages + stage)] 64-bit credits: {tag0, steps of this launch the stage's consumer has finished reading},
 // [16 + 2 slots * stages + slot * stages + stage] where the workgroup runs: tag0 << 4 | XCD
@@ -111,8 +110,6 @@ constexpr size_t kGruPipeCtlBytes = (size_t(kGruPipeCtlWords) * 4 + 255) / 256 *
 // hears of it on its next call (GruPipeWorkspace::err).
 constexpr unsigned kGruPipeFastSpins = 64;
 constexpr unsigned kGruPipeSpinLimit = 1u << 15;
-constexpr int kGruPipeGiStep = 8 * 4 * 1024;                  // bytes of one step of gate granules: [wave][item][lane][16]
-constexpr int kGruPipeHStep = 16 * 16 * 64;                   // bytes of one step of state granules: [k-octet][stream][8][8]
 constexpr int kGruPipePlanes = 128 * 1024;                    // staging buffers of stage 0; 16 steps of planes of a time-packed tile
 constexpr int kGruPipeLds = kGruPipePlanes + 1024;            // dynamic LDS of a workgroup (one per CU anyway): the planes, and
                                                               // behind them the per-column scales of a time-packed tile
@@ -1271,65 +1268,21 @@ __global__ __launch_bounds__(kThreads) void gru_pipe_kernel(const GruF16Params Q
   }
 }
 
-// ---- geometry of one call: stream slots per workgroup, tiles, resident slots ----
-struct GruPipeGeom {
-  int stages, spw, tiles, slots, slots_p;
-};
-inline bool gru_pipe_geom(int nlayers, int B, int T, int cus, GruPipeGeom* g) {
-  g->stages = 2 * nlayers;
-  int smax = cus / g->stages;
-  smax = smax > kGruPipeMaxSlots ? kGruPipeMaxSlots : smax;
-  if (smax < 1 || nlayers > kGruMaxLayers) return false;
-  // streaming chunks (T <= 16): fewer streams per tile while every tile still gets its own slot -- a workgroup's time does
-  // not depend on how many of its 16 MFMA columns are real, and tiles of <= 8 streams run the first stage time-packed (all
-  // steps in one or two MFMA tiles).  Longer inputs: full tiles -- a time-packed first stage makes ALL steps before the
-  // recurrence sees the first one (measured at B = 256 x 98 frames: 0.67x of the layer-major kernels)
-  int spw = T <= 16 ? 1 : 16;
-  while (spw < 16 && (B + spw - 1) / spw > smax) spw *= 2;
-  g->spw = spw;
-  g->tiles = (B + spw - 1) / spw;
-  g->slots = g->tiles < smax ? g->tiles : smax;
-  g->slots_p = (g->slots + 7) / 8 * 8;                       // block b runs on XCD b % 8: a slot's stages share an XCD
-  return true;
-}
-// bytes of one call: the plain workspace behind the control words (seq_in, seq_top, sc: each per slot) and the granule
-// workspace (gi per layer, state granules per layer below the top: a ring per slot each)
-struct GruPipeBytes {
-  size_t seq, sc, gi, hs;
-  size_t plain() const { return 2 * seq + sc; }
-  size_t granules(int nlayers) const { return size_t(nlayers) * gi + size_t(nlayers - 1) * hs; }
-};
-inline bool gru_pipe_bytes(int nlayers, int B, int T, int cus, GruPipeBytes* b) {
-  GruPipeGeom g;
-  if (!gru_pipe_geom(nlayers, B, T, cus, &g)) return false;
-  auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-  b->seq = al(size_t(g.slots) * T * GruF16Geom<1>::SEQ_STEP);
-  b->sc = al(size_t(g.slots) * T * 16 * sizeof(float));
-  b->gi = al(size_t(g.slots) * kGruPipeRing * kGruPipeGiStep);
-  b->hs = al(size_t(g.slots) * kGruPipeRing * kGruPipeHStep);
-  return true;
-}
-// (a slot's steps of one launch are numbered in an int)
-inline bool gru_pipe_supported(const GruF16Params& Q, int T) {
-  return gru_f16_supported(Q) && T < (1 << 24);
-}
-
-inline int launch_gru_pipe(const GruF16Params& Q, const GruPipeWorkspace& ws, const float* x, int B, int T, const float* h0,
-                           float* y, float* hn, int cus, hipStream_t stream) {
-  if (!gru_pipe_supported(Q, T)) return -4;
-  GruPipeGeom g;
-  if (!gru_pipe_geom(Q.base.nlayers, B, T, cus, &g)) return -4;
+// runs a GRU_PIPE route of select_gru_route (route.h); ws.nf is set exactly when the route runs the non-finite pass in the kernel
+inline int launch_gru_pipe(const GruRoute& r, const GruF16Params& Q, const GruPipeWorkspace& ws, const float* x, int B, int T, const float* h0,
+                           float* y, float* hn, hipStream_t stream) {
+  if (r.family != GRU_PIPE || r.lds_bytes != kGruPipeLds || (ws.nf != nullptr) != (r.nf_in_kernel != 0) || r.stages != 2 * Q.base.nlayers ||
+      r.slots < 1 || r.slots > kGruPipeMaxSlots)
+    return -4;
   using G = GruF16Geom<1>;
   static DynLdsGrant grant[4];
-  // <2>: at most two K steps of features in whole, 16-byte aligned octets (the 40-d / 64-d front ends); <4>: anything else
-  const bool k2 = Q.kpre16 <= 64 && Q.base.idim % 8 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0;
-  const bool pk = g.spw <= 8;
+  // <2>: at most two K steps of features in whole, 16-byte aligned octets; <4>: anything else.  pk: a time-packed first stage
+  const bool k2 = r.k2, pk = r.pk;
   auto kern = k2 ? (pk ? gru_pipe_kernel<2, true> : gru_pipe_kernel<2, false>) : (pk ? gru_pipe_kernel<4, true> : gru_pipe_kernel<4, false>);
   static_assert(kGruPipeLds >= int(G::LDS_BYTES), "staging buffers");
   if (grant_dynamic_lds(kern, kGruPipeLds, grant[(k2 ? 0 : 2) + (pk ? 1 : 0)])) return -3;
-  // (+ one non-finite workgroup per slot behind the stage workgroups when the caller handed a context over: gru_pipe_kernel)
-  hipLaunchKernelGGL(kern, dim3(g.stages * g.slots_p + (ws.nf ? g.slots : 0)), dim3(kThreads), kGruPipeLds, stream, Q, ws, x, B, T, h0,
-                     y, hn, g.tiles, g.slots, g.slots_p, g.spw);
+  // (grid: the stage workgroups, + one non-finite workgroup per slot behind them when the route says so: gru_pipe_kernel)
+  hipLaunchKernelGGL(kern, dim3(r.grid), dim3(kThreads), kGruPipeLds, stream, Q, ws, x, B, T, h0, y, hn, r.tiles, r.slots, r.slots_p, r.spw);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

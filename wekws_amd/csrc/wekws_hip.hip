@@ -334,32 +334,16 @@ struct wekws_hip_model {
   wekws::DenseBlock* d_dblocks = nullptr;
   wekws::StackParams sp{};
   wekws::DenseParams dp{};
-  // kernel selection (defaults = the product choice; wekws_hip_set_option overrides, for A/B measurements and the tests
-  // that keep every kernel family parity-green)
-  bool mm_eligible = false; // DS-TCN h256 + per-frame linear head: the all-matrix-core kernel (ds256_mm.hip.h) can serve it
-  bool mm_ok = false;     // ... and does: default for CTC-sized heads (odim > 16); WEKWS_HIP_OPT_MM forces it on / off
-                          // (keyword heads: the 16-wave kernel is 12 % faster)
-  bool mdtc16_eligible = false;
-  bool ds_stream_eligible = false;     // ds256_stream.hip.h: C = 256, kernel size 8, dilations 1 / 2 / 4 / 8
-  bool mdtc_stream_eligible = false;   // mdtc64_stream.hip.h: dilations 1 / 2 / 4 / 8, the two streams' caches fit into LDS
-  bool mdtc16_ok = false; // MDTC h64: the 16-wave kernel (WEKWS_HIP_OPT_MDTC16 = 0: the generic 8-wave one)
-  bool w16_ok = true;     // DS-TCN h256: the 16-wave kernel (WEKWS_HIP_OPT_W16 = 0: the generic 8-wave one)
+  // kernel selection (route.h): what the model admits, and the options (defaults = the product choice; wekws_hip_set_option
+  // overrides, for A/B measurements and the tests that keep every kernel family parity-green)
+  wekws::RouteFlags rf{};
+  wekws::RouteOptions ro{};
   float spread_log2 = 0.f;  // Image::spread_log2 of the weights this model was created from
-  bool out_of_envelope = false;  // DEFAULT / F16X3 request, but the weights are outside the split-fp16 envelope ...
-  int gru_pipe = 1;       // GRU: 1 the layer wavefront (gru_pipe.hip.h) when every tile of streams gets its own slot, 2 always, 0 never
-  bool auto_f32 = false;  // ... and therefore the F32 kernels run (WEKWS_HIP_OPT_ENVELOPE = 0 keeps the split-fp16 kernels)
-  bool g16_ok = true;     // ... calls without an incoming cache: the register-resident kernel (ds256_g16.hip.h; WEKWS_HIP_OPT_G16 = 0: ds256_w16)
-  bool g16_one_pass = false;   // ... with a grid of B workgroups instead of persistent ones (option value 2: A/B measurements)
-  bool g16_ctx = true;    // ... and calls WITH an incoming cache: the kernel's context variant (option value 3: never, i.e. ds256_w16)
-  int fsmn_slices = -1;   // FSMN / DS-TCN-CTC head slices per tile for small calls: -1 automatic, 0 / 1 off, n forces n
-  bool stream_ok = true;  // DS-TCN h256 / MDTC h64, chunks of <= 16 frames: the kernel with the LDS-resident cache
-                          // (WEKWS_HIP_OPT_STREAM = 0 keeps the batch kernel)
-  bool dense_ok = false;  // plain TCN whose paddings fit the dense-stack kernel's halo
   wekws::GruParams gp{};
   wekws::GruF16Params gq{};
   wekws::FsmnParams fq{};
-  int fsmn_max_nt = 0;
-  int fsmn_cus = 256;     // compute units of the device (FSMN utterance packing, GRU pass splitting)
+  wekws::FsmnPlan fplan{};
+  int fsmn_cus = 256;     // compute units of the device (every route's grid)
   // Conv backbones created with a hidden_dim / kernel_size no kernel is built for run as the next built shape (extra channels
   // and the extra OLDEST taps are zero everywhere, see pad_conv_shape); desc then describes the built shape and these keep
   // the caller's: its channel count, its cache length, and how its cache's per-block slices map into the wider ones.
@@ -370,7 +354,6 @@ struct wekws_hip_model {
   // A shape no specialised kernel is built for (wider / deeper / longer kernels than the reference's recipes use), or an FSMN
   // that must run exact f32: the any-shape path of generic.hip.h on the packer's blob as it is (d_w); nothing else of this
   // struct is used then.
-  wekws::RouteFlags rf{};   // what the model's shape admits (route.h); the bools above that say the same are kept for the options
   bool generic = false;
   wekws::GenericModel gm{};
   // Utterances with a NaN / Inf input leave the fast path and are re-computed in exact IEEE f32 (nonfinite.hip.h): the
@@ -399,23 +382,40 @@ static bool nf_fix_all() {
   return v;
 }
 static thread_local wekws::Route g_last_route{};             // the route of this thread's last conv launch (tests: hooks build)
+// the route of EVERY tile of this thread's last forward (wekws_hip_debug_route_trace; hooks build only), as records of 9 ints
+enum : int { kTraceOther = 0, kTraceConv = 1, kTraceAnyShape = 2, kTraceGru = 3, kTraceFsmn = 4, kTraceMaxTiles = 256, kRecInts = 9 };
 #ifdef WEKWS_TEST_HOOKS
-// the route of EVERY tile of this thread's last forward (wekws_hip_debug_route_trace; hooks build only)
-enum : int { kTraceOther = 0, kTraceConv = 1, kTraceAnyShape = 2, kTraceMaxTiles = 256 };
 struct RouteTrace {
   int path = kTraceOther, ntiles = 0;
-  wekws::Route tile[kTraceMaxTiles];
+  int rec[kTraceMaxTiles][kRecInts];
 };
 static thread_local RouteTrace g_route_trace;
-#endif
-static wekws::RouteOptions route_options(const wekws_hip_model* m) {
-  wekws::RouteOptions o;
-  o.w16_ok = m->w16_ok; o.g16_ok = m->g16_ok; o.g16_ctx = m->g16_ctx; o.g16_one_pass = m->g16_one_pass; o.stream_ok = m->stream_ok;
-  o.mdtc16_ok = m->mdtc16_ok; o.mm_ok = m->mm_ok;
-  o.f32 = m->desc.precision == WEKWS_HIP_PRECISION_F32 || m->auto_f32;
-  o.split = m->desc.precision != WEKWS_HIP_PRECISION_F16;
-  return o;
+// family, nt, split, ctx, fast, grid, threads, lds, utts_per_wg
+static void route_record(const wekws::Route& r, int* o) {
+  const int v[kRecInts] = {r.family, r.nt, r.split, r.ctx, r.fast, r.grid, r.threads, r.lds_bytes, r.utts_per_wg};
+  for (int i = 0; i < kRecInts; ++i) o[i] = v[i];
 }
+// family, nn, spw, tchunk (0: one launch), nchunks, slots, tiles, grid, pk | k2 << 1 | nf_in_kernel << 2
+static void route_record(const wekws::GruRoute& r, int* o) {
+  const int v[kRecInts] = {r.family, r.nn, r.spw, r.chunked ? r.tchunk : 0, r.nchunks, r.slots, r.tiles, r.grid,
+                           r.pk | r.k2 << 1 | r.nf_in_kernel << 2};
+  for (int i = 0; i < kRecInts; ++i) o[i] = v[i];
+}
+// tile_frames, nt, u, head_slices, grid, lds, ntiles, 0, 0
+static void route_record(const wekws::FsmnRoute& r, int* o) {
+  const int v[kRecInts] = {r.tile_frames, r.nt, r.u, r.head_slices, r.grid, r.lds_bytes, r.ntiles, 0, 0};
+  for (int i = 0; i < kRecInts; ++i) o[i] = v[i];
+}
+template <class R>
+static void trace(int path, const R& r) {
+  g_route_trace.path = path;
+  if (g_route_trace.ntiles < kTraceMaxTiles) route_record(r, g_route_trace.rec[g_route_trace.ntiles]);
+  ++g_route_trace.ntiles;
+}
+#else
+template <class R>
+static void trace(int, const R&) {}
+#endif
 
 // The device-side context of nonfinite.hip.h for a model whose kernels run shape `d` on packer-order blob `blob` (host).
 // tmax: most frames one kernel call covers.  Returns a WEKWS_HIP_* code.
@@ -738,7 +738,7 @@ static int create_generic(const wekws_hip_desc& d, const float* blob, size_t n_e
   m->desc = d;
   m->device = device;
   m->generic = true;
-  m->gru_pipe = 0;
+  m->ro.gru_pipe = 0;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->d_w), n_elems * sizeof(float));
   if (e == hipSuccess) e = hipMemcpy(m->d_w, blob, n_elems * sizeof(float), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
@@ -755,28 +755,20 @@ static int create_generic(const wekws_hip_desc& d, const float* blob, size_t n_e
 }
 
 static int create_fsmn(const wekws_hip_desc& d, const float* blob_in, size_t n_elems, int device, wekws_hip_model** out) {
-  // precision F32 is served with the reference's own arithmetic (exact f32 products): the any-shape path -- the block-floating
-  // kernel below is the default / F16X3 / F16 one
-  if (d.precision == WEKWS_HIP_PRECISION_F32) return create_generic(d, blob_in, n_elems, device, out);
+  // every precision request but F32 is served by the block-floating split-fp16 kernel (22-bit products, fp32 accumulate: the
+  // accuracy of fp32 arithmetic at any operand scale, tests/test_hip_parity.py::test_scale_sweep); F32, and shapes beyond the
+  // kernel's tables or LDS: the any-shape path (route.h: fsmn_shape_plan)
+  const wekws::FsmnPlan plan = wekws::fsmn_shape_plan(d);
+  if (plan.kind == wekws::SHAPE_GENERIC) return create_generic(d, blob_in, n_elems, device, out);
   std::vector<float> balanced(blob_in, blob_in + n_elems);
   balance_operand_channels(d, balanced.data());
   const float* blob = balanced.data();
-  // every precision request is served by the block-floating split-fp16 kernel (22-bit products, fp32 accumulate: the
-  // accuracy of fp32 arithmetic at any operand scale, tests/test_hip_parity.py::test_scale_sweep); an exact-f32 FSMN
-  // kernel is not built
-  if (d.num_layers > wekws::kFsmnMaxLayers) return create_generic(d, blob_in, n_elems, device, out);   // (deeper than the kernel's table)
   const int I = d.idim, A1 = d.aux[0], A2 = d.aux[1], C = d.hdim, D = d.num_stack, K = d.odim;
   const int ntaps = d.kernel_size + d.stack_size;
-  if (ntaps > wekws::kFsmnMaxTaps) return create_generic(d, blob_in, n_elems, device, out);            // (longer memory than the kernel's taps)
   wekws::FsmnParams q{};
   q.idim = I; q.odim = K; q.proj = D;
-  q.kin = round_up(I, 32); q.a1p = round_up(A1, 32); q.linp = round_up(C, 32); q.dp = round_up(D, 32);
-  q.a2p = round_up(A2, 32); q.op = round_up(K, 32);
-  q.nlayers = d.num_layers; q.ntaps = ntaps; q.P = ntaps - 1; q.taps_ld = round_up(ntaps, 4);
-  int max_nt = 0;
-  for (int nt = 1; nt <= wekws::kFsmnTileFrames / 16; ++nt)
-    if (wekws::FsmnLds::make(q, 16 * nt, 1).bytes() <= wekws::kFsmnLdsLimit) max_nt = nt;
-  if (!max_nt) return create_generic(d, blob_in, n_elems, device, out);                                 // (layer widths beyond the 160 KiB LDS tile)
+  q.kin = plan.q.kin; q.a1p = plan.q.a1p; q.linp = plan.q.linp; q.dp = plan.q.dp; q.a2p = plan.q.a2p; q.op = plan.q.op;
+  q.nlayers = d.num_layers; q.ntaps = ntaps; q.P = ntaps - 1; q.taps_ld = plan.q.taps_ld;
 
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
@@ -839,7 +831,7 @@ static int create_fsmn(const wekws_hip_desc& d, const float* blob_in, size_t n_e
     // accuracy: exact f32 instead (wekws_hip_effective_precision reports F32, wekws_hip_weight_spread_log2 the spread)
     const float spread = img.spread_log2;
     const int rc = create_generic(d, blob_in, n_elems, device, out);
-    if (rc == WEKWS_HIP_OK) { (*out)->spread_log2 = spread; (*out)->out_of_envelope = true; }
+    if (rc == WEKWS_HIP_OK) { (*out)->spread_log2 = spread; (*out)->rf.out_of_envelope = true; }
     return rc;
   }
 
@@ -848,7 +840,8 @@ static int create_fsmn(const wekws_hip_desc& d, const float* blob_in, size_t n_e
   m->desc = d;
   m->device = device;
   m->cache_len = q.P;
-  m->fsmn_max_nt = max_nt;
+  m->fplan = plan;
+  m->ro = wekws::route_defaults(d, m->rf);
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) m->fsmn_cus = prop.multiProcessorCount;
@@ -863,7 +856,7 @@ static int create_fsmn(const wekws_hip_desc& d, const float* blob_in, size_t n_e
   q.w = m->d_w;
   m->fq = q;
   m->spread_log2 = img.spread_log2;
-  if (const int rc = nf_setup(m, d, blob_in, n_elems, 16 * max_nt); rc != WEKWS_HIP_OK) {
+  if (const int rc = nf_setup(m, d, blob_in, n_elems, 16 * plan.max_nt); rc != WEKWS_HIP_OK) {
     nf_teardown(m);
     (void)hipFree(m->d_w);
     delete m;
@@ -873,56 +866,28 @@ static int create_fsmn(const wekws_hip_desc& d, const float* blob_in, size_t n_e
   return WEKWS_HIP_OK;
 }
 
+// The GRU route of a call (route.h); x16: the features 16-byte aligned
+static wekws::GruRoute gru_route(const wekws_hip_model* m, int B, int T, bool x16 = true) {
+  return wekws::select_gru_route(m->desc, m->ro, wekws::GruCall{B, T, x16, m->user_hdim != 0, m->fsmn_cus});
+}
 // Scratch bytes one wekws_hip_forward(m, B, T) takes from its stream's workspace (0: none) -- the single source for the
-// forward paths below and for wekws_hip_reserve.
-// GRU: does a call of T frames run the layer wavefront (gru_pipe.hip.h)?
-static bool gru_pipe_call(const wekws_hip_model* m, int B, int T) {
-  const wekws_hip_desc& d = m->desc;
-  if (!(d.backbone == WEKWS_HIP_BACKBONE_GRU && m->gru_pipe && d.precision != WEKWS_HIP_PRECISION_F32 && !m->auto_f32 &&
-        wekws::gru_pipe_supported(m->gq, T)))
-    return false;
-  wekws::GruPipeGeom g;
-  if (!wekws::gru_pipe_geom(d.num_layers, B, T, m->fsmn_cus, &g)) return false;
-  // many more tiles than resident slots: every workgroup serves several tiles one after the other (each round fills and drains
-  // the pipeline), and beyond ~8 rounds the layer-major kernels (all CUs on every pass, two tiles per workgroup) win --
-  // measured with the ring buffers, 2 layers: 1.65x at B = 2048 (2 rounds), 1.31x at 4096, 1.09x at 8192 (8 rounds), 0.96x at
-  // B = 16384 (16 rounds); option value 2 runs the wavefront anyway
-  return g.tiles <= 8 * g.slots || m->gru_pipe == 2;
-}
-// ... and the bytes of its granule buffer (a second per-stream buffer that holds nothing else)
-static size_t granule_need(const wekws_hip_model* m, int B, int T) {
-  if (B <= 0 || T <= 0 || !gru_pipe_call(m, B, T)) return 0;
-  wekws::GruPipeBytes pb{};
-  if (!wekws::gru_pipe_bytes(m->desc.num_layers, B, T, m->fsmn_cus, &pb)) return 0;
-  return pb.granules(m->desc.num_layers);
-}
+// forward paths below and for wekws_hip_reserve ...
 static size_t workspace_need(const wekws_hip_model* m, int B, int T) {
   const wekws_hip_desc& d = m->desc;
   if (B <= 0 || T <= 0) return 0;
   if (m->generic) return wekws::gen_workspace_bytes(m->gm, B, T);     // (monotonic in B and T)
-  if (d.backbone == WEKWS_HIP_BACKBONE_FSMN) {
-    const int TILE = 16 * m->fsmn_max_nt;
-    if (T <= TILE) return 0;
-    return 2 * size_t(B) * d.num_stack * m->cache_len * d.num_layers * sizeof(float);
-  }
-  if (d.backbone == WEKWS_HIP_BACKBONE_GRU) {
-    // (a hidden size below the built 128 runs zero-padded: widened copies of the caller's states, in + out)
-    const size_t padded = m->user_hdim ? 2 * size_t(d.num_layers) * B * d.hdim * sizeof(float) : 0;
-    if (d.precision == WEKWS_HIP_PRECISION_F32 || m->auto_f32 || !wekws::gru_f16_supported(m->gq)) return padded;
-    size_t seq_b = 0, gi_b = 0, sc_b = 0;
-    if (gru_pipe_call(m, B, T)) {                            // seq_in, seq_top | sc
-      wekws::GruPipeBytes pb{};
-      wekws::gru_pipe_bytes(d.num_layers, B, T, m->fsmn_cus, &pb);
-      return pb.plain() + padded;
-    }
-    wekws::gru_f16_workspace_bytes(B, T, m->fsmn_cus, &seq_b, &gi_b, &sc_b);
-    return 2 * ((seq_b + 255) / 256 * 256) + (gi_b + 255) / 256 * 256 + (sc_b + 255) / 256 * 256 + padded;
-  }
+  if (d.backbone == WEKWS_HIP_BACKBONE_FSMN) return wekws::select_fsmn_route(m->fplan, d, m->ro, B, T, 0, m->fsmn_cus).ws_bytes;
+  if (d.backbone == WEKWS_HIP_BACKBONE_GRU) return gru_route(m, B, T).plain_bytes;
   const size_t ce = size_t(B) * d.hdim * m->cache_len;
   const size_t padded = m->user_hdim ? 2 * ce : 0;          // the caller's caches, widened to the built channel count, in + out
   if (T <= WEKWS_HIP_TILE_FRAMES) return padded * sizeof(float);
   const size_t ge = d.head == WEKWS_HIP_HEAD_GLOBAL ? size_t(B) * d.hdim : 0;
   return (2 * ce + ge + padded) * sizeof(float);
+}
+// ... and the bytes of its granule buffer (the GRU wavefront: a second per-stream buffer that holds nothing else)
+static size_t granule_need(const wekws_hip_model* m, int B, int T) {
+  if (B <= 0 || T <= 0 || m->generic || m->desc.backbone != WEKWS_HIP_BACKBONE_GRU) return 0;
+  return gru_route(m, B, T).granule_bytes;
 }
 
 // Conv backbones whose hidden_dim C is not one of the built widths (32 / 64 / 128 / 256) run as the next built width Cp with
@@ -1011,12 +976,12 @@ static std::vector<float> pad_conv_shape(const wekws_hip_desc& d, const float* p
 static int forward_fsmn(wekws_hip_model* m, const float* x, int B, int T, const float* in_cache, float* y,
                         float* out_cache, hipStream_t stream) {
   const wekws_hip_desc& d = m->desc;
-  const int TILE = 16 * m->fsmn_max_nt;
-  const int ntiles = (T + TILE - 1) / TILE;
+  const wekws::FsmnRoute first = wekws::select_fsmn_route(m->fplan, d, m->ro, B, T, 0, m->fsmn_cus);
+  const int TILE = first.tile_frames, ntiles = first.ntiles;
   float* ws_cache[2] = {nullptr, nullptr};
   if (ntiles > 1) {
     const size_t ce = size_t(B) * d.num_stack * m->cache_len * d.num_layers;
-    char* base = stream_workspace(m, stream, workspace_need(m, B, T));
+    char* base = stream_workspace(m, stream, first.ws_bytes);
     if (!base) return WEKWS_HIP_ENOMEM;
     ws_cache[0] = reinterpret_cast<float*>(base);
     ws_cache[1] = ws_cache[0] + ce;
@@ -1034,22 +999,13 @@ static int forward_fsmn(wekws_hip_model* m, const float* x, int B, int T, const 
     a.B = B;
     a.T = Tt;
     a.nf = m->nf_dev;
-    // short inputs: pack 2 or 4 utterances into one workgroup, as long as every CU still gets a workgroup
-    const int nt = (Tt + 15) / 16;
-    int u = 1;
-    for (int cand = 4; cand >= 2; cand /= 2)
-      if (nt * cand <= m->fsmn_max_nt && nt * cand <= 4 && B >= cand * m->fsmn_cus &&
-          wekws::FsmnLds::make(m->fq, 16 * nt * cand, cand).bytes() <= wekws::kFsmnLdsLimit) { u = cand; break; }
-    // few tiles on many CUs: split the vocabulary-sized last layer over up to 8 workgroups per tile (fsmn_f16.hip.h)
-    a.head_slices = 1;
-    if (const int groups = (B + u - 1) / u; d.odim >= 256 && groups * 2 <= m->fsmn_cus) {
-      int sl = m->fsmn_cus / groups;
-      sl = sl > 8 ? 8 : sl;
-      if (m->fsmn_slices >= 0) sl = m->fsmn_slices > 0 ? m->fsmn_slices : 1;
-      a.head_slices = sl;
-    }
-    const int rc = wekws::launch_fsmn_f16(nt, u, m->fq, a, stream);
-    if (rc) return fail(rc, "fsmn launch failed (nt=%d u=%d): %s", nt, u, hipGetErrorString(hipGetLastError()));
+    // frame tiles, utterances per workgroup, head slices: route.h
+    const wekws::FsmnRoute route = i == 0 ? first : wekws::select_fsmn_route(m->fplan, d, m->ro, B, T, i, m->fsmn_cus);
+    trace(kTraceFsmn, route);
+    a.head_slices = route.head_slices;
+    const int rc = wekws::launch_fsmn_f16(route, m->fq, a, stream);
+    if (rc == -4) return fail(WEKWS_HIP_EUNSUPPORTED, "internal: the FSMN kernel has no instance for the route (nt=%d u=%d LDS %d)", route.nt, route.u, route.lds_bytes);
+    if (rc) return fail(rc, "fsmn launch failed (nt=%d u=%d): %s", route.nt, route.u, hipGetErrorString(hipGetLastError()));
   }
   return WEKWS_HIP_OK;
 }
@@ -1085,10 +1041,10 @@ int wekws_hip_create(const wekws_hip_desc* desc, const float* blob, size_t n_ele
   balance_operand_channels(d, balanced.data());
   blob = balanced.data();
   // which shape the kernels run: as it is, zero-padded to the next built one, or the any-shape path -- a pure function of the
-  // descriptor (route.h: conv_shape_plan; tests/test_route.py sweeps it on the CPU)
-  const wekws::ShapePlan plan = desc_conv(d) ? wekws::conv_shape_plan(d, wekws::kAmaxMaxBlocks) : wekws::ShapePlan{wekws::SHAPE_AS_IS, C, ks, nullptr};
+  // descriptor (route.h: conv_shape_plan / gru_shape_plan; tests/test_route.py sweeps them on the CPU)
+  const wekws::ShapePlan plan = desc_conv(d) ? wekws::conv_shape_plan(d, wekws::kAmaxMaxBlocks) : wekws::gru_shape_plan(d);
   if (plan.kind == wekws::SHAPE_GENERIC) return create_generic(d, orig, n_elems, device, out);
-  {
+  if (desc_conv(d)) {
     if (plan.kind == wekws::SHAPE_PADDED) {
       // any width up to 256 and any kernel size up to the built one (kws_model.py:114,142-157 take any): run as the next
       // built shape, zero-padded -- exact, see pad_conv_shape
@@ -1117,25 +1073,20 @@ int wekws_hip_create(const wekws_hip_desc* desc, const float* blob, size_t n_ele
       return WEKWS_HIP_OK;
     }
   }
-  if (!desc_conv(d)) {
-    if (C < 128 && d.head == WEKWS_HIP_HEAD_LINEAR && d.num_layers <= wekws::kGruMaxLayers) {
-      wekws_hip_desc dd = d;
-      dd.hdim = 128;
-      const std::vector<float> wide = pad_gru_hidden(d, blob, 128);
-      if (wide.size() != blob_elems(dd)) return fail(WEKWS_HIP_EINVAL, "internal: widened blob has %zu floats, expected %zu", wide.size(), blob_elems(dd));
-      const int rc = wekws_hip_create(&dd, wide.data(), wide.size(), device, out);
-      if (rc != WEKWS_HIP_OK) return rc;
-      wekws_hip_model* m = *out;
-      m->user_hdim = C;
-      if (const int rz = nf_set_skip_zero(m); rz != WEKWS_HIP_OK) { wekws_hip_destroy(m); *out = nullptr; return rz; }
-      m->widen.nb = m->narrow.nb = 1;                        // states (L, B, H): one "slice" per row
-      m->widen.s_off[0] = m->widen.d_off[0] = m->narrow.s_off[0] = m->narrow.d_off[0] = 0;
-      m->widen.len[0] = m->narrow.len[0] = C;
-      return WEKWS_HIP_OK;
-    }
-    // hidden sizes above the built 128, more layers than the kernels' tables, pooled / identity heads on a GRU
-    if (C != 128 || d.num_layers > wekws::kGruMaxLayers || d.head != WEKWS_HIP_HEAD_LINEAR)
-      return create_generic(d, orig, n_elems, device, out);
+  if (plan.kind == wekws::SHAPE_PADDED) {                   // GRU: zero-padded to the built hidden size (pad_gru_hidden)
+    wekws_hip_desc dd = d;
+    dd.hdim = plan.C;
+    const std::vector<float> wide = pad_gru_hidden(d, blob, plan.C);
+    if (wide.size() != blob_elems(dd)) return fail(WEKWS_HIP_EINVAL, "internal: widened blob has %zu floats, expected %zu", wide.size(), blob_elems(dd));
+    const int rc = wekws_hip_create(&dd, wide.data(), wide.size(), device, out);
+    if (rc != WEKWS_HIP_OK) return rc;
+    wekws_hip_model* m = *out;
+    m->user_hdim = C;
+    if (const int rz = nf_set_skip_zero(m); rz != WEKWS_HIP_OK) { wekws_hip_destroy(m); *out = nullptr; return rz; }
+    m->widen.nb = m->narrow.nb = 1;                          // states (L, B, H): one "slice" per row
+    m->widen.s_off[0] = m->widen.d_off[0] = m->narrow.s_off[0] = m->narrow.d_off[0] = 0;
+    m->widen.len[0] = m->narrow.len[0] = C;
+    return WEKWS_HIP_OK;
   }
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
@@ -1301,17 +1252,8 @@ int wekws_hip_create(const wekws_hip_desc* desc, const float* blob, size_t n_ele
     dp.pre_inv_s = pre_inv_s;
     sp.head_inv_s = dp.head_inv_s;
     // what this shape can run on: one pure function of the descriptor (route.h), shared with the CPU tests
-    m->rf = wekws::conv_route_flags(d, int(wekws::mdtc64_stream_lds_bytes(off)));
+    m->rf = wekws::conv_route_flags(d, int(wekws::ds256_stream_lds_bytes(off)), int(wekws::mdtc64_stream_lds_bytes(off)));
     if (m->rf.cache_len != off) { delete m; return fail(WEKWS_HIP_EINVAL, "internal: cache length %d vs %d", m->rf.cache_len, off); }
-    m->dense_ok = m->rf.dense_ok;
-    m->mdtc16_eligible = m->rf.mdtc16_eligible;
-    m->ds_stream_eligible = m->rf.ds_stream_eligible;
-    m->mdtc16_ok = m->mdtc16_eligible;
-    m->mdtc_stream_eligible = m->rf.mdtc_stream_eligible;
-    m->mm_eligible = m->rf.mm_eligible;
-    // default: on for CTC-sized heads (its activation planes feed an MFMA classifier directly), off for keyword heads
-    // (the 16-wave kernel is 12 % faster there)
-    m->mm_ok = m->mm_eligible && K > 16;
   } else {
     wekws::GruParams& gp = m->gp;
     gp.idim = d.idim;
@@ -1360,9 +1302,12 @@ int wekws_hip_create(const wekws_hip_desc* desc, const float* blob, size_t n_ele
   // the promise of DEFAULT / F16X3 is fp32-level accuracy: weights outside the envelope in which the split-fp16 kernels
   // keep it (Image::spread_log2) are served by the exact-f32 kernels instead (wekws_hip_effective_precision says so)
   m->spread_log2 = img.spread_log2;
-  m->out_of_envelope = (d.precision == WEKWS_HIP_PRECISION_DEFAULT || d.precision == WEKWS_HIP_PRECISION_F16X3) &&
-                       img.spread_log2 > WEKWS_HIP_F16X3_ENVELOPE_LOG2;
-  m->auto_f32 = m->out_of_envelope;
+  m->rf.out_of_envelope = (d.precision == WEKWS_HIP_PRECISION_DEFAULT || d.precision == WEKWS_HIP_PRECISION_F16X3) &&
+                          img.spread_log2 > WEKWS_HIP_F16X3_ENVELOPE_LOG2;
+  m->ro = wekws::route_defaults(d, m->rf);
+  // (measurement aid: WEKWS_GRU_NF_IN_KERNEL=0 keeps the GRU wavefront's non-finite pass a launch of its own)
+  static const bool nf_in_kernel_off = [] { const char* e = std::getenv("WEKWS_GRU_NF_IN_KERNEL"); return e && e[0] == '0'; }();
+  m->ro.gru_nf_in_kernel = !nf_in_kernel_off;
 
   auto cleanup = [&]() {
     if (m->d_w) (void)hipFree(m->d_w);
@@ -1436,20 +1381,8 @@ int wekws_hip_cache_len(const wekws_hip_model* m) { return !m ? 0 : m->user_hdim
 
 int wekws_hip_effective_precision(const wekws_hip_model* m) {
   if (!m) return fail(WEKWS_HIP_EINVAL, "NULL model");
-  const wekws_hip_desc& d = m->desc;
   if (m->generic) return WEKWS_HIP_PRECISION_F32;                                     // the any-shape path: exact f32 products
-  if (d.backbone == WEKWS_HIP_BACKBONE_FSMN) return WEKWS_HIP_PRECISION_F16X3;        // the block-floating kernel (fsmn_f16.hip.h)
-  if (d.backbone == WEKWS_HIP_BACKBONE_GRU)
-    return (d.precision == WEKWS_HIP_PRECISION_F32 || m->auto_f32 || !wekws::gru_f16_supported(m->gq))
-               ? WEKWS_HIP_PRECISION_F32 : WEKWS_HIP_PRECISION_F16X3;
-  if (d.precision == WEKWS_HIP_PRECISION_F32 || m->auto_f32) return WEKWS_HIP_PRECISION_F32;   // conv_stack.hip.h serves every shape
-  if (d.precision == WEKWS_HIP_PRECISION_F16) {
-    // one product per term only where a 16-wave kernel takes the `split` switch (wekws_hip_forward's dispatch)
-    const bool ds16 = d.backbone == WEKWS_HIP_BACKBONE_DS_TCN && d.hdim == 256 && m->w16_ok && !m->mm_ok;
-    const bool md16 = d.backbone == WEKWS_HIP_BACKBONE_MDTC && m->mdtc16_ok;
-    if (ds16 || md16) return WEKWS_HIP_PRECISION_F16;
-  }
-  return WEKWS_HIP_PRECISION_F16X3;
+  return wekws::effective_precision(m->desc, m->rf, m->ro, m->fsmn_cus);              // the routes the model can take
 }
 
 float wekws_hip_weight_spread_log2(const wekws_hip_model* m) { return m ? m->spread_log2 : -1.f; }
@@ -1470,50 +1403,19 @@ size_t wekws_hip_output_elems(const wekws_hip_model* m, int B, int T) {
 
 int wekws_hip_set_option(wekws_hip_model* m, int option, int value) {
   if (!m) return fail(WEKWS_HIP_EINVAL, "NULL model");
-  switch (option) {
-    case WEKWS_HIP_OPT_W16: m->w16_ok = value != 0; break;
-    case WEKWS_HIP_OPT_MDTC16: m->mdtc16_ok = m->mdtc16_eligible && value != 0; break;
-    case WEKWS_HIP_OPT_STREAM: m->stream_ok = value != 0; break;
-    case WEKWS_HIP_OPT_MM: m->mm_ok = m->mm_eligible && (value < 0 ? m->desc.odim > 16 : value != 0); break;
-    case WEKWS_HIP_OPT_HEAD_SLICES: m->fsmn_slices = value; break;
-    case WEKWS_HIP_OPT_G16: m->g16_ok = value != 0; m->g16_one_pass = value == 2; m->g16_ctx = value != 3; break;   // (2: one workgroup per utterance; 3: no context variants -- measurement aids)
-    case WEKWS_HIP_OPT_ENVELOPE: m->auto_f32 = m->out_of_envelope && value != 0; break;
-    case WEKWS_HIP_OPT_GRU_PIPE: m->gru_pipe = value < 0 ? 1 : value > 2 ? 2 : value; break;
-    default: return fail(WEKWS_HIP_EINVAL, "unknown option %d", option);
-  }
+  if (wekws::apply_route_option(m->ro, m->desc, m->rf, option, value)) return fail(WEKWS_HIP_EINVAL, "unknown option %d", option);
   return WEKWS_HIP_OK;
 }
 
 size_t wekws_hip_workspace_bytes(const wekws_hip_model* m, int B, int T) { return m ? workspace_need(m, B, T) + granule_need(m, B, T) : 0; }
 
-// What a reservation for "calls of up to (B, T)" has to hold: workspace_need() is not monotonic -- a GRU chunk of <= 16
-// frames spreads its streams over more, smaller workgroups (gru_f16_spw), so (256, 10) needs more scratch than (256, 20)
-// and (128, 10) as much as (256, 10) -- so the maximum over the shapes where the geometry changes is taken: the frame
-// counts {T, min(T, 16)} and the stream counts B, the packed-workgroup boundaries 2^k x (workgroups) below B, and the
-// two-tiles-per-workgroup threshold.
+// What a reservation for "calls of up to (B, T)" has to hold: the GRU's scratch is not monotonic in (B, T) (route.h:
+// gru_reserve_bytes); every other path's is
 static void reserve_need(const wekws_hip_model* m, int B, int T, size_t* plain, size_t* gran) {
-  *plain = *gran = 0;
-  const int ts[2] = {T, T < 16 ? T : 16};
-  int bs[12], nb = 0;
-  bs[nb++] = B;
-  const int wgs = m->fsmn_cus < wekws::kGruMaxPackedWgs ? m->fsmn_cus : wekws::kGruMaxPackedWgs;
-  for (int k = 1; k <= 16; k *= 2)
-    if (k * wgs < B) bs[nb++] = k * wgs;
-  if (16 * 256 < B) bs[nb++] = 16 * 256;
-  if (m->desc.backbone == WEKWS_HIP_BACKBONE_GRU) {
-    // the wavefront's geometry (gru_pipe_geom): most slots (= most rings) with one stream per tile
-    wekws::GruPipeGeom g;
-    if (wekws::gru_pipe_geom(m->desc.num_layers, 1 << 30, 1, m->fsmn_cus, &g)) {
-      if (g.slots < B) bs[nb++] = g.slots;
-      if (16 * g.slots + 1 <= B) bs[nb++] = 16 * g.slots + 1;
-    }
-  }
-  for (int i = 0; i < nb; ++i)
-    for (int j = 0; j < 2; ++j) {
-      const size_t n = workspace_need(m, bs[i], ts[j]), g = granule_need(m, bs[i], ts[j]);
-      *plain = n > *plain ? n : *plain;
-      *gran = g > *gran ? g : *gran;
-    }
+  if (!m->generic && m->desc.backbone == WEKWS_HIP_BACKBONE_GRU)
+    return wekws::gru_reserve_bytes(m->desc, m->ro, wekws::GruCall{B, T, 1, m->user_hdim != 0, m->fsmn_cus}, plain, gran);
+  *plain = workspace_need(m, B, T);
+  *gran = 0;
 }
 
 int wekws_hip_reserve(wekws_hip_model* m, int B, int T, void* stream_) {
@@ -1525,7 +1427,7 @@ int wekws_hip_reserve(wekws_hip_model* m, int B, int T, void* stream_) {
   if (!guard.ok) return fail(WEKWS_HIP_EDEVICE, "hipSetDevice(%d)", m->device);
   if (need && !stream_workspace(m, static_cast<hipStream_t>(stream_), need)) return WEKWS_HIP_ENOMEM;
   if (gran && !stream_workspace(m, static_cast<hipStream_t>(stream_), gran, true)) return WEKWS_HIP_ENOMEM;
-  if (m->desc.backbone == WEKWS_HIP_BACKBONE_GRU && m->gru_pipe && !stream_ctl(m, static_cast<hipStream_t>(stream_))) return WEKWS_HIP_ENOMEM;
+  if (m->desc.backbone == WEKWS_HIP_BACKBONE_GRU && m->ro.gru_pipe && !stream_ctl(m, static_cast<hipStream_t>(stream_))) return WEKWS_HIP_ENOMEM;
   return WEKWS_HIP_OK;
 }
 
@@ -1612,11 +1514,12 @@ __global__ void debug_hog_kernel(unsigned long long ticks, int busy) {
 // The routing functions of route.h, callable WITHOUT a device (tests/test_route.py, hooks library only).
 //   desc: any conv descriptor wekws_hip_create accepts.  opts[9] (or NULL = the defaults for that precision): w16_ok, g16_ok, g16_ctx,
 //   g16_one_pass, stream_ok, mdtc16_ok, mm_ok (-1: the default: CTC-sized heads), f32, split.  call[8]: B, T (of the tile), ntiles,
-//   has_in, has_out, x16, cache16, cus.  out[14]: plan kind, built C, built ks, family, nt, split, ctx, fast, grid, threads, lds,
-//   utts_per_wg, cache_len (built shape), max_pad.  why: the reason text for "any-shape path" / "no kernel".  Returns 0.
+//   has_in, has_out, x16, cache16, cus.  out[16]: plan kind, built C, built ks, family, nt, split, ctx, fast, grid, threads, lds,
+//   utts_per_wg, cache_len (built shape), max_pad, head_slices, effective precision (of the model under these options).  why: the
+//   reason text for "any-shape path" / "no kernel".  Returns 0.
 extern "C" int wekws_hip_debug_conv_route(const wekws_hip_desc* desc, const int* opts, const int* call, int* out, char* why, int why_len) {
   if (!desc || !call || !out || !desc_conv(*desc)) return WEKWS_HIP_EINVAL;
-  for (int i = 0; i < 14; ++i) out[i] = 0;
+  for (int i = 0; i < 16; ++i) out[i] = 0;
   if (why && why_len > 0) why[0] = 0;
   auto say = [&](const char* t) { if (why && why_len > 0 && t) { std::strncpy(why, t, size_t(why_len) - 1); why[why_len - 1] = 0; } };
   const wekws::ShapePlan plan = wekws::conv_shape_plan(*desc, wekws::kAmaxMaxBlocks);
@@ -1624,23 +1527,20 @@ extern "C" int wekws_hip_debug_conv_route(const wekws_hip_desc* desc, const int*
   if (plan.kind == wekws::SHAPE_GENERIC) { say(plan.why); return WEKWS_HIP_OK; }
   wekws_hip_desc d = *desc;
   d.hdim = plan.C; d.kernel_size = plan.ks;
-  const wekws::RouteFlags f = wekws::conv_route_flags(d, 0);
-  wekws::RouteFlags ff = wekws::conv_route_flags(d, int(wekws::mdtc64_stream_lds_bytes(f.cache_len)));
-  wekws::RouteOptions o;
-  o.f32 = d.precision == WEKWS_HIP_PRECISION_F32;
-  o.split = d.precision != WEKWS_HIP_PRECISION_F16;
-  o.mdtc16_ok = ff.mdtc16_eligible;
-  o.mm_ok = ff.mm_eligible && d.odim > 16;
+  const int cache_len = wekws::conv_route_flags(d, 0, 0).cache_len;
+  const wekws::RouteFlags ff = wekws::conv_route_flags(d, int(wekws::ds256_stream_lds_bytes(cache_len)), int(wekws::mdtc64_stream_lds_bytes(cache_len)));
+  wekws::RouteOptions o = wekws::route_defaults(d, ff);
   if (opts) {
     o.w16_ok = opts[0]; o.g16_ok = opts[1]; o.g16_ctx = opts[2]; o.g16_one_pass = opts[3]; o.stream_ok = opts[4];
-    o.mdtc16_ok = ff.mdtc16_eligible && opts[5]; o.mm_ok = ff.mm_eligible && (opts[6] < 0 ? d.odim > 16 : opts[6] != 0);
+    wekws::apply_route_option(o, d, ff, WEKWS_HIP_OPT_MDTC16, opts[5]);
+    wekws::apply_route_option(o, d, ff, WEKWS_HIP_OPT_MM, opts[6]);
     o.f32 = opts[7]; o.split = opts[8];
   }
   wekws::RouteCall c{call[0], call[1], call[2], call[3], call[4], call[5], call[6], call[7]};
-  const wekws::Route r = wekws::select_conv_route(d, ff, o, c, int(wekws::ds256_stream_lds_bytes(ff.cache_len)),
-                                                  int(wekws::mdtc64_stream_lds_bytes(ff.cache_len)));
+  const wekws::Route r = wekws::select_conv_route(d, ff, o, c);
   out[3] = r.family; out[4] = r.nt; out[5] = r.split; out[6] = r.ctx; out[7] = r.fast; out[8] = r.grid; out[9] = r.threads; out[10] = r.lds_bytes;
-  out[11] = r.utts_per_wg; out[12] = ff.cache_len; out[13] = ff.max_pad;
+  out[11] = r.utts_per_wg; out[12] = ff.cache_len; out[13] = ff.max_pad; out[14] = r.head_slices;
+  out[15] = wekws::effective_precision(d, ff, o, c.cus);
   if (r.family == wekws::ROUTE_NONE) say(r.why_not);
   else say(wekws::route_family_name(r.family));
   return WEKWS_HIP_OK;
@@ -1653,22 +1553,75 @@ extern "C" int wekws_hip_debug_last_route(int* out) {
   out[8] = r.utts_per_wg;
   return WEKWS_HIP_OK;
 }
-// the route of every tile of the calling thread's last forward: out[0] = path (0: no conv kernel ran -- GRU / FSMN, or no forward
-// yet; 1: the conv routes of route.h; 2: the any-shape path of generic.hip.h), out[1] = tiles of the call, then per tile (at most
-// max_tiles, and the first 256 of a call) the 9 values of wekws_hip_debug_last_route.  out holds 2 + 9 * max_tiles ints.  Returns
-// the number of tile records written.
+// GRU (hooks library only): desc: any GRU descriptor wekws_hip_create accepts; opts: nopts (WEKWS_HIP_OPT_*, value) pairs applied to
+// the defaults.  call[5]: B, T, x16, cus, with_reserve.  out[20] (int64): plan kind, built hidden size, the 9 ints of the trace
+// record (route_record), stages, slots_p, lds, chunked, plain bytes, granule bytes, reserved plain / granule bytes (with_reserve),
+// effective precision.  why: the family's name, or the reason.  Returns 0.
+extern "C" int wekws_hip_debug_gru_route(const wekws_hip_desc* desc, const int* opts, int nopts, const int* call, int64_t* out, char* why,
+                                         int why_len) {
+  if (!desc || !call || !out || desc->backbone != WEKWS_HIP_BACKBONE_GRU || (nopts && !opts)) return WEKWS_HIP_EINVAL;
+  for (int i = 0; i < 20; ++i) out[i] = 0;
+  auto say = [&](const char* t) { if (why && why_len > 0 && t) { std::strncpy(why, t, size_t(why_len) - 1); why[why_len - 1] = 0; } };
+  const wekws::ShapePlan plan = wekws::gru_shape_plan(*desc);
+  out[0] = plan.kind; out[1] = plan.C;
+  if (plan.kind == wekws::SHAPE_GENERIC) { say(plan.why); return WEKWS_HIP_OK; }
+  wekws_hip_desc d = *desc;
+  d.hdim = plan.C;
+  const wekws::RouteFlags f{};
+  wekws::RouteOptions o = wekws::route_defaults(d, f);
+  for (int i = 0; i < nopts; ++i)
+    if (wekws::apply_route_option(o, d, f, opts[2 * i], opts[2 * i + 1])) return WEKWS_HIP_EINVAL;
+  const wekws::GruCall c{call[0], call[1], call[2], plan.kind == wekws::SHAPE_PADDED, call[3]};
+  const wekws::GruRoute r = wekws::select_gru_route(d, o, c);
+  int rec[kRecInts];
+  route_record(r, rec);
+  for (int i = 0; i < kRecInts; ++i) out[2 + i] = rec[i];
+  out[11] = r.stages; out[12] = r.slots_p; out[13] = r.lds_bytes; out[14] = r.chunked;
+  out[15] = int64_t(r.plain_bytes); out[16] = int64_t(r.granule_bytes);
+  if (call[4]) {
+    size_t p = 0, g = 0;
+    wekws::gru_reserve_bytes(d, o, c, &p, &g);
+    out[17] = int64_t(p); out[18] = int64_t(g);
+  }
+  out[19] = wekws::effective_precision(d, f, o, c.cus);
+  say(r.family == wekws::GRU_NONE ? r.why_not : wekws::gru_family_name(r.family));
+  return WEKWS_HIP_OK;
+}
+// FSMN (hooks library only): desc: any FSMN descriptor; opts / nopts as above.  call[4]: B, T, tile index, cus.  out[16]: plan kind,
+// max_nt, the 9 ints of the tile's trace record, workspace bytes of the call, effective precision, 0...  Returns 0.
+extern "C" int wekws_hip_debug_fsmn_route(const wekws_hip_desc* desc, const int* opts, int nopts, const int* call, int64_t* out, char* why,
+                                          int why_len) {
+  if (!desc || !call || !out || desc->backbone != WEKWS_HIP_BACKBONE_FSMN || (nopts && !opts)) return WEKWS_HIP_EINVAL;
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  auto say = [&](const char* t) { if (why && why_len > 0 && t) { std::strncpy(why, t, size_t(why_len) - 1); why[why_len - 1] = 0; } };
+  const wekws::FsmnPlan plan = wekws::fsmn_shape_plan(*desc);
+  out[0] = plan.kind; out[1] = plan.max_nt;
+  if (plan.kind == wekws::SHAPE_GENERIC) { say(plan.why); return WEKWS_HIP_OK; }
+  const wekws::RouteFlags f{};
+  wekws::RouteOptions o = wekws::route_defaults(*desc, f);
+  for (int i = 0; i < nopts; ++i)
+    if (wekws::apply_route_option(o, *desc, f, opts[2 * i], opts[2 * i + 1])) return WEKWS_HIP_EINVAL;
+  const wekws::FsmnRoute r = wekws::select_fsmn_route(plan, *desc, o, call[0], call[1], call[2], call[3]);
+  int rec[kRecInts];
+  route_record(r, rec);
+  for (int i = 0; i < kRecInts; ++i) out[2 + i] = rec[i];
+  out[11] = int64_t(r.ws_bytes);
+  out[12] = wekws::effective_precision(*desc, f, o, call[3]);
+  say(r.why_not ? r.why_not : "fsmn_f16");
+  return WEKWS_HIP_OK;
+}
+// the route of every tile of the calling thread's last forward: out[0] = path (0: no forward yet; 1: the conv routes of route.h;
+// 2: the any-shape path of generic.hip.h; 3: the GRU route of route.h -- one record; 4: the FSMN routes of route.h), out[1] =
+// records of the call, then per record (at most max_tiles, and the first 256 of a call) its 9 ints: conv, the values of
+// wekws_hip_debug_last_route; GRU / FSMN, route_record's.  out holds 2 + 9 * max_tiles ints.  Returns the number of records written.
 extern "C" int wekws_hip_debug_route_trace(int* out, int max_tiles) {
   if (!out || max_tiles < 0) return WEKWS_HIP_EINVAL;
   const RouteTrace& t = g_route_trace;
   out[0] = t.path; out[1] = t.ntiles;
   int n = t.ntiles < kTraceMaxTiles ? t.ntiles : kTraceMaxTiles;
   n = n < max_tiles ? n : max_tiles;
-  for (int i = 0; i < n; ++i) {
-    const wekws::Route& r = t.tile[i];
-    int* o = out + 2 + 9 * i;
-    o[0] = r.family; o[1] = r.nt; o[2] = r.split; o[3] = r.ctx; o[4] = r.fast; o[5] = r.grid; o[6] = r.threads; o[7] = r.lds_bytes;
-    o[8] = r.utts_per_wg;
-  }
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < kRecInts; ++k) out[2 + kRecInts * i + k] = t.rec[i][k];
   return n;
 }
 extern "C" int wekws_hip_debug_hog(int device, int blocks, int ms, void* stream_) {
@@ -1711,19 +1664,22 @@ int wekws_hip_forward(wekws_hip_model* m, const float* x, int B, int T, const fl
     const int rc = forward_fsmn(m, x, B, T, in_cache, y, out_cache, stream);
     if (rc) return rc;
   } else if (d.backbone == WEKWS_HIP_BACKBONE_GRU) {
-    const bool f16 = d.precision != WEKWS_HIP_PRECISION_F32 && !m->auto_f32 && wekws::gru_f16_supported(m->gq);
     // a wavefront launch of an EARLIER call on this stream that gave up is reported here, by the call that follows it (one
     // read of host memory; the reference's forward either returns correct values or raises -- keyword_spotting.cc:77-79)
     int rc = stream_health(m, stream);
     if (rc) return rc;
+    // ---- which kernels, their geometry and scratch: route.h (select_gru_route)
+    const wekws::GruRoute route = gru_route(m, B, T, reinterpret_cast<uintptr_t>(x) % 16 == 0);
+    if (route.family == wekws::GRU_NONE) return fail(WEKWS_HIP_EUNSUPPORTED, "no GRU kernel for this call: %s", route.why_not ? route.why_not : "?");
+    trace(kTraceGru, route);
+    // workspace: one grow-only buffer per (model, stream) -- calls on the same stream are ordered by the stream, calls on
+    // different streams never share a buffer
+    char* base = nullptr;
+    if (route.plain_bytes && !(base = stream_workspace(m, stream, route.plain_bytes))) return WEKWS_HIP_ENOMEM;
     float* user_h_out = nullptr;
-    bool gru_nf_in_kernel = false;
     if (m->user_hdim) {                                      // zero-padded hidden size: widened copies of the caller's states
-      const size_t need = workspace_need(m, B, T);
-      char* base = stream_workspace(m, stream, need);
-      if (!base) return WEKWS_HIP_ENOMEM;
       const size_t he = size_t(d.num_layers) * B * d.hdim;
-      float* wide = reinterpret_cast<float*>(base + need) - 2 * he;       // (the tail of the workspace)
+      float* wide = reinterpret_cast<float*>(base + route.plain_bytes) - 2 * he;       // (the tail of the workspace)
       const int rows = d.num_layers * B;
       const int grid = int(std::min<size_t>((he + 255) / 256, 4096));
       if (in_cache) {
@@ -1732,50 +1688,31 @@ int wekws_hip_forward(wekws_hip_model* m, const float* x, int B, int T, const fl
       }
       if (out_cache) { user_h_out = out_cache; out_cache = wide + he; }
     }
-    if (f16) {
-      // workspace (layer sequences + gate pre-activations): one grow-only buffer per (model, stream) -- calls on the
-      // same stream are ordered by the stream, calls on different streams never share a buffer
-      size_t seq_b = 0, gi_b = 0, sc_b = 0;
-      char* base = stream_workspace(m, stream, workspace_need(m, B, T));
-      if (!base) return WEKWS_HIP_ENOMEM;
-      if (gru_pipe_call(m, B, T)) {
-        wekws::GruPipeBytes pb{};
-        wekws::gru_pipe_bytes(d.num_layers, B, T, m->fsmn_cus, &pb);
-        wekws::GruPipeGeom geo;
-        wekws::gru_pipe_geom(d.num_layers, B, T, m->fsmn_cus, &geo);
-        char* gran = stream_workspace(m, stream, pb.granules(d.num_layers), true, unsigned(geo.slots) << 8 | unsigned(d.num_layers));
-        if (!gran) return WEKWS_HIP_ENOMEM;
-        wekws::GruPipeWorkspace ws{};
-        ws.ctl = stream_ctl(m, stream, &ws.err);
-        if (!ws.ctl) return WEKWS_HIP_ENOMEM;
-        ws.seq_in = base;
-        ws.seq_top = ws.seq_in + pb.seq;
-        ws.sc = reinterpret_cast<float*>(ws.seq_top + pb.seq);
-        for (int l = 0; l < d.num_layers; ++l) { ws.gi[l] = gran; gran += pb.gi; }
-        for (int l = 0; l + 1 < d.num_layers; ++l) { ws.hs[l] = gran; gran += pb.hs; }
-        // Non-finite pass: the wavefront's own extra workgroups (one per slot) where there are CUs left for them to run BESIDE the
-        // pipeline -- streaming chunks, small batches: no second launch, 2.68 -> 2.48 us per frame at B = 1 --; where the stage
-        // workgroups fill the device they would only start behind it and scan 16 streams each (measured at B = 1024 x 98:
-        // 0.186 ms against 0.176 with the separate launch, whose 1024 small workgroups scan in parallel): the launch stays.
-        static const bool nf_in_kernel_off = [] { const char* e = std::getenv("WEKWS_GRU_NF_IN_KERNEL"); return e && e[0] == '0'; }();   // (A/B aid)
-        if (!nf_in_kernel_off && (geo.stages + 1) * geo.slots <= m->fsmn_cus) {
-          ws.nf = m->nf_dev;
-          gru_nf_in_kernel = true;
-        }
-        rc = wekws::launch_gru_pipe(m->gq, ws, x, B, T, in_cache, y, out_cache, m->fsmn_cus, stream);
-      } else {
-        wekws::gru_f16_workspace_bytes(B, T, m->fsmn_cus, &seq_b, &gi_b, &sc_b);
-        const size_t seq_al = (seq_b + 255) / 256 * 256, gi_al = (gi_b + 255) / 256 * 256;
-        wekws::GruF16Workspace ws{{base, base + seq_al}, reinterpret_cast<float*>(base + 2 * seq_al),
-                                  reinterpret_cast<float*>(base + 2 * seq_al + gi_al)};
-        rc = wekws::launch_gru_f16(m->gq, ws, x, B, T, in_cache, y, out_cache, m->fsmn_cus, stream);
-      }
+    if (route.family == wekws::GRU_PIPE) {
+      char* gran = stream_workspace(m, stream, route.granule_bytes, true, unsigned(route.slots) << 8 | unsigned(d.num_layers));
+      if (!gran) return WEKWS_HIP_ENOMEM;
+      wekws::GruPipeWorkspace ws{};
+      ws.ctl = stream_ctl(m, stream, &ws.err);
+      if (!ws.ctl) return WEKWS_HIP_ENOMEM;
+      ws.seq_in = base;
+      ws.seq_top = ws.seq_in + route.seq_bytes;
+      ws.sc = reinterpret_cast<float*>(ws.seq_top + route.seq_bytes);
+      for (int l = 0; l < d.num_layers; ++l) { ws.gi[l] = gran; gran += route.gi_bytes; }
+      for (int l = 0; l + 1 < d.num_layers; ++l) { ws.hs[l] = gran; gran += route.hs_bytes; }
+      ws.nf = route.nf_in_kernel ? m->nf_dev : nullptr;
+      rc = wekws::launch_gru_pipe(route, m->gq, ws, x, B, T, in_cache, y, out_cache, stream);
+    } else if (route.family == wekws::GRU_F16) {
+      wekws::GruF16Workspace ws{{base, base + route.seq_bytes}, reinterpret_cast<float*>(base + 2 * route.seq_bytes),
+                                reinterpret_cast<float*>(base + 2 * route.seq_bytes + route.gi_bytes)};
+      rc = wekws::launch_gru_f16(route, m->gq, ws, x, B, T, in_cache, y, out_cache, stream);
     } else {
-      rc = wekws::launch_gru(m->gp, x, B, T, in_cache, y, out_cache, stream);
+      rc = wekws::launch_gru(route, m->gp, x, B, T, in_cache, y, out_cache, stream);
     }
+    // (a launcher that refuses what the route chose: the two have drifted apart -- an internal error)
+    if (rc == -4) return fail(WEKWS_HIP_EUNSUPPORTED, "internal: %s has no kernel for the route", wekws::gru_family_name(route.family));
     if (rc) return fail(rc, "gru launch failed: %s", hipGetErrorString(hipGetLastError()));
     // streams with a NaN / Inf feature or state (their loads entered the kernels above as 0): the reference's arithmetic
-    if (!gru_nf_in_kernel) {                                 // (the layer-major and exact-f32 kernels: their own launch behind them)
+    if (!route.nf_in_kernel) {                               // (the layer-major and exact-f32 kernels: their own launch behind them)
       hipLaunchKernelGGL(wekws::gru_nf_fix_kernel, dim3(B), dim3(256), 0, stream, m->nf_dev, x, B, T, in_cache, out_cache, y);
       if (hipGetLastError() != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "gru non-finite pass: launch failed");
     }
@@ -1832,15 +1769,9 @@ int wekws_hip_forward(wekws_hip_model* m, const float* x, int B, int T, const fl
       a.T_total = T;
       a.first_tile = (i == 0);
       a.last_tile = (i == ntiles - 1);
-      a.head_slices = 0;
       a.nf = m->nf_dev;
-      if (m->mm_ok && d.odim >= 256 && B * 2 <= m->fsmn_cus) {       // CTC head, a handful of streams (ds256_mm.hip.h)
-        const int sl = m->fsmn_cus / B;
-        a.head_slices = m->fsmn_slices >= 0 ? m->fsmn_slices : (sl > 8 ? 8 : sl);
-      }
       int rc;
       // ---- which kernel: one pure function of (shape flags, options, call) -- route.h; tests/test_route.py sweeps it on the CPU
-      const wekws::RouteOptions ro = route_options(m);
       wekws::RouteCall rcall{};
       rcall.B = B; rcall.T = Tt; rcall.ntiles = ntiles;
       rcall.has_in = a.in_cache != nullptr; rcall.has_out = a.out_cache != nullptr;
@@ -1849,15 +1780,11 @@ int wekws_hip_forward(wekws_hip_model* m, const float* x, int B, int T, const fl
       rcall.cache16 = (reinterpret_cast<uintptr_t>(in_cache) | reinterpret_cast<uintptr_t>(out_cache)) % 16 == 0;
       rcall.cus = m->fsmn_cus;
       if (ntiles == 1) { rcall.has_in = in_cache != nullptr; rcall.has_out = out_cache != nullptr; }
-      const wekws::Route route = wekws::select_conv_route(d, m->rf, ro, rcall, int(wekws::ds256_stream_lds_bytes(m->cache_len)),
-                                                          int(wekws::mdtc64_stream_lds_bytes(m->cache_len)));
+      const wekws::Route route = wekws::select_conv_route(d, m->rf, m->ro, rcall);
       if (route.family == wekws::ROUTE_NONE) return fail(WEKWS_HIP_EUNSUPPORTED, "no kernel for this call: %s", route.why_not ? route.why_not : "?");
       g_last_route = route;
-#ifdef WEKWS_TEST_HOOKS
-      g_route_trace.path = kTraceConv;
-      if (g_route_trace.ntiles < kTraceMaxTiles) g_route_trace.tile[g_route_trace.ntiles] = route;
-      ++g_route_trace.ntiles;
-#endif
+      trace(kTraceConv, route);
+      a.head_slices = route.head_slices;
       const wekws::StackParams& sp = m->sp;
       switch (route.family) {
         case wekws::ROUTE_DS256_STREAM: rc = wekws::launch_ds256_stream(route, sp, a, stream); break;
