@@ -168,6 +168,19 @@ def random_config_spec(cfg):
 #   * GPU, every row (tests/test_hip_route_matrix.py): at most 4.0e-6 (ds256_mm, the CTC heads), 9.7e-7 on every other family;
 #     every one-fp16-product control at least 12x the bar.
 # 2^-15 (3.05e-5): 7.6x the largest measured kernel error, 4.8x the float32 oracle's, 9.6x below the fp16 emulations.
+# GRU and FSMN (tests/route_matrix_rnn.py: 55 GRU + 29 FSMN rows over every route tuple of select_gru_route / select_fsmn_route;
+# every chunk's output compared on its own, the GRU's state after every chunk, the FSMN's final cache; four named CTC-head rows
+# that carry a stream over short calls take each class's scale over the whole stream -- the reason stands beside them):
+#   * CPU, every row at <= 4 utterances (tests/test_route.py::test_tight_bar_holds_f32_and_rejects_one_rounded_matrix): the
+#     float32 oracle and ATen float32 reach 5.4e-6 on the GRU rows (ATen, the 5-layer any-shape row; 4.1e-6 on the kernels'
+#     rows) and the float32 oracle 5.4e-6 on the FSMN rows (the first call of a CTC-head stream; 3.5e-6 otherwise); the least
+#     visible SINGLE weight matrix rounded to fp16 misses the bar by 2.48x (GRU: the classifier, here of the hidden-160 model)
+#     and 2.42x (FSMN: a layer's affine transform), most matrices by 3 .. 30x;
+#   * GPU (tests/test_hip_route_gru_fsmn.py), at the full batch, measured on the 59 single-chunk rows (a multi-chunk row's
+#     figures are in the error report of a GPU run, route_matrix/gru/... and route_matrix/fsmn/...): GRU at most 3.9e-6 (a
+#     state channel of a two-stream row), FSMN at most 2.4e-6 (the 2599-class head); the rounded-matrix control misses the bar
+#     on each of their 40 control rows, by 1.78x at least for the GRU (a full batch raises the channels' scales above those
+#     of the 4-utterance CPU case) and 2.41x for FSMN.
 TIGHT_K = 2.0 ** -15
 F16_TOL = 5e-4
 CHANNEL_FLOOR = 2.0 ** -10

@@ -392,3 +392,137 @@ def test_effective_precision_agrees_with_the_routes(hooks, seed):
         assert r0["eff"] == ("f16" if split0 else "f16x3"), (cfg, opts)
         assert route(hooks, cfg, 1, 1, precision="f32")["eff"] == "f32"
         assert route(hooks, cfg, 1, 1, precision="default")["eff"] == "f16x3"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the GRU / FSMN route matrix (tests/route_matrix_rnn.py)
+from tests import route_matrix_rnn as rr  # noqa: E402
+
+RNN_IDS = [r["id"] for r in rr.ROWS]
+
+
+@pytest.mark.parametrize("row", rr.ROWS, ids=RNN_IDS)
+def test_gru_fsmn_matrix_predictions_are_route_h(hooks, row):
+    """The literal record of every chunk (FSMN: of every tile) is what route.h chooses for the call the forward makes."""
+    assert rr.predict(hooks, row) == rr.EXPECT[row["id"]]
+
+
+def _gru_reachable(lib):
+    """Every (family, nn, spw, chunked, nchunks > 1, pk, k2, nf_in_kernel, tiles > slots) select_gru_route reaches over 1 .. 4
+    layers, the stream counts at the edges of its choices, short and long inputs, both precisions, the three values of option
+    gru_pipe, aligned and unaligned features and the four feature widths."""
+    import itertools
+    seen = {}
+    for layers in (1, 2, 3, 4):
+        smax = min(rm.CUS // (2 * layers), 128)                   # gru_pipe_geom: the wavefront's resident slots
+        Bs = {1, 2, 3, 15, 16, 17, 4096, 4097, 16383, 16384}
+        for k in (1, 2, 4, 8, 16, 8 * 16):                        # slots x streams per tile; 8 rounds of full tiles
+            Bs |= {smax * k - 1, smax * k, smax * k + 1}
+        for k in (1, 2, 4, 8, 16):                                # gru_f16_spw: 128 packed workgroups
+            Bs |= {128 * k - 1, 128 * k, 128 * k + 1}
+        for idim in (40, 64, 80, 23):
+            cfg = _gru_cfg(layers)
+            cfg["input_dim"] = idim
+            for B, T, p, gp, x16 in itertools.product(sorted(Bs), (1, 8, 16, 17, 31, 32, 98), ("default", "f32"), (0, 1, 2), (0, 1)):
+                r = rm.gru_route(lib, cfg, B, T, precision=p, x16=x16, opts={"gru_pipe": gp})
+                assert r["plan"] == "as_is" and r["family"] != "none", r
+                seen.setdefault(rr.gru_tuple(rm.gru_record(r)), (layers, idim, B, T, p, gp, x16))
+    return seen
+
+
+def _fsmn_reachable(lib):
+    """Every (max_nt, nt, u, head_slices > 1, tile index > 0, ntiles > 1) select_fsmn_route reaches over the configurations and the
+    B / T grid of test_fsmn_route_invariants."""
+    cfgs = [M[n] for n in M if M[n]["backbone"]["type"] == "fsmn"]
+    for base in list(cfgs):
+        for lo in (20, 40):
+            cfg = copy.deepcopy(base)
+            cfg["backbone"]["left_order"] = lo
+            cfgs.append(cfg)
+    seen = {}
+    for cfg in cfgs:
+        for B in (1, 2, 255, 256, 513, 1024, 4096):
+            for T in (1, 16, 17, 32, 33, 64, 65, 130):
+                first = rm.fsmn_route(lib, cfg, B, T)
+                if first["plan"] == "generic":
+                    continue
+                for i in range(first["ntiles"]):
+                    r = rm.fsmn_route(lib, cfg, B, T, tile=i)
+                    seen.setdefault(rr.fsmn_tuple(rm.fsmn_record(r), i), (cfg["output_dim"], cfg["backbone"]["left_order"], B, T, i))
+    return seen
+
+
+def test_gru_fsmn_matrix_covers_every_reachable_route(hooks):
+    """A route.h change that adds a GRU or FSMN variant fails here until a row runs it on the GPU -- and every route tuple has a row
+    that compares per-frame logits (activation identity) of a head of at least 12 classes, and a control row."""
+    for kind, reach, least in (("gru", _gru_reachable(hooks), 31), ("fsmn", _fsmn_reachable(hooks), 19)):
+        rows = [r for r in rr.ROWS if r["kind"] == kind]
+        have = set().union(*(rr.row_tuples(r) for r in rows))
+        missing = {t: reach[t] for t in reach if t not in have}
+        assert not missing, missing
+        assert len(reach) >= least, (kind, len(reach))                  # (the sweep cannot shrink silently)
+        logits = set().union(*(rr.row_tuples(r) for r in rows if rr.is_identity(r) and rr.row_config(r)["output_dim"] >= 12))
+        assert have == logits, have - logits
+        control = set().union(*(rr.row_tuples(r) for r in rr.control_rows() if r["kind"] == kind))
+        assert have == control, have - control
+        assert {rr.EXPECT[r["id"]][0] for r in rows} == ({"as_is", "padded", "generic"} if kind == "gru" else {"as_is", "generic"})
+
+
+def test_gru_fsmn_matrix_rows_cover_the_edges():
+    G, F = rr.GRU_ROWS, rr.FSMN_ROWS
+    rec = [(r, dict(zip(rm.GRU_REC, c))) for r in G for c in rr.EXPECT[r["id"]][1] if c]
+    fam = lambda f: [(r, d) for r, d in rec if d["family"] == f]                      # noqa: E731
+    assert {d["nn"] for _, d in fam("gru_f32")} == {1, 4} and {d["nn"] for _, d in fam("gru_f16")} == {1, 2}
+    assert {d["spw"] for r, d in fam("gru_f16") if max(r["chunks"]) <= 16 and d["nn"] == 1} == {1, 2, 4, 8, 16}
+    assert any(d["tchunk"] and sum(r["chunks"]) % d["tchunk"] for r, d in fam("gru_f16"))          # the last time chunk is shorter
+    assert any(not d["tchunk"] and max(r["chunks"]) >= 32 for r, d in fam("gru_f16"))
+    assert {d["spw"] for _, d in fam("gru_pipe")} == {1, 2, 4, 8, 16}
+    assert {(d["bits"] & 1, d["bits"] >> 1 & 1, d["bits"] >> 2 & 1) for _, d in fam("gru_pipe")} == {(a, b, c) for a in (0, 1) for b in (0, 1) for c in (0, 1)}
+    assert any(d["tiles"] > 8 * d["slots"] and r["opts"].get("gru_pipe") == 2 for r, d in fam("gru_pipe"))
+    assert any(d["slots"] < d["tiles"] <= 8 * d["slots"] for _, d in fam("gru_pipe"))
+    k2_0 = {(rr.row_config(r)["input_dim"], r["x_off"]) for r, d in fam("gru_pipe") if not d["bits"] >> 1 & 1}
+    assert {(80, 0), (23, 0), (40, 1)} <= k2_0
+    assert {40, 64} <= {rr.row_config(r)["input_dim"] for r, d in fam("gru_pipe") if d["bits"] >> 1 & 1}
+    assert {rr.row_config(r)["backbone"]["num_layers"] for r in G} == {1, 2, 3, 4, 5}
+    assert {rr.row_config(r)["hidden_dim"] for r in G} == {64, 128, 160}
+    assert any(rr.EXPECT[r["id"]][0] == "padded" and r["state"] for r in G)
+    odims = {rr.row_config(r)["output_dim"] for r in G}
+    assert {1, 2, 17} <= odims and max(odims) > 128
+    assert {1, 2, 3, 15, 16, 17, 33} <= {t for r in G for t in r["chunks"]} and any(t > 2 * 16 + 16 for r in G for t in r["chunks"])
+    assert any(r["B"] == 1 for r in G) and any(r["B"] % 16 for r in G) and any(d["slots"] and r["B"] % d["slots"] == 1 for r, d in rec)
+    assert any(r["chunks"] == [10, 10, 10] for r in G) and {0.5, 3.0, None} == {r["state"] for r in G}
+    frec = [(r, dict(zip(rm.FSMN_REC, t)), i) for r in F for ch in rr.EXPECT[r["id"]][1] for i, t in enumerate(ch)]
+    assert {d["nt"] for _, d, _ in frec} == {1, 2, 3, 4} and {d["u"] for _, d, _ in frec} == {1, 2, 4}
+    assert any(d["u"] > 1 and sum(r["chunks"][:1]) % 16 for r, d, _ in frec)
+    assert {1, 3, 8} <= {d["head_slices"] for _, d, _ in frec} and any("head_slices" in r["opts"] for r in F)
+    assert {2, 3} <= {d["ntiles"] for _, d, _ in frec} and any(i and i == d["ntiles"] - 1 and 16 * d["nt"] < d["tile_frames"] for _, d, i in frec)
+    assert {2, 3, 4} <= {d["tile_frames"] // 16 for _, d, _ in frec}
+    assert any(r["state"] for r in F) and any(r["state"] is None for r in F) and any(len(r["chunks"]) > 1 for r in F)
+    assert any(r["x_off"] for r in F) and any(r["c_off"] and r["state"] for r in F)
+    assert any(rr.row_config(r)["backbone"]["linear_dim"] % 32 for r in F)                      # padded widths
+    generic = [r for r in F if rr.EXPECT[r["id"]][0] == "generic"]
+    assert any(r["precision"] == "f32" for r in generic) and any(rr.row_config(r)["backbone"]["left_order"] > 32 for r in generic)
+
+
+@pytest.mark.parametrize("row", rr.ROWS, ids=RNN_IDS)
+def test_tight_bar_holds_f32_and_rejects_one_rounded_matrix(row):
+    """TIGHT_K on every GRU / FSMN row (at most 4 utterances: the bar is per element), from both sides.  (a) The float32 numpy
+    oracle, and ATen float32 where oracle/torch_ref.py has the model, are within TIGHT_K / 4 of the float64 oracle.  (b) The
+    float32 oracle with ONE weight matrix rounded to fp16 -- an F16X3 product that dropped its lo(w) * x term in one place: every
+    matrix the kernels multiply on the matrix cores, one at a time -- misses the bar by a factor of at least 2, in the outputs or in
+    the returned state.  (The factor is 2 and not the conv calibration's 4: one matrix is a much smaller defect than the
+    whole-network emulations used there.  The classifier of a sigmoid row is left out: rr.defect_visibility.)"""
+    cfg, sd, x, s0 = rr.calibration_case(row)
+    rys, rcs = rr.reference(cfg, sd, x, s0, row["chunks"], np.float64)
+    ys, cs = rr.reference(cfg, sd, x, s0, row["chunks"], np.float32)
+    e32 = rr.row_error(row, cfg, ys, cs, rys, rcs)
+    assert e32 <= TIGHT_K / 4, e32
+    aten = rr.aten_reference(cfg, sd, x, s0, row["chunks"])
+    assert (aten is not None) == (row["kind"] == "gru")
+    if aten is not None:
+        et = rr.row_error(row, cfg, aten[0], aten[1], rys, rcs)
+        assert et <= TIGHT_K / 4, et
+    vis = rr.defect_visibility(row, (cfg, sd, x, s0), (rys, rcs))
+    assert len(vis) == len(rr.matrices(cfg, sd)) - (row["kind"] == "gru" and not rr.is_identity(row))
+    weak = {k: v / TIGHT_K for k, v in vis.items() if v < 2 * TIGHT_K}
+    assert not weak, weak
