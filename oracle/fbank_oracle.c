@@ -77,6 +77,44 @@ static void fft_forward(const int* rev, const float* tbl, float* re, float* im, 
   }
 }
 
+/* fbank.h:51-88: triangular weights in the mel domain, float32 arithmetic and libm's logf like the reference.
+ * melw: (num_bins, N / 2), zero-initialised by the caller; first / count may be NULL. */
+static void mel_bank(int num_bins, int sample_rate, int N, float* melw, int* first, int* count) {
+  const int NB = N / 2;
+  const float bin_width = (float)sample_rate / N;
+  const float lo = mel_scale(20.0f), hi = mel_scale((float)(sample_rate / 2));
+  const float delta = (hi - lo) / (num_bins + 1);
+  for (int b = 0; b < num_bins; ++b) {
+    const float left = lo + b * delta, center = lo + (b + 1) * delta, right = lo + (b + 2) * delta;
+    int fi = -1, li = -1;
+    for (int i = 0; i < NB; ++i) {
+      const float m = mel_scale(bin_width * i);
+      if (m > left && m < right) {
+        melw[(size_t)b * NB + i] = (m <= center) ? (m - left) / (center - left) : (right - m) / (right - center);
+        if (fi < 0) fi = i;
+        li = i;
+      }
+    }
+    if (first) first[b] = fi < 0 ? 0 : fi;
+    if (count) count[b] = fi < 0 ? 0 : li + 1 - fi;
+  }
+}
+
+/* The bank alone, for the float64 evaluation of the pipeline (oracle/fbank_oracle.py::fbank_f64): the weights are ill-conditioned
+ * in the mel values (one ulp of logf moves a weight by tens of float32 eps), so the arbiter takes the very bank the float32
+ * pipeline uses instead of rebuilding it with another logarithm.  melw: (num_bins, N / 2), overwritten.  Returns the number of
+ * filters that cover no FFT bin. */
+int wekws_oracle_mel_bank(int num_bins, int sample_rate, int frame_length, float* melw) {
+  const int N = next_pow2(frame_length), NB = N / 2;
+  int* count = (int*)malloc(sizeof(int) * num_bins);
+  int empty = 0;
+  memset(melw, 0, sizeof(float) * (size_t)num_bins * NB);
+  mel_bank(num_bins, sample_rate, N, melw, NULL, count);
+  for (int b = 0; b < num_bins; ++b) empty += count[b] == 0;
+  free(count);
+  return empty;
+}
+
 /* out: (num_frames, num_bins) row-major; returns num_frames (0 if the signal is shorter than one frame).
  * window: 0 = Hamming (the runtime), 1 = Povey (torchaudio/Kaldi default; parity unpinned). */
 int wekws_oracle_fbank(const float* wave, int nsamp, int num_bins, int sample_rate, int frame_length, int frame_shift,
@@ -103,25 +141,7 @@ int wekws_oracle_fbank(const float* wave, int nsamp, int num_bins, int sample_ra
       win[i] = (float)w;
     }
   }
-  {                                                                      /* fbank.h:51-88 */
-    const float bin_width = (float)sample_rate / N;
-    const float lo = mel_scale(20.0f), hi = mel_scale((float)(sample_rate / 2));
-    const float delta = (hi - lo) / (num_bins + 1);
-    for (int b = 0; b < num_bins; ++b) {
-      const float left = lo + b * delta, center = lo + (b + 1) * delta, right = lo + (b + 2) * delta;
-      int fi = -1, li = -1;
-      for (int i = 0; i < NB; ++i) {
-        const float m = mel_scale(bin_width * i);
-        if (m > left && m < right) {
-          melw[(size_t)b * NB + i] = (m <= center) ? (m - left) / (center - left) : (right - m) / (right - center);
-          if (fi < 0) fi = i;
-          li = i;
-        }
-      }
-      first[b] = fi < 0 ? 0 : fi;
-      count[b] = fi < 0 ? 0 : li + 1 - fi;
-    }
-  }
+  mel_bank(num_bins, sample_rate, N, melw, first, count);
   for (int f = 0; f < nframes; ++f) {
     const float* src = wave + (size_t)f * frame_shift;
     float mean = 0.0f;

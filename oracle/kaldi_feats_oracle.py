@@ -88,13 +88,37 @@ def lifter_coeffs(num_ceps, cepstral_lifter=22.0):
     return 1.0 + 0.5 * cepstral_lifter * np.sin(np.pi * np.arange(num_ceps) / cepstral_lifter)
 
 
-def dct_lifter(logmel, num_ceps, cepstral_lifter=22.0):
-    """The MFCC tail on given log-mel rows: (rows, num_mel_bins) -> (rows, num_ceps)."""
+def dct_lifter(logmel, num_ceps, cepstral_lifter=22.0, dtype=np.float32):
+    """The MFCC tail on given log-mel rows: (rows, num_mel_bins) -> (rows, num_ceps).  Float64 inside; dtype=np.float64 keeps
+    the result unrounded (the arbiter of the DCT / lifter kernel's tight bar)."""
     logmel = np.asarray(logmel, np.float64)
     out = logmel @ dct_matrix(num_ceps, logmel.shape[-1])
     if cepstral_lifter != 0.0:
         out = out * lifter_coeffs(num_ceps, cepstral_lifter)
-    return out.astype(np.float32)
+    return out.astype(dtype)
+
+
+def dct_lifter_scale(logmel, num_ceps, cepstral_lifter=22.0):
+    """The error unit of dct_lifter per element: eps |lifter_k| sum_j |M[j, k] x_j| -- one float32 rounding of each product (the
+    lifter 1 + 11 sin(pi k / 22) is negative for k = 23 .. 43)."""
+    m = np.abs(dct_matrix(num_ceps, np.shape(logmel)[-1]))
+    s = np.abs(np.asarray(logmel, np.float64)) @ m
+    if cepstral_lifter != 0.0:
+        s = s * np.abs(lifter_coeffs(num_ceps, cepstral_lifter))
+    return EPS * s
+
+
+def dct_lifter_f32(logmel, num_ceps, cepstral_lifter=22.0, entry=None):
+    """A float32 evaluation (the matrix with the lifter folded in rounded to float32, float32 products summed in float32):
+    calibrates the bar of the kernel.  entry=(j, k, factor): matrix entry [j, k] times `factor` (the negative control)."""
+    x = np.asarray(logmel, np.float32)
+    m = dct_matrix(num_ceps, x.shape[-1])
+    if cepstral_lifter != 0.0:
+        m = m * lifter_coeffs(num_ceps, cepstral_lifter)
+    m = m.astype(np.float32)
+    if entry is not None:
+        m[entry[0], entry[1]] *= np.float32(entry[2])
+    return (x @ m).astype(np.float32)
 
 
 def mfcc(wave, num_ceps=80, num_mel_bins=80, sample_rate=16000, frame_length_ms=25.0, frame_shift_ms=10.0):

@@ -48,8 +48,8 @@ def test_short_input_yields_no_frames():
 
 @pytest.mark.parametrize("case", FBANK_CASES, ids=[c["name"] for c in FBANK_CASES])
 def test_float64_evaluation_is_the_same_pipeline(case, fgolden):
-    """fbank_f64 (the arbiter of the GPU fuzz test: is a difference the reference's own rounding noise?) is the pipeline of the
-    goldens: within the reference's documented float32 FFT noise of them (2.4e-5 at 40 bins, 1.7e-4 at 80: tests/test_hip_fbank.py),
+    """fbank_f64 (the arbiter of the GPU tests: tests/test_hip_fbank_f64.py and the fuzz test of tests/test_hip_fbank.py hold every
+    bin of the kernel to it, in fbank_units at tests/helpers.py::K_FBANK) is the pipeline of the goldens: within the reference's documented float32 FFT noise of them (2.4e-5 at 40 bins, 1.7e-4 at 80: tests/test_hip_fbank.py),
     and identical in shape and in the floor (log FLT_EPSILON) for silence."""
     pcm = fbank_input(case)
     sr = case["sample_rate"]

@@ -12,6 +12,7 @@ import torch
 
 from oracle import fbank_oracle
 from tests.golden.fbank_cases import FBANK_CASES, fbank_input
+from tests.helpers import K_FBANK
 from wekws_amd.frontend import Fbank
 from wekws_amd.utils import synth
 
@@ -184,12 +185,14 @@ def framing_bound(ref, tol):
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 558, 917, 2175, 2208, 2221, 2235])
-def test_random_framings_against_the_c_oracle(seed):
+def test_random_framings_against_the_c_oracle(seed, error_report):
     """Seeded fuzz of the extractor's configuration space (fbank.h:33-97 takes any bin count / frame length; feature_pipeline.cc
     any sample count): random sample rates, frame lengths 65 .. 512, shifts, bin counts, windows, batch sizes and lengths around
     the framing boundaries, float and int16 input, against the plain-C oracle (bit-exact against the compiled reference front-end,
     tests/test_fbank_oracle.py), every bin within framing_bound.  Seeds >= 558: the configurations of a 2,300-seed run that come
-    closest to the bound (pure tones through short FFTs; 558 and 917 are the worst at <= 40 / > 40 bins)."""
+    closest to the bound (pure tones through short FFTs; 558 and 917 are the worst at <= 40 / > 40 bins).
+    Every bin is also held to the float64 evaluation fbank_f64 in fbank_units at K_FBANK."""
+    worst = 0.0
     for what, pcm in framing_cases(seed):
         _, trial, sr, flen, shift, bins, window, B, nsamp, kind = what
         if fbank_oracle.has_empty_filter(bins, sr, flen):   # the reference's constructor CHECK-fails (fbank.h:81): refused, not wrong
@@ -206,6 +209,11 @@ def test_random_framings_against_the_c_oracle(seed):
             if ref.size:
                 over = np.abs(got[i] - ref) - framing_bound(ref, tol)
                 assert float(over.max()) <= 0.0, (what, i, float(over.max()), float(np.abs(got[i] - ref).max()))
+                # ... and every bin against the float64 evaluation at the tight bar (tests/helpers.py::K_FBANK)
+                u = fbank_oracle.fbank_units(got[i], pcm[i], bins, sr, flen, shift, 0 if window == "hamming" else 1)
+                worst = max(worst, float(u.max()))
+                assert float(u.max()) <= K_FBANK, (what, i, float(u.max()), np.unravel_index(int(u.argmax()), u.shape))
         if nsamp:
             i16 = torch.from_numpy(np.ascontiguousarray(pcm).astype(np.int16)).cuda()
             assert torch.equal(fb(i16), fb(i16.float())), what
+    error_report[f"fbank_f64/fuzz_seed{seed}"] = worst

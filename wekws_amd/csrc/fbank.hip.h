@@ -20,7 +20,7 @@
 //      gets two or more); a lane owns a slot for the whole launch with its 16 weights in registers, so a frame costs it
 //      16 LDS reads + 16 FMAs, ascending in k like the reference; slot sums are combined per filter in slot order (the
 //      only departure from the reference's single ascending loop: one float reassociation per extra slot), floored
-//      at FLT_EPSILON, logf, stored as (T, num_bins) rows.  (LDS float atomics were tried for this step and cost 4x
+//      at FLT_EPSILON, the logarithm (fb_logf below, not the device library's logf), stored as (T, num_bins) rows.  (LDS float atomics were tried for this step and cost 4x
 //      the whole rest of the kernel: tens of lanes serialise on one accumulator.)
 // PMC of the previous gather version (one lane per mel bin walking its taps, tables re-read from LDS every frame):
 // vector ALU 59 % and LDS 74 % busy, 46 % of the LDS time in bank conflicts.
@@ -59,6 +59,13 @@ struct FbankParams {
   int32_t table_floats;
 };
 
+// The reference transforms UpperPowerOfTwo(frame_length) points (fbank.h:43,117-119), 128 at the least here (frames of 65 samples up).
+inline int fbank_ref_points(int frame_length) {
+  int Nref = 64;
+  while (Nref < frame_length) Nref *= 2;
+  return Nref;
+}
+
 // Host: tables for the kernel.  Mel bank follows fbank.h:51-88 in float32 like the reference; the
 // window follows fbank.h:90-96 (double, stored as float); twiddles are exact-rounded from double.
 // Returns -1, or the index of the first mel filter that covers no FFT bin (too many bins for this sample rate / frame length:
@@ -90,8 +97,7 @@ inline int fbank_build_tables(int num_bins, int sample_rate, int frame_length, i
   // transform on the zero-padded frame: bin k of an Nref-point DFT of a frame of <= Nref samples IS bin k * 512 / Nref of
   // its 512-point DFT, so shorter frames (8 kHz audio: 200 samples, 256 points) only change WHERE the mel bank looks -- the
   // filters are computed over the reference's Nref / 2 bins and laid out over every stride-th bin of the 512-point spectrum.
-  int Nref = 64;
-  while (Nref < frame_length) Nref *= 2;
+  const int Nref = fbank_ref_points(frame_length);
   const int stride = N / Nref;
   auto mel = [](float f) { return 1127.0f * logf(1.0f + f / 700.0f); };
   const float bin_width = float(sample_rate) / Nref;
@@ -287,6 +293,21 @@ __device__ __forceinline__ void fb_untangle2(fb_f2 zka, fb_f2 zna, fb_f2 ua, fb_
 #undef FB_SUB
 #undef FB_CMUL1
 #undef FB_CMUL2
+// Natural logarithm of a positive normal float with one rounding at the result's own magnitude.  The device library's logf is
+// v_log_f32 times ln 2: measured up to 2.3 ulp of the result over [e^-16, e^27] -- on a log-mel of 16 .. 26 that is up to 35 float32
+// eps of the mel energy, seven times what the whole transform in front of it loses (tests/test_hip_fbank_f64.py held the kernel to
+// the float64 evaluation and found this stage).  Here the exponent is split off: e = m 2^k with m in [sqrt(1/2), sqrt(2)), so
+// log m = v_log_f32(m) ln 2 is at most 0.35 in magnitude (absolute error < 1e-7: under one eps of the energy) and
+// k ln 2 is added as hi + lo with fused multiply-adds: log e = fma(k, ln2_hi, fma(k, ln2_lo, log m)) -- half an ulp of the result.
+__device__ __forceinline__ float fb_logf(float e) {
+  const float m0 = __builtin_amdgcn_frexp_mantf(e);          // [0.5, 1)
+  const bool low = m0 < 0.70710678f;
+  const float m = low ? 2.f * m0 : m0;
+  const float k = float(__builtin_amdgcn_frexp_expf(e) - int(low));
+  const float lm = __builtin_amdgcn_logf(m) * 0.693147182f;    // (v_log_f32 is log2; m is normal: no denormal scaling needed)
+  return fmaf(k, 0.693147182f, fmaf(k, -1.90465421e-9f, lm));  // ln 2 = 0.693147182464599609375 - 1.90465421e-9 ...
+}
+
 #ifndef WEKWS_FBANK_FW
 #define WEKWS_FBANK_FW 1
 #endif
@@ -302,6 +323,18 @@ constexpr int kFbankFW = WEKWS_FBANK_FW;   // frames per wave, interleaved throu
 // per frame halve, and the window / twiddle / mel-weight registers serve both frames.  Same arithmetic per frame, bit for bit.
 // (two slot rounds -- 80 mel bins: 140 registers = three waves per SIMD; capped at 128 = four, 24 bytes of scratch: 548 -> 528 us per
 //  8192 x 1 s, round 6.  Three rounds would spill 136 bytes: left alone.)
+// even sample count, frame length and shift, a buffer aligned to a sample PAIR: every element of every frame is one aligned pair inside
+// or outside the frame (the kernel's branch-free loads); anything else takes the per-sample path.  One function for the kernel and for
+// the test build's launch record.
+template <typename S>
+__host__ __device__ inline bool fbank_pair_ok(int nsamp, int frame_shift, int frame_length, const S* pcm) {
+  return (nsamp % 2 == 0) && (frame_shift % 2 == 0) && (frame_length % 2 == 0) && (reinterpret_cast<uintptr_t>(pcm) % (2 * sizeof(S)) == 0);
+}
+
+// ROUNDS == 3 (129 .. 192 slots) has not been found REACHABLE through wekws_hip_fbank_create: over 16 sample rates from 2 to 96 kHz
+// (the usual audio rates, not every integer rate), every bin count 1 .. 128 and the three transform lengths that frames of 65 .. 512
+// samples select, no bank without an empty filter has more than 128 slots (tests/test_fbank_matrix.py sweeps fbank_build_tables and
+// asserts it for those rates).  The instantiations stay for a rate outside that sample; no test runs them.
 template <int ROUNDS, typename S>
 __global__ __launch_bounds__(64 * kFbankWaves, ROUNDS == 2 ? 4 : 1) void fbank_kernel(const FbankParams P, const S* __restrict__ pcm,
                                                                  int B, int nsamp, int nframes,
@@ -395,7 +428,7 @@ __global__ __launch_bounds__(64 * kFbankWaves, ROUNDS == 2 ? 4 : 1) void fbank_k
   float2 vn[FW][4];
   // even frame length and shift, aligned buffer: every element is one aligned pair inside or outside the frame -- loads under a lane
   // mask, no branches (round 6: the general form below compiled to 25 branches per frame)
-  const bool pair_ok = (nsamp % 2 == 0) && (P.frame_shift % 2 == 0) && (FL % 2 == 0) && (reinterpret_cast<uintptr_t>(pcm) % (2 * sizeof(S)) == 0);
+  const bool pair_ok = fbank_pair_ok(nsamp, P.frame_shift, FL, pcm);
   auto fetch = [&](int b0, int fr0) __attribute__((always_inline)) {
 #pragma unroll
     for (int w = 0; w < FW; ++w) {
@@ -555,7 +588,7 @@ __global__ __launch_bounds__(64 * kFbankWaves, ROUNDS == 2 ? 4 : 1) void fbank_k
 #ifdef WEKWS_FBANK_FASTLOG
             feats[g * P.num_bins + sbin[r]] = __logf(fmaxf(e, FLT_EPSILON));
 #else
-            feats[g * P.num_bins + sbin[r]] = logf(fmaxf(e, FLT_EPSILON));
+            feats[g * P.num_bins + sbin[r]] = fb_logf(fmaxf(e, FLT_EPSILON));
 #endif
           }
         }
@@ -582,6 +615,20 @@ inline int fbank_resident_groups(const FbankParams& P) {
   return 256 * 4;
 }
 
+// workgroups of a launch over `total` frames: one per kFbankWaves * kFbankFW frames, capped at one resident round
+inline int64_t fbank_grid(int64_t total, int resident) {
+  const int64_t grid = (total + kFbankWaves * kFbankFW - 1) / (kFbankWaves * kFbankFW);
+  return resident > 0 && grid > resident ? resident : grid;
+}
+
+#ifdef WEKWS_TEST_HOOKS
+// test build only: what the last launch of this thread was given and chose -- rounds, sample size, pair_ok, grid, resident, B, nsamp, nframes
+inline int* fbank_last_launch() {
+  static thread_local int rec[8];
+  return rec;
+}
+#endif
+
 template <typename S>
 inline int launch_fbank(const FbankParams& P, const S* pcm, int B, int nsamp, int nframes, float* feats, int resident,
                         hipStream_t stream) {
@@ -589,9 +636,14 @@ inline int launch_fbank(const FbankParams& P, const S* pcm, int B, int nsamp, in
   if (rounds < 1 || rounds > 3) return -4;
   const size_t lds = size_t(kFbankWaves * kFbankFW * kFbankStrip) * sizeof(float);
   const int64_t total = int64_t(B) * nframes;
-  int64_t grid = (total + kFbankWaves * kFbankFW - 1) / (kFbankWaves * kFbankFW);
+  const int64_t grid = fbank_grid(total, resident);
   auto kern = rounds == 1 ? fbank_kernel<1, S> : rounds == 2 ? fbank_kernel<2, S> : fbank_kernel<3, S>;
-  if (resident > 0 && grid > resident) grid = resident;
+#ifdef WEKWS_TEST_HOOKS
+  {
+    const int v[8] = {rounds, int(sizeof(S)), int(fbank_pair_ok(nsamp, P.frame_shift, P.frame_length, pcm)), int(grid), resident, B, nsamp, nframes};
+    for (int i = 0; i < 8; ++i) fbank_last_launch()[i] = v[i];
+  }
+#endif
   hipLaunchKernelGGL(kern, dim3(unsigned(grid)), dim3(64 * kFbankWaves), lds, stream, P, pcm, B, nsamp, nframes, feats);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }

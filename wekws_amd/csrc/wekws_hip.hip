@@ -1827,6 +1827,51 @@ int wekws_hip_forward(wekws_hip_model* m, const float* x, int B, int T, const fl
 }
 
 // --------------------------------------------- fbank ---------------------------------------------
+#ifdef WEKWS_TEST_HOOKS   // libwekws_hip_hooks.so only: what the last fbank launch of this thread ran, the table plan, the device table
+// out[8]: rounds, sample size in bytes, pair_ok, grid, resident, B, nsamp, nframes as launch_fbank recorded them at this thread's last launch
+extern "C" int wekws_hip_debug_fbank_last(int* out) {
+  if (!out) return WEKWS_HIP_EINVAL;
+  for (int i = 0; i < 8; ++i) out[i] = wekws::fbank_last_launch()[i];
+  return WEKWS_HIP_OK;
+}
+// The table plan of a configuration, WITHOUT a device (fbank_build_tables alone).  out[16]: rounds (mel slots per lane), nslots, spectrum
+// stride (512 / the reference's transform length), slots of the widest filter, kFbankFW, kFbankWaves, mel_first_off, mel_size_off,
+// mel_start_off, mel_w_off, mel_w_count, slot_first_off, slot_bin_off, slot_w_off, table_floats, first empty filter (-1: none; then
+// the plan before it is not filled in and wekws_hip_fbank_create refuses the configuration).
+extern "C" int wekws_hip_debug_fbank_plan(const wekws_hip_fbank_cfg* cfg, int* out) {
+  if (!cfg || !out || cfg->num_bins <= 0 || cfg->num_bins > wekws::kFbankMaxBins || cfg->sample_rate <= 0 || cfg->frame_length <= 64 ||
+      cfg->frame_length > wekws::kFbankMaxFft || cfg->frame_shift <= 0)
+    return WEKWS_HIP_EINVAL;
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  wekws::FbankParams fp{};
+  std::vector<float> t;
+  out[15] = wekws::fbank_build_tables(cfg->num_bins, cfg->sample_rate, cfg->frame_length, cfg->frame_shift, cfg->window, &fp, &t);
+  out[2] = wekws::kFbankMaxFft / wekws::fbank_ref_points(cfg->frame_length);
+  out[4] = wekws::kFbankFW;
+  out[5] = wekws::kFbankWaves;
+  if (out[15] >= 0) return WEKWS_HIP_OK;
+  int widest = 0;
+  for (int b = 0; b < fp.num_bins; ++b) widest = std::max(widest, (int(t[size_t(fp.mel_size_off) + b]) + 15) / 16);
+  const int v[15] = {(fp.nslots + 63) / 64, fp.nslots, out[2], widest, out[4], out[5], fp.mel_first_off, fp.mel_size_off, fp.mel_start_off,
+                     fp.mel_w_off, fp.mel_w_count, fp.slot_first_off, fp.slot_bin_off, fp.slot_w_off, fp.table_floats};
+  for (int i = 0; i < 15; ++i) out[i] = v[i];
+  return WEKWS_HIP_OK;
+}
+// Read (set == 0) or overwrite (set != 0) the handle's device table: n must be its table_floats.  The kernel takes its per-lane constants
+// (twiddles, window, mel slots) from this table at every launch, so a test can run it on a perturbed table and put the table back.
+extern "C" int wekws_hip_debug_fbank_tables(wekws_hip_fbank* f, float* host_buf, int n, int set) {
+  if (!f || !host_buf || n != f->fp.table_floats) return fail(WEKWS_HIP_EINVAL, "fbank tables: n=%d, the table has %d floats", n, f ? f->fp.table_floats : 0);
+  DeviceGuard guard(f->device);
+  if (!guard.ok) return fail(WEKWS_HIP_EDEVICE, "hipSetDevice(%d)", f->device);
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess)
+    e = set ? hipMemcpy(f->d_tables, host_buf, size_t(n) * sizeof(float), hipMemcpyHostToDevice)
+            : hipMemcpy(host_buf, f->d_tables, size_t(n) * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "fbank tables: %s", hipGetErrorString(e));
+  return WEKWS_HIP_OK;
+}
+#endif
 int wekws_hip_fbank_create(const wekws_hip_fbank_cfg* cfg, int device, wekws_hip_fbank** out) {
   if (!cfg || !out) return fail(WEKWS_HIP_EINVAL, "NULL argument");
   *out = nullptr;
