@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate tests/golden/shape_golden.npz from the LIVE reference: conv backbones whose hidden_dim is none of the widths the
 kernels are built for (kws_model.py:114 takes any hidden_dim; the library runs them zero-padded to the next built width,
-wekws_hip.hip::pad_conv_channels).  Per case: one-shot forward without a cache, and the same input in two chunks with the
+weight_image.hip.h::pad_conv_shape).  Per case: one-shot forward without a cache, and the same input in two chunks with the
 carried cache (the cache the caller sees keeps the model's own channel count).
 
 Runs only in the build container (needs /root/reference); the GPU box consumes the committed .npz.

@@ -68,7 +68,7 @@ def route(lib, cfg, B, T, has_in=False, has_out=True, precision="default", x16=1
 PLANS = ["as_is", "padded", "generic"]
 PRECISIONS = ["default", "f32", "f16x3", "f16"]                 # enum wekws_hip_precision
 GRU_FAMILIES = ["none", "gru_f32", "gru_f16", "gru_pipe"]
-# the 9 ints of a GRU trace record (wekws_hip.hip: route_record), then what only the CPU entry point reports
+# the 9 ints of a GRU trace record (wekws_hip_hooks.hip.h: route_record), then what only the CPU entry point reports
 GRU_REC = ("family", "nn", "spw", "tchunk", "nchunks", "slots", "tiles", "grid", "bits")
 GRU_KEYS = ("plan", "C") + GRU_REC + ("stages", "slots_p", "lds", "chunked", "plain", "gran", "res_plain", "res_gran", "eff")
 FSMN_REC = ("tile_frames", "nt", "u", "head_slices", "grid", "lds", "ntiles", "_0", "_1")

@@ -134,7 +134,7 @@ def shape_golden():
 @pytest.mark.parametrize("case", SHAPE_CASES, ids=[c["name"] for c in SHAPE_CASES])
 def test_hidden_dims_without_a_kernel(case, precision, shape_golden, error_report):
     """hidden_dim is free in the reference (kws_model.py:114); the kernels are built for 32 / 64 / 128 / 256 channels.  Any
-    other width up to 256 runs zero-padded to the next built one (wekws_hip.hip::pad_conv_channels): exact, because a zero
+    other width up to 256 runs zero-padded to the next built one (weight_image.hip.h::pad_conv_shape): exact, because a zero
     channel stays zero through the network.  Goldens from the live reference (make_shape_golden.py): one-shot posteriors and
     cache (with the MODEL's channel count), and the same input in two chunks with the carried cache."""
     from wekws_amd.utils import synth as synth_
@@ -760,6 +760,27 @@ def test_long_input_tiling_matches_oracle():
         ry, rc = kws_oracle.forward(cfg, sd, x, None)
         assert max_abs(y, ry) <= tol_for(ry)
         assert max_abs(cache, rc) <= tol_for(rc)
+
+
+@pytest.mark.parametrize("model,hidden,B,T,chunks", [("mdtc_small_global12", 24, 3, 250, [120, 130]), ("gru_2x128", 96, 3, 40, [17, 23])],
+                         ids=["mdtc_h24_global12", "gru_2x96"])
+def test_padded_model_shares_one_workspace(model, hidden, B, T, chunks, error_report):
+    """A zero-padded model AND a multi-tile call AND a pooled head AND carried caches at once: only then do the ping-pong caches,
+    the global head's running sums and the widened copies of the caller's in / out caches share one workspace (conv: 24 channels run
+    as 32, both chunks beyond the 112-frame tile; GRU: 96 units run as 128, the layer sequences beside the widened states)."""
+    from wekws_amd import _capi, pack
+    cfg = shape_case_config(dict(model=model, hidden=hidden))
+    sd = synth.synth_state_dict(pack.model_spec(cfg), 7)
+    net = build(cfg, sd)
+    x = synth.synth_feats(B, T, cfg["input_dim"], seed=13)
+    for key, ch in (("oneshot", None), ("chunks", chunks)):
+        y, c = run(net, x, chunks=ch)
+        ry, rc = oracle64(cfg, sd, x, None, ch)
+        assert y.shape == ry.shape and c.shape == rc.shape, (y.shape, c.shape)       # the CALLER's channel count and cache length
+        assert (c.shape[-1] if cfg["backbone"]["type"] == "gru" else c.shape[1]) == hidden
+        assert max_abs(y, ry) <= tol_for(ry) and max_abs(c, rc) <= tol_for(rc), (key, max_abs(y, ry), max_abs(c, rc))
+        check_tight(error_report, f"padded_workspace/{model}_h{hidden}/{key}", cfg, y, c, ry, rc)
+    assert _capi.load().wekws_hip_workspace_bytes(net._get_handle(torch.device("cuda", torch.cuda.current_device())).ptr, B, chunks[-1]) > 0
 
 
 @pytest.mark.parametrize("name", ["ds_tcn_h256", "mdtc_h64", "gru_2x128", "fsmn_small", "tcn_h64"])

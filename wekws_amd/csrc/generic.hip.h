@@ -227,19 +227,10 @@ struct GenericModel {
   int cache_len = 0;             // conv: sum of paddings; fsmn: left_order - 1 + right_order; gru: 0
 };
 
-inline int gen_nblocks(const wekws_hip_desc& d) {
-  return d.backbone == WEKWS_HIP_BACKBONE_MDTC ? 1 + d.num_stack * d.stack_size : d.num_layers;
-}
-inline int gen_dilation(const wekws_hip_desc& d, int i) {
-  if (d.backbone == WEKWS_HIP_BACKBONE_MDTC) return i == 0 ? 1 : 1 << ((i - 1) % d.stack_size);   // mdtc.py:151-156, :229-237
-  return 1 << i;                                                                                   // tcn.py:131-137
-}
 inline int gen_cache_len(const wekws_hip_desc& d) {
   if (d.backbone == WEKWS_HIP_BACKBONE_GRU) return 0;
   if (d.backbone == WEKWS_HIP_BACKBONE_FSMN) return d.kernel_size - 1 + d.stack_size;
-  int s = 0;
-  for (int i = 0; i < gen_nblocks(d); ++i) s += (d.kernel_size - 1) * gen_dilation(d, i);
-  return s;
+  return int(conv_schedule(d).cache_len);                    // route.h
 }
 // widest row any intermediate of the model has (floats)
 inline int gen_width(const wekws_hip_desc& d) {
@@ -257,7 +248,7 @@ inline size_t gen_workspace_bytes(const GenericModel& m, int B, int T) {
   int pmax = 0;
   if (d.backbone == WEKWS_HIP_BACKBONE_FSMN) pmax = m.cache_len;
   else if (d.backbone != WEKWS_HIP_BACKBONE_GRU)
-    for (int i = 0; i < gen_nblocks(d); ++i) pmax = std::max(pmax, (d.kernel_size - 1) * gen_dilation(d, i));
+    pmax = conv_schedule(d).max_pad;
   const size_t cu = d.backbone == WEKWS_HIP_BACKBONE_FSMN ? d.num_stack : d.hdim;
   size_t n = 4 * gen_al(rows * w * 4) + gen_al(size_t(B) * (pmax + T) * cu * 4);
   if (d.backbone == WEKWS_HIP_BACKBONE_GRU) n += gen_al(size_t(B) * 3 * d.hdim * 4) + gen_al(size_t(B) * d.hdim * 4);
@@ -359,15 +350,15 @@ inline int generic_forward(const GenericModel& m, const float* x, int B, int T, 
       swap();
     }
   } else {
-    const int nb = gen_nblocks(d), ks = d.kernel_size, Pc = m.cache_len;
-    int off = 0;
+    const ConvSchedule sched = conv_schedule(d);              // route.h
+    const int ks = d.kernel_size, Pc = m.cache_len;
     bool zinit = true;
-    for (int i = 0; i < nb; ++i) {
-      const int dil = gen_dilation(d, i), pad = (ks - 1) * dil;
-      const GenCacheMap cm{int64_t(C) * Pc, Pc, 1, off};
+    for (int i = 0; i < sched.nb; ++i) {
+      const ConvBlock blk = sched.block(i);
+      const int dil = blk.dil, pad = blk.pad;
+      const GenCacheMap cm{int64_t(C) * Pc, Pc, 1, blk.cache_off};
       hipLaunchKernelGGL(gen_ctx_kernel, dim3(gen_grid(int64_t(B) * (pad + T) * C)), dim3(256), 0, st, ub, h, int64_t(T) * C, int64_t(C),
                          in_cache, out_cache, cm, B, T, C, pad);
-      off += pad;
       if (d.backbone == WEKWS_HIP_BACKBONE_DS_TCN) {
         const float* wd = p; p += size_t(C) * ks;
         const float* bd = p; p += C;
@@ -395,7 +386,7 @@ inline int generic_forward(const GenericModel& m, const float* x, int B, int T, 
         gen_linear(st, tm, w1, b1, nullptr, o, rows, C, C, GEN_RELU);
         gen_linear(st, o, w2, b2, h, tm, rows, C, C, GEN_RELU | GEN_RES_BEFORE);
         std::swap(tm, o);                                                                               // (the block's output is in `o` again)
-        if (i > 0 && (i - 1) % d.stack_size == d.stack_size - 1) {                                      // end of a stack: mdtc.py:270-273
+        if (blk.zadd) {                                                                                 // end of a stack: mdtc.py:270-273
           hipLaunchKernelGGL(gen_add_kernel, dim3(gen_grid(rows * C)), dim3(256), 0, st, zs, o, rows * C, zinit ? 1 : 0);
           zinit = false;
         }

@@ -18,7 +18,7 @@
 // The results are the reference's: same class (finite / NaN / +Inf / -Inf) at every position of y and of the returned cache,
 // same finite values (tests/test_hip_nonfinite.py against goldens recorded from the live reference).
 //
-// Models that run zero-padded (wekws_hip.hip: pad_conv_shape, pad_gru_hidden -- widths / kernel sizes / hidden sizes no kernel
+// Models that run zero-padded (weight_image.hip.h: pad_conv_shape, pad_gru_hidden -- widths / kernel sizes / hidden sizes no kernel
 // is built for) carry exact-zero weights the caller's model does not have; 0 * NaN would spread the poison through taps and
 // channels that do not exist.  For those models (NfCtx::skip_zero) a zero weight contributes nothing, which reproduces the
 // unpadded model exactly.
@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "../../include/wekws_hip.h"
+#include "route.h"
 
 namespace wekws {
 
@@ -140,14 +141,6 @@ __device__ inline void nf_release(const NfCtx* R, int slot) {
   if (threadIdx.x == 0) atomicExch(&R->slots[slot], 0u);
 }
 
-__device__ inline int nf_conv_nblocks(const wekws_hip_desc& d) {
-  return d.backbone == WEKWS_HIP_BACKBONE_MDTC ? 1 + d.num_stack * d.stack_size : d.num_layers;
-}
-__device__ inline int nf_conv_dilation(const wekws_hip_desc& d, int i) {
-  if (d.backbone == WEKWS_HIP_BACKBONE_MDTC) return i == 0 ? 1 : 1 << ((i - 1) % d.stack_size);
-  return 1 << i;
-}
-
 // ---- conv backbones (DS-TCN, TCN, MDTC), one utterance `b` of one call tile: the operator sequence of generic_forward()
 // (generic.hip.h:315-398) on (T, C) row-major activations in the slot.  Pointers are those of the kernel's CallArgs:
 //   x        first frame of the tile, utterance 0 (+ b * xs_b);   y / ys_b likewise
@@ -173,11 +166,11 @@ __device__ inline void nf_repair_conv(const NfCtx* R, const float* x, int64_t xs
   nf_preproc(R, xb, d.idim, p, p + int64_t(C) * d.idim, h, C, T);
   p += int64_t(C) * d.idim + C;
   __syncthreads();
-  const int nb = nf_conv_nblocks(d);
+  const int nb = route_blocks(d);                             // the schedule: route.h
   int off = 0;
   bool zinit = true;
   for (int i = 0; i < nb; ++i) {
-    const int dil = nf_conv_dilation(d, i), pad = (ks - 1) * dil;
+    const int dil = route_dilation(d, i), pad = (ks - 1) * dil;
     // u = [cache slice | h] (tcn.py:45-53, mdtc.py:98-104); the returned slice = its last `pad` rows
     for (int e = tid; e < (pad + T) * C; e += nthr) {
       const int c = e % C, tau = e / C;
@@ -227,7 +220,7 @@ __device__ inline void nf_repair_conv(const NfCtx* R, const float* x, int64_t xs
         nf_linear(o, C, w2, C, 1, b2, h, C, tm, C, T, C, C, NF_RELU | NF_RES_BEFORE, s0);
         __syncthreads();
         { float* t2 = tm; tm = o; o = t2; }                    // (the block's output is in `o`)
-        if (i > 0 && (i - 1) % d.stack_size == d.stack_size - 1) {                                          // mdtc.py:270-273
+        if (route_stack_end(d, i)) {                                                                        // mdtc.py:270-273
           for (int e = tid; e < T * C; e += nthr) zs[e] = zinit ? o[e] : zs[e] + o[e];
           zinit = false;
           __syncthreads();

@@ -1,4 +1,6 @@
 // WHICH KERNEL RUNS A CALL -- pure functions, and the only place the choice is made.
+//   * conv_schedule()  the blocks of a conv model: dilation, padding, cache slice and end-of-stack of each, cache length, longest
+//     padding -- the one statement of it, usable from device code (ROUTE_HD); conv_workspace(): the scratch layout of a conv call;
 //   * conv_route_flags()  what a conv model can run on, from its (built-shape) descriptor alone -- wekws_hip_create stores it;
 //   * route_defaults() / apply_route_option()  the options of every backbone (wekws_hip_create, wekws_hip_set_option);
 //   * select_conv_route() (flags, options, call) -> Route {family, tile count, split, context variant, fast, grid, threads, LDS
@@ -9,7 +11,7 @@
 //   * fsmn_shape_plan() / select_fsmn_route(): the FSMN kernel's tile and, per tile, its frame tiles, utterances per workgroup, head
 //     slices, grid and LDS bytes;
 //   * effective_precision(): what wekws_hip_effective_precision reports, from the routes a model can take.
-// wekws_hip_forward hands a route to its family's launcher, which executes it: the kernel variant, grid, threads and LDS from the
+// wekws_hip_forward (forward_conv / forward_gru / forward_fsmn) hands a route to its family's launcher, which executes it: the kernel variant, grid, threads and LDS from the
 // route.  A launcher tests no eligibility of its own; it only refuses (-4, an internal error) a route whose threads or LDS bytes are
 // not its kernel's or that names a variant it does not build.  So the geometry below restates every kernel header's (or the kernel
 // headers take their constants from here), and the route the hooks trace records is the launch that ran.
@@ -86,12 +88,53 @@ struct Route {
   const char* why_not;            // set when family == ROUTE_NONE: the invariant that failed
 };
 
-inline int route_blocks(const wekws_hip_desc& d) {
+// ---- THE SCHEDULE of a conv model: which blocks, their dilations, paddings and cache slices, where a stack ends.  The kernels' block
+// tables, the cache maps of a padded model, the any-shape path (generic.hip.h) and the non-finite path (nonfinite.hip.h, on the device:
+// hence ROUTE_HD) all read it from here.
+#ifdef __HIPCC__
+#define ROUTE_HD __host__ __device__
+#else
+#define ROUTE_HD
+#endif
+ROUTE_HD inline int route_blocks(const wekws_hip_desc& d) {
   return d.backbone == WEKWS_HIP_BACKBONE_MDTC ? 1 + d.num_stack * d.stack_size : d.num_layers;
 }
-inline int route_dilation(const wekws_hip_desc& d, int i) {
+ROUTE_HD inline int route_dilation(const wekws_hip_desc& d, int i) {
   if (d.backbone == WEKWS_HIP_BACKBONE_MDTC) return i == 0 ? 1 : 1 << ((i - 1) % d.stack_size);   // mdtc.py:151-156, :229-237
   return 1 << i;                                                                                   // tcn.py:131-137
+}
+// block i closes a stack of an MDTC: its output joins the sum the classifier sees (mdtc.py:270-273)
+ROUTE_HD inline bool route_stack_end(const wekws_hip_desc& d, int i) {
+  return d.backbone == WEKWS_HIP_BACKBONE_MDTC && i > 0 && (i - 1) % d.stack_size == d.stack_size - 1;
+}
+// the dilations of blocks 0 .. i - 1, summed: a stack of S blocks holds 2^S - 1, block 0 of an MDTC stands before the stacks
+ROUTE_HD inline int64_t route_dilations_before(const wekws_hip_desc& d, int i) {
+  if (d.backbone != WEKWS_HIP_BACKBONE_MDTC) return (int64_t(1) << i) - 1;
+  if (i == 0) return 0;
+  const int S = d.stack_size;
+  return 1 + int64_t((i - 1) / S) * ((int64_t(1) << S) - 1) + (int64_t(1) << ((i - 1) % S)) - 1;
+}
+struct ConvBlock {
+  int32_t dil, pad, cache_off;    // padding (kernel_size - 1) x dilation = frames of its cache slice, which starts at cache_off
+  int32_t zadd;                   // route_stack_end
+};
+struct ConvSchedule {
+  wekws_hip_desc d;
+  int32_t nb, max_pad;
+  int64_t cache_len;              // (64 bits: create_generic checks a corrupt descriptor's against the int the kernels index with)
+  ROUTE_HD ConvBlock block(int i) const {
+    const int dil = route_dilation(d, i);
+    return ConvBlock{dil, (d.kernel_size - 1) * dil, int32_t((d.kernel_size - 1) * route_dilations_before(d, i)), route_stack_end(d, i)};
+  }
+};
+// (shifts by the depth of a stack: create_generic refuses depths beyond 24 before it asks)
+ROUTE_HD inline ConvSchedule conv_schedule(const wekws_hip_desc& d) {
+  ConvSchedule s{d, route_blocks(d), 0, (d.kernel_size - 1) * route_dilations_before(d, route_blocks(d))};
+  for (int i = 0; i < s.nb; ++i) {
+    const int64_t pad = int64_t(d.kernel_size - 1) * route_dilation(d, i);
+    s.max_pad = pad > s.max_pad ? int32_t(pad < INT32_MAX ? pad : INT32_MAX) : s.max_pad;
+  }
+  return s;
 }
 inline int route_round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -99,15 +142,14 @@ inline RouteFlags conv_route_flags(const wekws_hip_desc& d, int ds_stream_lds, i
   RouteFlags f{};
   f.ds_stream_lds = ds_stream_lds;
   f.mdtc_stream_lds = mdtc_stream_lds;
-  const int C = d.hdim, ks = d.kernel_size, nb = route_blocks(d);
+  const int C = d.hdim, ks = d.kernel_size;
+  const ConvSchedule s = conv_schedule(d);
   f.kpre16 = route_round_up(d.idim, 32);
+  f.cache_len = int32_t(s.cache_len);
+  f.max_pad = s.max_pad;
   f.dils_1248 = 1;
-  for (int i = 0; i < nb; ++i) {
-    const int dil = route_dilation(d, i), pad = (ks - 1) * dil;
-    f.cache_len += pad;
-    f.max_pad = pad > f.max_pad ? pad : f.max_pad;
-    if (!(dil == 1 || dil == 2 || dil == 4 || dil == 8)) f.dils_1248 = 0;
-  }
+  for (int i = 0; i < s.nb; ++i)
+    if (const int dil = route_dilation(d, i); !(dil == 1 || dil == 2 || dil == 4 || dil == 8)) f.dils_1248 = 0;
   f.dense_ok = d.backbone == WEKWS_HIP_BACKBONE_TCN && f.max_pad <= 56 && C <= 128;
   f.mdtc16_eligible = d.backbone == WEKWS_HIP_BACKBONE_MDTC && C == 64 && ks == 5;
   f.ds_stream_eligible = d.backbone == WEKWS_HIP_BACKBONE_DS_TCN && C == 256 && ks == 8 && f.dils_1248;
@@ -115,6 +157,30 @@ inline RouteFlags conv_route_flags(const wekws_hip_desc& d, int ds_stream_lds, i
                            f.dils_1248;
   f.mm_eligible = d.backbone == WEKWS_HIP_BACKBONE_DS_TCN && C == 256 && ks == 8 && f.max_pad <= 56 && d.head == WEKWS_HIP_HEAD_LINEAR;
   return f;
+}
+
+// ---- THE SCRATCH of a conv call, as byte offsets into the stream's workspace: the ping-pong caches that hand the causal context from
+// one tile of a long input to the next, the global head's running sums (gsum; only where pooled), and -- a zero-padded model -- the
+// widened copies of the caller's in / out caches.  d: the built shape; cache_len: its schedule's.  wekws_hip_workspace_bytes reports
+// `bytes`, the forward takes its pointers from the offsets.
+struct ConvWorkspace {
+  int32_t ntiles, pooled;
+  size_t cache[2], gsum, wide_in, wide_out, bytes;
+};
+inline ConvWorkspace conv_workspace(const wekws_hip_desc& d, int cache_len, int B, int T, bool padded) {
+  ConvWorkspace w{};
+  w.ntiles = (T + WEKWS_HIP_TILE_FRAMES - 1) / WEKWS_HIP_TILE_FRAMES;
+  w.pooled = d.head == WEKWS_HIP_HEAD_GLOBAL;
+  const size_t ce = size_t(B) * d.hdim * cache_len;
+  const size_t wide = padded ? 2 * ce : 0;                  // the caller's caches, widened to the built channel count, in + out
+  const size_t ge = w.pooled ? size_t(B) * d.hdim : 0;
+  const size_t tiled = T <= WEKWS_HIP_TILE_FRAMES ? 0 : 2 * ce + ge;
+  w.cache[1] = ce * sizeof(float);
+  w.gsum = 2 * ce * sizeof(float);
+  w.wide_in = tiled * sizeof(float);
+  w.wide_out = (tiled + ce) * sizeof(float);
+  w.bytes = (tiled + wide) * sizeof(float);
+  return w;
 }
 
 // The product's options for a model (any backbone; f: conv_route_flags, or zero but for out_of_envelope)
@@ -149,7 +215,7 @@ inline int apply_route_option(RouteOptions& o, const wekws_hip_desc& d, const Ro
 }
 
 // The shape a conv model RUNS as (wekws_hip_create): as it is, zero-padded to the next built width / kernel size (exact: see
-// pad_conv_shape in wekws_hip.hip), or on the any-shape path of generic.hip.h.
+// pad_conv_shape in weight_image.hip.h), or on the any-shape path of generic.hip.h.
 enum : int { SHAPE_AS_IS = 0, SHAPE_PADDED = 1, SHAPE_GENERIC = 2 };
 struct ShapePlan {
   int32_t kind, C, ks;            // SHAPE_PADDED: the built width / kernel size it runs as
@@ -312,7 +378,7 @@ inline int gru_f32_lds_bytes(int kpre, int nlayers, int nn) {                   
 }
 
 // The shape a GRU RUNS as (wekws_hip_create): as it is, zero-padded to the built hidden size (exact: see pad_gru_hidden in
-// wekws_hip.hip), or on the any-shape path of generic.hip.h.  (ShapePlan::C: the built hidden size.)
+// weight_image.hip.h), or on the any-shape path of generic.hip.h.  (ShapePlan::C: the built hidden size.)
 inline ShapePlan gru_shape_plan(const wekws_hip_desc& d) {
   ShapePlan p{SHAPE_AS_IS, d.hdim, d.kernel_size, nullptr};
   auto generic = [&](const char* why) { p.kind = SHAPE_GENERIC; p.why = why; return p; };
@@ -554,7 +620,7 @@ struct FsmnRoute {
   int32_t tile_frames, ntiles;    // the call: cut into tiles of tile_frames, chained through ping-pong workspace caches
   int32_t nt, u;                  // this tile: 16-frame tiles per utterance, utterances per workgroup (nt u <= 4)
   int32_t head_slices, grid, lds_bytes;   // workgroups per tile sharing out_linear2's o-tiles (gridDim.y); gridDim.x; LDS bytes
-  size_t ws_bytes;                // the call's scratch
+  size_t ws_bytes, ws_cache;      // the call's scratch: two hand-over caches of ws_cache bytes each (more than one tile)
   const char* why_not;
 };
 // the route of tile `i` of a call of B utterances x T frames
@@ -564,7 +630,8 @@ inline FsmnRoute select_fsmn_route(const FsmnPlan& p, const wekws_hip_desc& d, c
   r.tile_frames = 16 * p.max_nt;
   r.ntiles = (T + r.tile_frames - 1) / r.tile_frames;
   const int P = d.kernel_size + d.stack_size - 1;             // cache frames per layer
-  r.ws_bytes = r.ntiles > 1 ? 2 * size_t(B) * d.num_stack * P * d.num_layers * sizeof(float) : 0;
+  r.ws_cache = size_t(B) * d.num_stack * P * d.num_layers * sizeof(float);
+  r.ws_bytes = r.ntiles > 1 ? 2 * r.ws_cache : 0;
   const int Tt = T - i * r.tile_frames < r.tile_frames ? T - i * r.tile_frames : r.tile_frames;
   if (i < 0 || Tt <= 0) { r.why_not = "tile beyond the call"; return r; }
   // short inputs: pack 2 or 4 utterances into one workgroup, as long as every CU still gets a workgroup

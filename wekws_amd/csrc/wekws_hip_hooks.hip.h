@@ -1,0 +1,247 @@
+// The test hooks of libwekws_hip_hooks.so (make hooks: wekws_hip.hip compiled with -DWEKWS_TEST_HOOKS, which includes this file):
+// the route trace of a forward, the routing functions of route.h without a device, the GRU epoch, a CU hog, the fbank's plan and
+// table.  Not part of the ABI in include/wekws_hip.h: the product library exports nothing outside the header.
+#pragma once
+
+struct RouteTrace {
+  int path = kTraceOther, ntiles = 0;
+  int rec[kTraceMaxTiles][kRecInts];
+};
+static thread_local RouteTrace g_route_trace;
+// family, nt, split, ctx, fast, grid, threads, lds, utts_per_wg
+static void route_record(const wekws::Route& r, int* o) {
+  const int v[kRecInts] = {r.family, r.nt, r.split, r.ctx, r.fast, r.grid, r.threads, r.lds_bytes, r.utts_per_wg};
+  for (int i = 0; i < kRecInts; ++i) o[i] = v[i];
+}
+// family, nn, spw, tchunk (0: one launch), nchunks, slots, tiles, grid, pk | k2 << 1 | nf_in_kernel << 2
+static void route_record(const wekws::GruRoute& r, int* o) {
+  const int v[kRecInts] = {r.family, r.nn, r.spw, r.chunked ? r.tchunk : 0, r.nchunks, r.slots, r.tiles, r.grid,
+                           r.pk | r.k2 << 1 | r.nf_in_kernel << 2};
+  for (int i = 0; i < kRecInts; ++i) o[i] = v[i];
+}
+// tile_frames, nt, u, head_slices, grid, lds, ntiles, 0, 0
+static void route_record(const wekws::FsmnRoute& r, int* o) {
+  const int v[kRecInts] = {r.tile_frames, r.nt, r.u, r.head_slices, r.grid, r.lds_bytes, r.ntiles, 0, 0};
+  for (int i = 0; i < kRecInts; ++i) o[i] = v[i];
+}
+template <class R>
+static void trace(int path, const R& r) {
+  g_route_trace.path = path;
+  if (g_route_trace.ntiles < kTraceMaxTiles) route_record(r, g_route_trace.rec[g_route_trace.ntiles]);
+  ++g_route_trace.ntiles;
+}
+static void trace_reset(int path) {
+  g_route_trace.path = path;
+  g_route_trace.ntiles = 0;
+}
+// the reason text of a debug entry point
+static void say(char* why, int why_len, const char* t) {
+  if (why && why_len > 0 && t) { std::strncpy(why, t, size_t(why_len) - 1); why[why_len - 1] = 0; }
+}
+
+// Set the launch epoch of the stream's wavefront control block, so that a test can walk the 32-bit tag counter across its wrap
+// (tests/test_hip_parity.py::test_gru_wavefront_epoch_wrap).
+extern "C" int wekws_hip_debug_set_gru_epoch(wekws_hip_model* m, void* stream_, unsigned epoch) {
+  if (!m) return fail(WEKWS_HIP_EINVAL, "NULL model");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  DeviceGuard guard(m->device);
+  if (!guard.ok) return fail(WEKWS_HIP_EDEVICE, "hipSetDevice(%d)", m->device);
+  unsigned* ctl = stream_ctl(m, stream);
+  if (!ctl) return WEKWS_HIP_ENOMEM;
+  if (hipMemcpyAsync(ctl, &epoch, sizeof(epoch), hipMemcpyHostToDevice, stream) != hipSuccess ||
+      hipStreamSynchronize(stream) != hipSuccess)
+    return fail(WEKWS_HIP_EDEVICE, "setting the epoch: %s", hipGetErrorString(hipGetLastError()));
+  return WEKWS_HIP_OK;
+}
+// A tenant that keeps CUs busy: `blocks` workgroups of 128 KB of LDS each (one per CU, like the wavefront's own), every one
+// holding its CU for `ms` milliseconds of wall clock.  tests: a wavefront launch whose later workgroups find no CU for longer
+// than its bounded waits must END (not hang) and be reported by the next call; a shorter squeeze must change nothing.
+// ms < 0: the same occupancy with every SIMD BUSY (matrix + vector instructions, no memory traffic) for -ms milliseconds -- to
+// tell a neighbour's compute / power from a neighbour's memory traffic (tools/probe/gru_neighbours.py)
+extern "C" __global__ void debug_hog_kernel(unsigned long long ticks, int busy) {
+  extern __shared__ char hog_lds[];
+  if (threadIdx.x == 0) hog_lds[0] = 1;
+  const unsigned long long t0 = wall_clock64();              // 100 MHz
+  if (!busy) {
+    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(127);
+    return;
+  }
+  typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  h8 a = {1, 1, 1, 1, 1, 1, 1, 1}, b = a;
+  f4 c0 = {0, 0, 0, 0}, c1 = c0;
+  float v = float(threadIdx.x);
+  while (wall_clock64() - t0 < ticks) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c0, 0, 0, 0);
+      c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c1, 0, 0, 0);
+      v = fmaf(v, 1.0001f, 0.5f);
+    }
+  }
+  if (c0[0] + c1[0] + v == 12345.f) hog_lds[1] = 1;
+}
+// The routing functions of route.h, callable WITHOUT a device (tests/test_route.py, hooks library only).
+//   desc: any conv descriptor wekws_hip_create accepts.  opts[9] (or NULL = the defaults for that precision): w16_ok, g16_ok, g16_ctx,
+//   g16_one_pass, stream_ok, mdtc16_ok, mm_ok (-1: the default: CTC-sized heads), f32, split.  call[8]: B, T (of the tile), ntiles,
+//   has_in, has_out, x16, cache16, cus.  out[16]: plan kind, built C, built ks, family, nt, split, ctx, fast, grid, threads, lds,
+//   utts_per_wg, cache_len (built shape), max_pad, head_slices, effective precision (of the model under these options).  why: the
+//   reason text for "any-shape path" / "no kernel".  Returns 0.
+extern "C" int wekws_hip_debug_conv_route(const wekws_hip_desc* desc, const int* opts, const int* call, int* out, char* why, int why_len) {
+  if (!desc || !call || !out || !desc_conv(*desc)) return WEKWS_HIP_EINVAL;
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  if (why && why_len > 0) why[0] = 0;
+  const wekws::ShapePlan plan = wekws::conv_shape_plan(*desc, wekws::kAmaxMaxBlocks);
+  out[0] = plan.kind; out[1] = plan.C; out[2] = plan.ks;
+  if (plan.kind == wekws::SHAPE_GENERIC) { say(why, why_len, plan.why); return WEKWS_HIP_OK; }
+  wekws_hip_desc d = *desc;
+  d.hdim = plan.C; d.kernel_size = plan.ks;
+  const int cache_len = wekws::conv_route_flags(d, 0, 0).cache_len;
+  const wekws::RouteFlags ff = wekws::conv_route_flags(d, int(wekws::ds256_stream_lds_bytes(cache_len)), int(wekws::mdtc64_stream_lds_bytes(cache_len)));
+  wekws::RouteOptions o = wekws::route_defaults(d, ff);
+  if (opts) {
+    o.w16_ok = opts[0]; o.g16_ok = opts[1]; o.g16_ctx = opts[2]; o.g16_one_pass = opts[3]; o.stream_ok = opts[4];
+    wekws::apply_route_option(o, d, ff, WEKWS_HIP_OPT_MDTC16, opts[5]);
+    wekws::apply_route_option(o, d, ff, WEKWS_HIP_OPT_MM, opts[6]);
+    o.f32 = opts[7]; o.split = opts[8];
+  }
+  wekws::RouteCall c{call[0], call[1], call[2], call[3], call[4], call[5], call[6], call[7]};
+  const wekws::Route r = wekws::select_conv_route(d, ff, o, c);
+  out[3] = r.family; out[4] = r.nt; out[5] = r.split; out[6] = r.ctx; out[7] = r.fast; out[8] = r.grid; out[9] = r.threads; out[10] = r.lds_bytes;
+  out[11] = r.utts_per_wg; out[12] = ff.cache_len; out[13] = ff.max_pad; out[14] = r.head_slices;
+  out[15] = wekws::effective_precision(d, ff, o, c.cus);
+  if (r.family == wekws::ROUTE_NONE) say(why, why_len, r.why_not);
+  else say(why, why_len, wekws::route_family_name(r.family));
+  return WEKWS_HIP_OK;
+}
+// the route of the calling thread's last conv launch: out[9] = family, nt, split, ctx, fast, grid, threads, lds, utts_per_wg
+extern "C" int wekws_hip_debug_last_route(int* out) {
+  if (!out) return WEKWS_HIP_EINVAL;
+  route_record(g_last_route, out);
+  return WEKWS_HIP_OK;
+}
+// GRU (hooks library only): desc: any GRU descriptor wekws_hip_create accepts; opts: nopts (WEKWS_HIP_OPT_*, value) pairs applied to
+// the defaults.  call[5]: B, T, x16, cus, with_reserve.  out[20] (int64): plan kind, built hidden size, the 9 ints of the trace
+// record (route_record), stages, slots_p, lds, chunked, plain bytes, granule bytes, reserved plain / granule bytes (with_reserve),
+// effective precision.  why: the family's name, or the reason.  Returns 0.
+extern "C" int wekws_hip_debug_gru_route(const wekws_hip_desc* desc, const int* opts, int nopts, const int* call, int64_t* out, char* why,
+                                         int why_len) {
+  if (!desc || !call || !out || desc->backbone != WEKWS_HIP_BACKBONE_GRU || (nopts && !opts)) return WEKWS_HIP_EINVAL;
+  for (int i = 0; i < 20; ++i) out[i] = 0;
+  const wekws::ShapePlan plan = wekws::gru_shape_plan(*desc);
+  out[0] = plan.kind; out[1] = plan.C;
+  if (plan.kind == wekws::SHAPE_GENERIC) { say(why, why_len, plan.why); return WEKWS_HIP_OK; }
+  wekws_hip_desc d = *desc;
+  d.hdim = plan.C;
+  const wekws::RouteFlags f{};
+  wekws::RouteOptions o = wekws::route_defaults(d, f);
+  for (int i = 0; i < nopts; ++i)
+    if (wekws::apply_route_option(o, d, f, opts[2 * i], opts[2 * i + 1])) return WEKWS_HIP_EINVAL;
+  const wekws::GruCall c{call[0], call[1], call[2], plan.kind == wekws::SHAPE_PADDED, call[3]};
+  const wekws::GruRoute r = wekws::select_gru_route(d, o, c);
+  int rec[kRecInts];
+  route_record(r, rec);
+  for (int i = 0; i < kRecInts; ++i) out[2 + i] = rec[i];
+  out[11] = r.stages; out[12] = r.slots_p; out[13] = r.lds_bytes; out[14] = r.chunked;
+  out[15] = int64_t(r.plain_bytes); out[16] = int64_t(r.granule_bytes);
+  if (call[4]) {
+    size_t p = 0, g = 0;
+    wekws::gru_reserve_bytes(d, o, c, &p, &g);
+    out[17] = int64_t(p); out[18] = int64_t(g);
+  }
+  out[19] = wekws::effective_precision(d, f, o, c.cus);
+  say(why, why_len, r.family == wekws::GRU_NONE ? r.why_not : wekws::gru_family_name(r.family));
+  return WEKWS_HIP_OK;
+}
+// FSMN (hooks library only): desc: any FSMN descriptor; opts / nopts as above.  call[4]: B, T, tile index, cus.  out[16]: plan kind,
+// max_nt, the 9 ints of the tile's trace record, workspace bytes of the call, effective precision, 0...  Returns 0.
+extern "C" int wekws_hip_debug_fsmn_route(const wekws_hip_desc* desc, const int* opts, int nopts, const int* call, int64_t* out, char* why,
+                                          int why_len) {
+  if (!desc || !call || !out || desc->backbone != WEKWS_HIP_BACKBONE_FSMN || (nopts && !opts)) return WEKWS_HIP_EINVAL;
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  const wekws::FsmnPlan plan = wekws::fsmn_shape_plan(*desc);
+  out[0] = plan.kind; out[1] = plan.max_nt;
+  if (plan.kind == wekws::SHAPE_GENERIC) { say(why, why_len, plan.why); return WEKWS_HIP_OK; }
+  const wekws::RouteFlags f{};
+  wekws::RouteOptions o = wekws::route_defaults(*desc, f);
+  for (int i = 0; i < nopts; ++i)
+    if (wekws::apply_route_option(o, *desc, f, opts[2 * i], opts[2 * i + 1])) return WEKWS_HIP_EINVAL;
+  const wekws::FsmnRoute r = wekws::select_fsmn_route(plan, *desc, o, call[0], call[1], call[2], call[3]);
+  int rec[kRecInts];
+  route_record(r, rec);
+  for (int i = 0; i < kRecInts; ++i) out[2 + i] = rec[i];
+  out[11] = int64_t(r.ws_bytes);
+  out[12] = wekws::effective_precision(*desc, f, o, call[3]);
+  say(why, why_len, r.why_not ? r.why_not : "fsmn_f16");
+  return WEKWS_HIP_OK;
+}
+// the route of every tile of the calling thread's last forward: out[0] = path (0: no forward yet; 1: the conv routes of route.h;
+// 2: the any-shape path of generic.hip.h; 3: the GRU route of route.h -- one record; 4: the FSMN routes of route.h), out[1] =
+// records of the call, then per record (at most max_tiles, and the first 256 of a call) its 9 ints: conv, the values of
+// wekws_hip_debug_last_route; GRU / FSMN, route_record's.  out holds 2 + 9 * max_tiles ints.  Returns the number of records written.
+extern "C" int wekws_hip_debug_route_trace(int* out, int max_tiles) {
+  if (!out || max_tiles < 0) return WEKWS_HIP_EINVAL;
+  const RouteTrace& t = g_route_trace;
+  out[0] = t.path; out[1] = t.ntiles;
+  int n = t.ntiles < kTraceMaxTiles ? t.ntiles : kTraceMaxTiles;
+  n = n < max_tiles ? n : max_tiles;
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < kRecInts; ++k) out[2 + kRecInts * i + k] = t.rec[i][k];
+  return n;
+}
+extern "C" int wekws_hip_debug_hog(int device, int blocks, int ms, void* stream_) {
+  DeviceGuard guard(device);
+  const int busy = ms < 0;
+  if (busy) ms = -ms;
+  if (!guard.ok || blocks <= 0 || ms > 2000) return fail(WEKWS_HIP_EINVAL, "hog: device %d blocks %d ms %d", device, blocks, ms);
+  static wekws::DynLdsGrant grant;
+  if (wekws::grant_dynamic_lds(debug_hog_kernel, 128 * 1024, grant)) return fail(WEKWS_HIP_EDEVICE, "hog: LDS grant");
+  hipLaunchKernelGGL(debug_hog_kernel, dim3(blocks), dim3(busy ? 512 : 64), 128 * 1024, static_cast<hipStream_t>(stream_), 100000ull * ms, busy);
+  return hipGetLastError() == hipSuccess ? WEKWS_HIP_OK : fail(WEKWS_HIP_EDEVICE, "hog launch");
+}
+
+// --------------------------------------------- fbank ---------------------------------------------
+// what the last fbank launch of this thread ran, the table plan, the device table
+// out[8]: rounds, sample size in bytes, pair_ok, grid, resident, B, nsamp, nframes as launch_fbank recorded them at this thread's last launch
+extern "C" int wekws_hip_debug_fbank_last(int* out) {
+  if (!out) return WEKWS_HIP_EINVAL;
+  for (int i = 0; i < 8; ++i) out[i] = wekws::fbank_last_launch()[i];
+  return WEKWS_HIP_OK;
+}
+// The table plan of a configuration, WITHOUT a device (fbank_build_tables alone).  out[16]: rounds (mel slots per lane), nslots, spectrum
+// stride (512 / the reference's transform length), slots of the widest filter, kFbankFW, kFbankWaves, mel_first_off, mel_size_off,
+// mel_start_off, mel_w_off, mel_w_count, slot_first_off, slot_bin_off, slot_w_off, table_floats, first empty filter (-1: none; then
+// the plan before it is not filled in and wekws_hip_fbank_create refuses the configuration).
+extern "C" int wekws_hip_debug_fbank_plan(const wekws_hip_fbank_cfg* cfg, int* out) {
+  if (!cfg || !out || cfg->num_bins <= 0 || cfg->num_bins > wekws::kFbankMaxBins || cfg->sample_rate <= 0 || cfg->frame_length <= 64 ||
+      cfg->frame_length > wekws::kFbankMaxFft || cfg->frame_shift <= 0)
+    return WEKWS_HIP_EINVAL;
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  wekws::FbankParams fp{};
+  std::vector<float> t;
+  out[15] = wekws::fbank_build_tables(cfg->num_bins, cfg->sample_rate, cfg->frame_length, cfg->frame_shift, cfg->window, &fp, &t);
+  out[2] = wekws::kFbankMaxFft / wekws::fbank_ref_points(cfg->frame_length);
+  out[4] = wekws::kFbankFW;
+  out[5] = wekws::kFbankWaves;
+  if (out[15] >= 0) return WEKWS_HIP_OK;
+  int widest = 0;
+  for (int b = 0; b < fp.num_bins; ++b) widest = std::max(widest, (int(t[size_t(fp.mel_size_off) + b]) + 15) / 16);
+  const int v[15] = {(fp.nslots + 63) / 64, fp.nslots, out[2], widest, out[4], out[5], fp.mel_first_off, fp.mel_size_off, fp.mel_start_off,
+                     fp.mel_w_off, fp.mel_w_count, fp.slot_first_off, fp.slot_bin_off, fp.slot_w_off, fp.table_floats};
+  for (int i = 0; i < 15; ++i) out[i] = v[i];
+  return WEKWS_HIP_OK;
+}
+// Read (set == 0) or overwrite (set != 0) the handle's device table: n must be its table_floats.  The kernel takes its per-lane constants
+// (twiddles, window, mel slots) from this table at every launch, so a test can run it on a perturbed table and put the table back.
+extern "C" int wekws_hip_debug_fbank_tables(wekws_hip_fbank* f, float* host_buf, int n, int set) {
+  if (!f || !host_buf || n != f->fp.table_floats) return fail(WEKWS_HIP_EINVAL, "fbank tables: n=%d, the table has %d floats", n, f ? f->fp.table_floats : 0);
+  DeviceGuard guard(f->device);
+  if (!guard.ok) return fail(WEKWS_HIP_EDEVICE, "hipSetDevice(%d)", f->device);
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess)
+    e = set ? hipMemcpy(f->d_tables, host_buf, size_t(n) * sizeof(float), hipMemcpyHostToDevice)
+            : hipMemcpy(host_buf, f->d_tables, size_t(n) * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "fbank tables: %s", hipGetErrorString(e));
+  return WEKWS_HIP_OK;
+}
