@@ -86,6 +86,11 @@ def case_config(case):
     cfg = copy.deepcopy(synth.MODEL_CONFIGS[case["model"]])
     if case.get("odim"):
         cfg["output_dim"] = case["odim"]
+    if case.get("classifier"):                   # a pooled head on a backbone whose recipe has the per-frame one
+        cfg["classifier"] = {"type": case["classifier"], "dropout": 0.5}
+    if case.get("no_subsampling"):               # NoSubsampling (subsampling.py:35-36): the features ARE the hidden tile
+        cfg["preprocessing"] = {"type": "none"}
+        cfg["input_dim"] = cfg["hidden_dim"]
     if case["cmvn"]:
         # cmvn stats are injected as buffers (no cmvn_file on disk); "_cmvn" tells the
         # builders to attach a GlobalCMVN whose mean/istd come from the state_dict.
@@ -96,7 +101,8 @@ def case_config(case):
 
 def case_input(case):
     cfg = synth.MODEL_CONFIGS[case["model"]]
-    return synth.synth_feats(case["B"], case["T"], cfg["input_dim"], seed=case["xseed"],
+    idim = cfg["hidden_dim"] if case.get("no_subsampling") else cfg["input_dim"]
+    return synth.synth_feats(case["B"], case["T"], idim, seed=case["xseed"],
                              cmvn_like=case["cmvn"])
 
 

@@ -26,6 +26,11 @@ def _std(T, idim):
             _x(4, c, 1 % idim, "nan"), _x(4, a, 5 % idim, "+inf"), _x(4, bq, 2 % idim, "-inf")]
 
 
+# frames 0 .. 3 of utterances 0 / 1 / 2: NaN / +Inf / -Inf, one feature per frame
+def _head():
+    return [_x(b, t, (3 + 5 * t) % 40, v) for b, v in enumerate(("nan", "+inf", "-inf")) for t in range(4)]
+
+
 CASES = []
 for _m, _idim in (("ds_tcn_h256", 40), ("ds_tcn_h64", 40), ("tcn_h64", 40), ("mdtc_h64", 40), ("mdtc_small", 40),
                   ("mdtc_h64_global12", 40), ("mdtc_small_last12", 40), ("gru_2x128", 40), ("fsmn_small", 40),
@@ -62,6 +67,16 @@ CASES += [
        softmax=True),
     # CMVN folded into the first Linear: (Inf - mean) * istd
     _c("ds_tcn_h256/cmvn", "ds_tcn_h256", 4, 98, [_x(1, 50, 3, "nan"), _x(2, 30, 7, "+inf"), _x(3, 60, 0, "-inf")], cmvn=True, xseed=1),
+    # running sums poisoned, inputs clean again: a GLOBAL head on a long input with the poison in frames 0 .. 3 only -- a later
+    # 112-frame tile sees clean features and a clean cache (receptive fields: 184 / 106 / 244 frames) and must still return what
+    # the pooled sums carry.  Utterance 0 NaN, 1 +Inf, 2 -Inf, 3 clean.
+    _c("mdtc_small_global12/sums_T300", "mdtc_small_global12", 4, 300, _head(), xseed=21),
+    _c("ds_tcn_h64_global/sums_T225", "ds_tcn_h64", 4, 225, _head(), classifier="global", xseed=22),
+    _c("mdtc_h64_global12/sums_T480", "mdtc_h64_global12", 4, 480, _head(), xseed=23),
+    # NoSubsampling: an Inf in one channel stays in that channel (through a full matrix product it would meet the zeros of every
+    # other row of the diagonal: tests/test_nonfinite_matrix.py, defect side)
+    _c("ds_tcn_h64_nosub/full", "ds_tcn_h64", 4, 60, [_x(1, 20, 3, "nan"), _x(2, 10, 63, "+inf"), _x(3, 30, 0, "-inf")], no_subsampling=True,
+       xseed=24),
 ]
 
 

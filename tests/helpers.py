@@ -2,6 +2,7 @@
 import numpy as np
 
 from tests.golden.cases import CASES, case_config, case_in_cache, case_input  # noqa: F401
+from tests.golden.nonfinite_cases import classify as value_classes  # 0 finite, 1 NaN (any encoding), 2 +Inf, 3 -Inf
 from wekws_amd import pack
 from wekws_amd.utils import synth
 
@@ -181,6 +182,27 @@ def random_config_spec(cfg):
 #     state channel of a two-stream row), FSMN at most 2.4e-6 (the 2599-class head); the rounded-matrix control misses the bar
 #     on each of their 40 control rows, by 1.78x at least for the GRU (a full batch raises the channels' scales above those
 #     of the 4-utterance CPU case) and 2.41x for FSMN.
+# Non-finite inputs (tests/nonfinite_matrix.py: 171 rows DERIVED from the two matrices, NaN / +-Inf in the features or in the
+# incoming cache / state of every route tuple -- conv 92 / 92, GRU 31 / 31, FSMN 22 / 22 by the coarse keys of nm.issue_key, plus
+# the padded and any-shape plans; masked_tight_error: classes first, then the bar on the finite values with S_c over the finite
+# reference values).  Calibrated on the CPU from three sides (tests/test_nonfinite_matrix.py), at the poisoned utterances plus two
+# clean ones of every row:
+#   * reference side: the float32 oracle has the float64 oracle's classes on every row and reaches 0.35 of the bar (FSMN, the
+#     2599-class head from a poisoned cache at B = 1), 0.30 (conv) and 0.29 (GRU); on the 33 golden cases 4.5e-6 = 0.15 of the
+#     bar (mdtc_small_last12/full).  Seven rows were moved or reseeded for it (nm.MOVED: one utterance whose few finite frames
+#     set every channel's scale is held to its own magnitude element by element); the bar did not move.
+#   * defect side, each a CLASS mismatch: the oracle with an fmax ReLU (relu(NaN) = 0: a missed detection) on each of the 125
+#     rows where a NaN meets a ReLU; the oracle on zero-padded weights (0 x NaN: skip_zero off) on the row whose KERNEL SIZE is
+#     padded -- where only the width is padded it cannot differ in what the caller sees, which the test asserts too --;
+#     NoSubsampling through the full matrix product (0 x Inf) on the golden case without a subsampling layer.
+#   * value side: on the finite values of the poisoned utterances ALONE, the most visible single weight matrix rounded to fp16
+#     misses the bar by 8.0 x (conv) / 3.1 x (FSMN) / 2.2 x (GRU) at the least, CONTROL_MARGIN = 1.5 asked; six rows keep nothing
+#     finite that a weight has touched (a poisoned state of a one-layer GRU, the only frame of a one-frame call) and are
+#     exempt by that rule, not by name.
+# GPU (tests/test_hip_nonfinite_matrix.py), all 171 rows, repaired and clean parts alike: conv at most 7.6e-6 (the repaired
+# utterances 3.8e-6), FSMN 1.27e-5 (the 2599-class head at B = 1, poisoned cache), GRU 1.62e-5 = 0.53 of the bar (h0 poisoned in
+# the last layer at B = 1: the first layer's 128 finite state values, each its own scale); the six stress rows at most 1.7e-6;
+# the f16 reruns' fast path at 0.01 of its 2e-2.  Per route in the error report of a GPU run under nonfinite_matrix/...
 TIGHT_K = 2.0 ** -15
 F16_TOL = 5e-4
 CHANNEL_FLOOR = 2.0 ** -10
@@ -200,6 +222,35 @@ def tight_error(got, ref, axis=None):
     axis = axis % ref.ndim
     other = tuple(i for i in range(ref.ndim) if i != axis)
     a = np.abs(ref)
+    s = np.maximum(a.max(axis=other, keepdims=True), CHANNEL_FLOOR * float(a.max()))
+    s = np.where(s > 0, s, 1.0)
+    return float((d / s).max())
+
+
+def masked_tight_error(got, ref, axis=None, where=None, scale_ref=None):
+    """tight_error for results that may hold NaN / +-Inf (non-finite inputs: tests/nonfinite_matrix.py).  Classes first: inf unless
+    got and ref are finite / NaN / +Inf / -Inf at the same positions (where: a boolean mask of the positions that count, all of
+    them by default).  Then max |got - ref| / S_c over the finite positions that count, S_c as in tight_error but taken over the
+    FINITE values of the whole reference (scale_ref: of that tensor instead -- a stream's concatenated chunks), whatever `where`
+    selects: a subset is held to the scales of the tensor it is part of."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    where = np.ones(ref.shape, bool) if where is None else np.broadcast_to(where, ref.shape)
+    if not ref.size or not where.any():
+        return 0.0
+    cg, cr = value_classes(got), value_classes(ref)
+    if not np.array_equal(cg[where], cr[where]):
+        return float("inf")
+    fin = (cr == 0) & where
+    if not fin.any():
+        return 0.0
+    d = np.where(fin, np.abs(np.where(fin, got, 0.0) - np.where(fin, ref, 0.0)), 0.0)
+    if axis is None:
+        return float(d.max())
+    sref = ref if scale_ref is None else np.asarray(scale_ref, np.float64)
+    axis = axis % ref.ndim
+    other = tuple(i for i in range(ref.ndim) if i != axis)
+    a = np.where(np.isfinite(sref), np.abs(sref), 0.0)
     s = np.maximum(a.max(axis=other, keepdims=True), CHANNEL_FLOOR * float(a.max()))
     s = np.where(s > 0, s, 1.0)
     return float((d / s).max())
@@ -228,6 +279,15 @@ def oracle64(cfg, sd, x, in_cache=None, chunks=None, softmax=False):
             t += n
         return np.concatenate(ys, axis=1), c
     return kws_oracle.forward(cfg, sd, x, in_cache, softmax=softmax, dtype=np.float64)
+
+
+def golden_oracle64(case, cfg, sd, x, c0):
+    """The float64 oracle on a golden case (tests/golden/nonfinite_cases.py: chunks or one call, forward or forward_softmax)."""
+    from oracle import kws_oracle
+    with np.errstate(all="ignore"):
+        if case.get("chunks"):
+            return kws_oracle.forward_streaming(cfg, sd, x, case["chunks"], c0, dtype=np.float64)
+        return kws_oracle.forward(cfg, sd, x, c0, softmax=case.get("softmax", False), dtype=np.float64)
 
 
 def tight_errors(cfg, y, c, ry, rc, softmax=False):

@@ -1,8 +1,10 @@
 """GPU: NaN / +Inf / -Inf in the features or in a carried cache -- the HIP path returns what the reference returns
 (torch.relu(nan) = nan and IEEE arithmetic: wekws/model/tcn.py:101-114, mdtc.py:95-121, kws_model.py:65-76): the same class
-(finite / NaN / +Inf / -Inf) at every position of y and of the returned cache, finite values within the 1e-4 bar, and every OTHER
-utterance of the batch bit-identical to the same call without the poison.  Goldens: tests/golden/nonfinite_golden.npz, recorded
-from the live reference (make_nonfinite_golden.py); the oracle is pinned to them by tests/test_nonfinite_oracle.py.
+(finite / NaN / +Inf / -Inf) at every position of y and of the returned cache, finite values within the TIGHT bar
+(tests/helpers.py::masked_tight_error: classes first, then |got - ref| / S_c <= TIGHT_K with S_c over the finite reference
+values), and every OTHER utterance of the batch bit-identical to the same call without the poison where a workgroup owns one
+utterance.  Goldens: tests/golden/nonfinite_golden.npz, recorded from the live reference (make_nonfinite_golden.py); the oracle is
+pinned to them by tests/test_nonfinite_oracle.py.  Every kernel route with poison: tests/test_hip_nonfinite_matrix.py.
 How: wekws_amd/csrc/nonfinite.hip.h."""
 import os
 
@@ -12,9 +14,8 @@ import torch
 
 from tests.golden.nonfinite_cases import CASES, classify, poisoned_input
 from tests.golden.cases import case_in_cache, case_input
-from tests.helpers import case_weights, random_model_config as _random_model_config
+from tests.helpers import TIGHT_K, cache_axis, case_weights, golden_oracle64, masked_tight_error, random_model_config as _random_model_config, y_axis
 from tests.test_hip_parity import build, run
-from tests.test_nonfinite_oracle import run_oracle
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -25,17 +26,24 @@ def nf_golden():
     return np.load(os.path.join(HERE, "golden", "nonfinite_golden.npz"))
 
 
-def same_classes_and_values(a, ref, what, tol=1e-4):
+def same_classes_and_values(a, ref, what, axis, where=None):
+    """Classes equal at every position; finite values (where: of the positions that count) under the masked tight bar."""
     assert a.shape == ref.shape, what
     ca, cr = classify(a), classify(ref)
     if not np.array_equal(ca, cr):
         bad = np.argwhere(ca != cr)
         raise AssertionError(f"{what}: {len(bad)} positions differ in class, first {bad[0].tolist()}: got {ca[tuple(bad[0])]} "
                              f"want {cr[tuple(bad[0])]}")
-    fin = cr == 0
+    err = masked_tight_error(a, ref, axis, where)
+    assert err <= TIGHT_K, f"{what}: finite values off by {err:.3e} (bar {TIGHT_K:.3e})"
+
+
+def within_f16_bar(a, ref, what, where):
+    """The one-fp16-product fast path's bar (precision f16): 2e-2 max(1, max|ref|) on the finite positions that count."""
+    fin = np.isfinite(ref) & where
     if fin.any():
         err = float(np.abs(a[fin].astype(np.float64) - ref[fin]).max())
-        assert err <= tol * max(1.0, float(np.abs(ref[fin]).max())), f"{what}: finite values off by {err:.3e}"
+        assert err <= 2e-2 * max(1.0, float(np.abs(ref[fin]).max())), f"{what}: finite values off by {err:.3e}"
 
 
 def poisoned_rows(case, cfg):
@@ -51,31 +59,40 @@ def test_nonfinite_inputs_propagate_like_the_reference(case, precision, nf_golde
     model = build(cfg, sd).set_precision(precision)
     x, cache0 = poisoned_input(case, cfg)
     y, cache = run(model, x, cache0, softmax=case.get("softmax", False), chunks=case.get("chunks"))
-    # (a) the live reference's classes and y
+    # (a) the live reference's classes and y (its float32 result: 4.5e-6 from the float64 oracle at worst, inside the bar)
     name = case["name"]
-    same_classes_and_values(y, nf_golden[name + "/y"], "y vs reference golden")
+    ya, ca = y_axis(cfg, case.get("softmax", False)), cache_axis(cfg)
+    same_classes_and_values(y, nf_golden[name + "/y"], "y vs reference golden", ya)
     assert np.array_equal(classify(cache), nf_golden[name + "/cache_class"]), "cache classes vs reference golden"
-    # (b) the oracle, values of the cache included
-    ry, rc = run_oracle(case, cfg, sd, x, cache0)
-    same_classes_and_values(y, ry, "y vs oracle")
-    same_classes_and_values(cache, rc, "cache vs oracle")
-    # (c) the utterances without poison: bit-identical to the same call on clean inputs
-    xc, cc = case_input(case), case_in_cache(case, cfg)
-    yc, cachec = run(model, xc, cc, softmax=case.get("softmax", False), chunks=case.get("chunks"))
+    # (b) the float64 oracle, values of the cache included
+    ry, rc = golden_oracle64(case, cfg, sd, x, cache0)
+    same_classes_and_values(y, ry, "y vs oracle", ya)
+    same_classes_and_values(cache, rc, "cache vs oracle", ca)
+    # (c) the utterances without poison
     bad = poisoned_rows(case, cfg)
     clean = [b for b in range(case["B"]) if b not in bad]
     assert clean, "every case keeps at least one clean utterance"
     gru = cfg["backbone"]["type"] == "gru"
-    cl, clc = (cache[:, clean], cachec[:, clean]) if gru else (cache[clean], cachec[clean])
-    # One utterance per workgroup (every DS-TCN h256 kernel): the neighbours run the fast path, bit for bit.  Kernels that pack
-    # 2 .. 4 utterances into a workgroup (hidden_dim <= 64 on the LDS-tile kernels, the MDTC streaming step) re-compute the
-    # workgroup's other utterances with the same exact-f32 routine, and the GRU kernels share a per-step operand scale among 16
-    # streams (the poisoned element enters as 0): there the neighbours are equal to fp32 rounding, not to the bit.
+    # One utterance per workgroup (every DS-TCN h256 kernel): the neighbours run the fast path, bit for bit as in the same call on
+    # clean inputs.  Kernels that pack 2 .. 4 utterances into a workgroup (hidden_dim <= 64 on the LDS-tile kernels, the MDTC
+    # streaming step) re-compute the workgroup's other utterances with the same exact-f32 routine, and the GRU kernels share a
+    # per-step operand scale among 16 streams (the poisoned element enters as 0): there the neighbours meet the tight bar
+    # against the oracle like everything else.
     if case["model"].startswith("ds_tcn_h256"):
+        xc, cc = case_input(case), case_in_cache(case, cfg)
+        yc, cachec = run(model, xc, cc, softmax=case.get("softmax", False), chunks=case.get("chunks"))
+        cl, clc = (cache[:, clean], cachec[:, clean]) if gru else (cache[clean], cachec[clean])
         assert np.array_equal(y[clean], yc[clean]) and np.array_equal(cl, clc), "clean utterances changed"
     else:
-        assert float(np.abs(y[clean].astype(np.float64) - yc[clean]).max()) <= 5e-6 * max(1.0, float(np.abs(yc[clean]).max()))
-        assert float(np.abs(cl.astype(np.float64) - clc).max()) <= 5e-6 * max(1.0, float(np.abs(clc).max()))
+        my = np.zeros(ry.shape, bool)
+        my[clean] = True
+        mc = np.zeros(rc.shape, bool)
+        if gru:
+            mc[:, clean] = True
+        else:
+            mc[clean] = True
+        same_classes_and_values(y, ry, "clean utterances' y vs oracle", ya, my)
+        same_classes_and_values(cache, rc, "clean utterances' cache vs oracle", ca, mc)
 
 
 @pytest.mark.parametrize("precision", ["f16x3", "f32", "f16"])
@@ -103,10 +120,43 @@ def test_nonfinite_fuzz(seed, precision):
             cuts = sorted(set(int(c) for c in rng.integers(1, T, size=int(rng.integers(1, 4)))))
             chunks = [b - a for a, b in zip([0] + cuts, cuts + [T])]
         y, cache = run(model, x, cache0, chunks=chunks)
-        with np.errstate(all="ignore"):
-            ry, rc = (kws_oracle.forward_streaming(cfg, sd, x, chunks, cache0) if chunks else kws_oracle.forward(cfg, sd, x, cache0))
-        tol = 1e-4 if precision != "f16" else 2e-2
         what = f"seed {seed} trial {trial} {precision} B={B} T={T} chunks={chunks} {cfg}"
-        same_classes_and_values(y, ry, "y: " + what, tol)
-        same_classes_and_values(cache, rc, "cache: " + what, tol)
+        ya, ca = y_axis(cfg), cache_axis(cfg)
+        # the float64 oracle in the pieces the kernels cut the input into: the caller's chunks, and 112-frame tiles inside a chunk
+        # (one launch per tile, the context handed over through the returned cache; the GRU takes a call whole) -- the same
+        # function for the per-frame heads, and its caches at the cuts say which pieces of a poisoned utterance were repaired
+        pieces = []
+        for n in (chunks or [T]):
+            pieces += [n] if gru else [min(112, n - t0) for t0 in range(0, n, 112)]
+        with np.errstate(all="ignore"):
+            ry, rc = (kws_oracle.forward_streaming(cfg, sd, x, chunks, cache0, dtype=np.float64) if chunks else
+                      kws_oracle.forward(cfg, sd, x, cache0, dtype=np.float64))
+        if precision != "f16":
+            same_classes_and_values(y, ry, "y: " + what, ya)
+            same_classes_and_values(cache, rc, "cache: " + what, ca)
+        else:
+            # one fp16 product on the fast path: the repaired pieces of the poisoned utterances -- IEEE f32 whatever was asked --
+            # are held to the tight bar, everything else to the fast path's 2e-2
+            assert np.array_equal(classify(y), classify(ry)) and np.array_equal(classify(cache), classify(rc)), "classes: " + what
+            # (a piece is exact only while every piece of the utterance before it was repaired too: behind a fast-path piece the
+            # repair starts from a cache of fp16 precision)
+            rep_y, rep_c = np.zeros(ry.shape, bool), np.zeros(rc.shape, bool)
+            exact = np.ones(B, bool)
+            with np.errstate(all="ignore"):
+                c, t0 = cache0, 0
+                for n in pieces:
+                    hit = np.array([not np.isfinite(x[b, t0:t0 + n]).all() or (c is not None and not np.isfinite(c[:, b] if gru else c[b]).all())
+                                    for b in range(B)])
+                    exact &= hit
+                    if head == "linear":
+                        rep_y[exact, t0:t0 + n] = True
+                    _, c = kws_oracle.forward(cfg, sd, x[:, t0:t0 + n], c, dtype=np.float64)
+                    t0 += n
+            if head != "linear":
+                rep_y[exact] = True                                           # (a pooled head: one output for all the pieces)
+            rep_c[(slice(None), exact) if gru else exact] = True
+            same_classes_and_values(y, ry, "repaired y: " + what, ya, rep_y)
+            same_classes_and_values(cache, rc, "repaired cache: " + what, ca, rep_c)
+            within_f16_bar(y, ry, "y: " + what, ~rep_y)
+            within_f16_bar(cache, rc, "cache: " + what, ~rep_c)
         assert np.isfinite(y[0]).all(), "utterance 0 carries no poison: " + what
