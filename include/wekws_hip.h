@@ -266,7 +266,11 @@ int wekws_hip_forward_status(wekws_hip_model* m, void* stream);
  *   y          device: (B, T, odim) for LINEAR / IDENTITY heads, (B, odim) for GLOBAL / LAST
  *   out_cache  device, same geometry as in_cache, or NULL if the caller does not need it;
  *              must not alias in_cache
- *   softmax    0: forward; 1: forward_softmax (softmax over the last axis, kws_model.py:89)
+ *   softmax    0: forward; 1: forward_softmax (softmax over the last axis, kws_model.py:89).
+ *              Non-finite logits as torch.softmax has them: a class whose logit is -Inf (a masked
+ *              class) gets exactly 0 and adds nothing to the other posteriors; a NaN or a +Inf
+ *              anywhere in a row, or -Inf in every class, makes every posterior of that row NaN.
+ *              Posteriors below float32's normal range (2^-126) may come out as 0.
  */
 int wekws_hip_forward(wekws_hip_model* m, const float* x, int B, int T, const float* in_cache,
                       float* y, float* out_cache, int softmax, void* stream);
@@ -353,6 +357,12 @@ int wekws_hip_dct_lifter(const float* logmel, int64_t rows, int num_bins, int nu
  *   logits (rows, K) device float32;  k in 1..8 (the reference uses 3)
  *   probs  (rows, k) device float32: the k largest softmax posteriors of each row, descending
  *   idx    (rows, k) device int32:   their column indices (equal values: lower index first; -1 if K < k)
+ * Non-finite logits: a class masked with -Inf adds nothing to the denominator and follows the same rule for equal
+ * values -- after the finite classes come the masked ones, probability 0, ascending index; they do not get -1, which is
+ * kept for slots that no class fills.  A NaN logit is never selected: it makes every probability of its row NaN (as
+ * torch.softmax does), the indices are those of the row's other classes in order, and slots left over -- fewer than k
+ * classes that are not NaN -- hold (-1, 0) like the padding for K < k.  A +Inf logit ranks first and makes the row's
+ * probabilities NaN; so does a row of -Inf alone (indices 0 .. k-1).  Indices are always in [0, K) or -1.
  */
 int wekws_hip_softmax_topk(const float* logits, int64_t rows, int K, int k, float* probs, int32_t* idx,
                            void* stream);

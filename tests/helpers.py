@@ -343,9 +343,48 @@ def tight_errors(cfg, y, c, ry, rc, softmax=False):
 # -> 8; one matrix entry x (1 + 2^-12), the largest of its column, shows as 15.1 at the least (128 x 128) in that column over three
 # rows or more.  The kernel computes its matrix itself (no table to perturb on the device), so this control is a CPU emulation alone.
 # GPU (tests/test_hip_mfcc_f64.py): at most 1.89 (the tail of Mfcc(80, 80) on the kernel's own log-mel; 1.31 on 2 x the grid's rows).
+#
+# K_SOFTMAX: softmax_rows_kernel (forward_softmax) and softmax_topk_kernel against oracle/topk_oracle.py::softmax_f64, per class in
+# the unit of softmax_units
+#     u = |got - p| / (eps p (1 + (m - l_i))),   eps = 2^-24, p the float64 posterior, m the row's maximum, l_i the class's logit
+# (relative to the posterior ITSELF -- the absolute bars, 1e-6 / 1e-4 / 2^-15, pass an all-zero tail and 8 % in every class of a
+# 2599-class row, whose typical posterior is 4e-4 -- plus the relative error (m - l_i) eps that one rounding of the exponent's
+# argument leaves in exp).  Classes first: finite / the exact zero of a masked (-Inf) class / NaN at the oracle's positions, or the
+# figure is infinite; a posterior below 2^-126 needs 0 <= got <= 2^-125 instead (at most 1 / 8 of a `deep/...` row, none elsewhere:
+# tests/test_softmax_matrix.py asserts it from the oracle alone).  The rule of K_FBANK: the smallest power of two at or above TWICE
+# the largest u of a plain float32 evaluation; the factor 2 is for the kernels' different but legitimate float32 order (per-lane
+# online rescaling, a 64-lane butterfly, the hardware exponential on a base-2 argument).
+# tests/test_softmax_matrix.py::test_k_softmax_is_twice_the_float32_evaluations asserts it.
+#   * CPU, every row of tests/softmax_matrix.py (389 rows, 2.7 M logits: K = 1 .. 10007, eleven finite laws, seven mask placements,
+#     NaN / +Inf rows):
+#       numpy float32 two-pass (pairwise sum)                  4.67  (gauss3/K256)
+#       ATen torch.softmax, float32                            9.26  (descending/K10007; with AVX512 kernels -- 13.9 with
+#                                                              ATEN_CPU_CAPABILITY=avx2 or default: the same power of two) -> 32
+#       the kernels' order, correctly rounded exp              5.35  (tests/softmax_matrix.py::kernel_order: inside K / 2, asserted)
+#       strictly serial single-accumulator float32 sum         107   (gauss3/K10007): a CORRECT evaluation that the bar rejects, by
+#                                                              design -- the bar separates summation orders.  Informational.
+#     Both plain evaluations have the oracle's classes on every row.
+#   * Negative controls, CPU emulations of the kernels' order with one defect (there is no device table to perturb), each on every
+#     row of the matrix row named for it, CONTROL_MARGIN = 1.5 asked (48):
+#       the K % 4 tail left out of the denominator             17,565 .. 19,804  (gauss0.1/K2599: 1.15e-3 relative; < 1e-6 absolute)
+#       one lane's sum added without its rescale to the max    7.7e6 .. 8.2e6    (gauss12/K300)
+#       the exponent's argument on a 2^-16 grid                118 .. 141        (gauss0.1/K2599)
+#   * GPU (tests/test_hip_softmax_f64.py, every row through both kernels; per (kernel, law) in the error report of a GPU run under
+#     softmax_f64/...):
+#       softmax_rows_kernel   at most 4.14 (descending/K10007; gauss3 4.02, ascending 3.22, every mask placement <= 3.05, deep 2.05)
+#       softmax_topk_kernel   at most 4.11 (descending/K10007; the same figures elsewhere: the worst class of a row is among its k best)
+#       the five ties to forward(softmax = 1), bit-identical, on their models' own logits: <= 2.71
+#     The hardware exponential on the rounded base-2 argument adds nothing the bar can see: the kernels sit BELOW the emulation
+#     of their order with a correctly rounded exp (5.35 on the CPU) and 7.7 x below the bar.  The factor the rule leaves is ATen's
+#     summation, not the kernels'.  tests/test_hip_topk.py under the added bar: its goldens, the 33,792-row call, 75 random shapes.
+#     NOT measured: the negative controls on the device (the kernels have no table to perturb; CPU emulations alone).
+#     The masked rows on the library BEFORE the guard (v == -Inf adds 0), softmax_topk through the C ABI, run once: 71 of the 95
+#     masked rows (mask_all left out) came back with NaN probabilities, 31 with other indices than the oracle's (masked classes
+#     were never ranked: -1).  softmax_rows_kernel of that library was not run on them: it has no entry point for chosen logits.
 CONTROL_MARGIN = 1.5
 K_FBANK = 16.0
 K_DCT = 8.0
+K_SOFTMAX = 32.0
 
 
 def pow2_at_or_above(v):

@@ -778,7 +778,8 @@ __global__ __launch_bounds__(kThreads, 2) void conv_stack_kernel(const StackPara
 
 // Row softmax over the last axis (KWSModel.forward_softmax, kws_model.py:89): one wave per row, two passes over the
 // row -- online (max, rescaled sum) with 16-byte loads through a 4-byte-aligned type (rows of an odd-width matrix are
-// only dword aligned), then normalise in place.
+// only dword aligned), then normalise in place.  Non-finite logits as torch.softmax has them: a class masked with -Inf
+// adds nothing and gets 0; a NaN or +Inf anywhere, or -Inf everywhere, makes the whole row NaN.
 static __global__ __attribute__((unused)) void softmax_rows_kernel(float* y, int64_t rows, int K) {
   const int64_t row = int64_t(blockIdx.x) * (blockDim.x / 64) + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -788,6 +789,7 @@ static __global__ __attribute__((unused)) void softmax_rows_kernel(float* y, int
   const int K4 = K & ~3;
   float mx = -INFINITY, s = 0.f;
   auto take = [&](float v) __attribute__((always_inline)) {
+    if (v == -INFINITY) return;                              // a masked class adds 0 (mx - v would be Inf - Inf while mx is -Inf)
     if (v > mx) { s *= __expf(mx - v); mx = v; }
     s += __expf(v - mx);
   };
@@ -799,7 +801,8 @@ static __global__ __attribute__((unused)) void softmax_rows_kernel(float* y, int
   if (K4 + lane < K) take(p[K4 + lane]);
   float gm = mx;
   for (int off = 32; off > 0; off >>= 1) gm = fmaxf(gm, __shfl_xor(gm, off));
-  float gs = (mx == -INFINITY) ? 0.f : s * __expf(mx - gm);
+  // (a lane without a finite class keeps mx = -Inf: its s is 0, or NaN if it saw a NaN, and goes in as it is)
+  float gs = (mx == -INFINITY) ? s : s * __expf(mx - gm);
   for (int off = 32; off > 0; off >>= 1) gs += __shfl_xor(gs, off);
   const float inv = 1.0f / gs;
   for (int k = lane * 4; k < K4; k += 256) {
@@ -809,6 +812,11 @@ static __global__ __attribute__((unused)) void softmax_rows_kernel(float* y, int
     *reinterpret_cast<V4*>(p + k) = q;
   }
   if (K4 + lane < K) p[K4 + lane] = __expf(p[K4 + lane] - gm) * inv;
+}
+// the one launch statement of softmax_rows_kernel: four rows (waves) per workgroup
+static inline __attribute__((unused)) bool launch_softmax_rows(float* y, int64_t rows, int K, hipStream_t stream) {
+  hipLaunchKernelGGL(softmax_rows_kernel, dim3(unsigned((rows + 3) / 4)), dim3(256), 0, stream, y, rows, K);
+  return hipGetLastError() == hipSuccess;
 }
 
 // Runs the conv_stack route of a KIND backbone with C channels.  Defined below, instantiated once per KIND in

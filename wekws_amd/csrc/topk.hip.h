@@ -4,6 +4,9 @@
 // logits, exp(l - max) / sum.  One wave per row: every lane keeps the running maximum, the rescaled sum of exponentials
 // and its own k best (value, index) over a strided slice, then k rounds of a wave-wide arg-max (ties -> lower index)
 // pop the winners.  HBM-bound: the logits are read exactly once, 8 k bytes per row are written.
+// Non-finite logits (include/wekws_hip.h states the contract): classes masked with -Inf add nothing to the denominator and
+// rank after every finite class, probability 0, ascending index; a NaN logit is never selected and makes every probability
+// of its row NaN, as +Inf does (which ranks first); a row of -Inf alone is NaN too.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,13 +28,17 @@ __global__ __launch_bounds__(256) void softmax_topk_kernel(const float* __restri
   for (int j = 0; j < KK; ++j) { bv[j] = -INFINITY; bi[j] = 0x7fffffff; }
   float mx = -INFINITY, sum = 0.f;
   auto take = [&](float v, int k) __attribute__((always_inline)) {
-    if (v > mx) { sum *= __expf(mx - v); mx = v; }           // online softmax denominator
-    sum += __expf(v - mx);
-    if (v > bv[KK - 1]) {                                    // insert into the lane's sorted k best (indices ascend
-      bv[KK - 1] = v; bi[KK - 1] = k;                        // within a lane, so strict > keeps the lower index first)
+    if (v != -INFINITY) {                                    // online softmax denominator; a masked class adds 0
+      if (v > mx) { sum *= __expf(mx - v); mx = v; }         // (mx - v would be Inf - Inf while mx is -Inf)
+      sum += __expf(v - mx);
+    }
+    // insert into the lane's k best, sorted by (value descending, index ascending).  Indices ascend within a lane, so among
+    // equal values the newcomer comes last -- except before an empty slot (-Inf, 0x7fffffff), which a masked class displaces
+    if (v > bv[KK - 1] || (v == bv[KK - 1] && k < bi[KK - 1])) {
+      bv[KK - 1] = v; bi[KK - 1] = k;
 #pragma unroll
       for (int j = KK - 1; j > 0; --j)
-        if (bv[j] > bv[j - 1]) {
+        if (bv[j] > bv[j - 1] || (bv[j] == bv[j - 1] && bi[j] < bi[j - 1])) {
           const float tv = bv[j]; bv[j] = bv[j - 1]; bv[j - 1] = tv;
           const int ti = bi[j]; bi[j] = bi[j - 1]; bi[j - 1] = ti;
         }
@@ -50,7 +57,8 @@ __global__ __launch_bounds__(256) void softmax_topk_kernel(const float* __restri
   // wave-wide maximum and denominator
   float gm = mx;
   for (int off = 32; off > 0; off >>= 1) gm = fmaxf(gm, __shfl_xor(gm, off));
-  float gs = (mx == -INFINITY) ? 0.f : sum * __expf(mx - gm);
+  // (a lane without a finite class keeps mx = -Inf: its sum is 0, or NaN if it saw a NaN, and goes in as it is)
+  float gs = (mx == -INFINITY) ? sum : sum * __expf(mx - gm);
   for (int off = 32; off > 0; off >>= 1) gs += __shfl_xor(gs, off);
   const float inv = 1.0f / gs;
   // k rounds: arg-max over the lanes' current heads, the winning lane pops its head

@@ -1240,8 +1240,7 @@ int wekws_hip_forward(wekws_hip_model* m, const float* x, int B, int T, const fl
   if (softmax || d.activation == WEKWS_HIP_ACT_SOFTMAX) {
     const int64_t rows = per_frame ? int64_t(B) * T : B;
     const int K = d.odim;
-    hipLaunchKernelGGL(wekws::softmax_rows_kernel, dim3(unsigned((rows + 3) / 4)), dim3(256), 0, stream, y, rows, K);
-    if (hipGetLastError() != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "softmax launch failed");
+    if (!wekws::launch_softmax_rows(y, rows, K, stream)) return fail(WEKWS_HIP_EDEVICE, "softmax launch failed");
   }
   return WEKWS_HIP_OK;
 }

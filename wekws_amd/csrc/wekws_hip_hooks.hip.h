@@ -1,6 +1,6 @@
 // The test hooks of libwekws_hip_hooks.so (make hooks: wekws_hip.hip compiled with -DWEKWS_TEST_HOOKS, which includes this file):
 // the route trace of a forward, the routing functions of route.h without a device, the GRU epoch, a CU hog, the fbank's plan and
-// table.  Not part of the ABI in include/wekws_hip.h: the product library exports nothing outside the header.
+// table, the row softmax on chosen logits.  Not part of the ABI in include/wekws_hip.h: the product library exports nothing outside the header.
 #pragma once
 
 struct RouteTrace {
@@ -243,5 +243,15 @@ extern "C" int wekws_hip_debug_fbank_tables(wekws_hip_fbank* f, float* host_buf,
             : hipMemcpy(host_buf, f->d_tables, size_t(n) * sizeof(float), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "fbank tables: %s", hipGetErrorString(e));
+  return WEKWS_HIP_OK;
+}
+
+// --------------------------------------------- softmax ---------------------------------------------
+// softmax_rows_kernel in place on y (rows, K), through the launch statement wekws_hip_forward uses for forward_softmax: a test
+// reaches the kernel with logits of its choice (tests/test_hip_softmax_f64.py) instead of the ones a model happens to produce.
+extern "C" int wekws_hip_debug_softmax_rows(float* y, int64_t rows, int K, void* stream_) {
+  if (!y || rows < 0 || K <= 0 || (rows + 3) / 4 > 0x7fffffffLL) return fail(WEKWS_HIP_EINVAL, "softmax_rows: rows=%lld K=%d", (long long)rows, K);
+  if (rows == 0) return WEKWS_HIP_OK;
+  if (!wekws::launch_softmax_rows(y, rows, K, static_cast<hipStream_t>(stream_))) return fail(WEKWS_HIP_EDEVICE, "softmax launch failed");
   return WEKWS_HIP_OK;
 }
