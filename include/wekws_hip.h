@@ -468,6 +468,66 @@ int wekws_hip_ctc_kws_read_beam(void* h, int id, void* out, void* stream);
 /* The stream's sticky status (0 or WEKWS_HIP_E*) into *status_out; synchronises `stream`. */
 int wekws_hip_ctc_kws_status(void* h, int id, int32_t* status_out, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * Streaming front end  --  the part of the streaming KeyWordSpotter that runs BEFORE the model, for many streams at once:
+ *   wekws/bin/stream_kws_ctc.py:335-398 accept_wave: the samples left over from the last chunk (wave_remained), Kaldi fbank
+ *   of (leftover + chunk), the last left + right feature frames for the context expansion (feature_remained) and the
+ *   frame-skip phase (feats_ctx_offset), carried per stream.
+ * int16 chunks of B streams go in, each row's new feature rows come out; a push is two launches (one without context and
+ * skip), no sample or feature crosses to the host.  Per stream, with L = frame_length, S = frame_shift, l / r the context,
+ * ds the skip and the state (rem, fr, off), a push of n samples:
+ *   1. tot = rem + n < L r: every sample is kept and the row is HELD (the reference's None)            (:348-351)
+ *   2. nf = 0 if tot < L else 1 + (tot - L) / S frames over [leftover | chunk]; rem' = tot - nf S       (:354-364)
+ *      -- frame k of a stream is always samples [k S, k S + L) of its whole signal, and equals wekws_hip_fbank_compute_i16
+ *      of those samples bit for bit (the kernels share the arithmetic)
+ *   3. context: the reference asserts nf > r (EINVAL here); pad = l copies of the first new frame + the new frames on the
+ *      stream's first processed chunk, else the remembered frames + the new ones; len(pad) - 2 r rows, row i = pad[i : i + l +
+ *      r + 1]; fr' = the last l + r of the NEW frames only (after a chunk of fewer frames the next chunk's windows start
+ *      late, as in the reference: reproduced, not judged)                                              (:366-390)
+ *   4. skip: rows off, off + ds, ... of the k rows of step 3; off' = (off - k) mod ds                   (:391-397)
+ * Context is either off (left = right = 0) or left == right >= 1: anything else is refused at creation (the reference raises
+ * inside its window loop for left > right and silently drops right - left frames per chunk for left < right: INTEGRATION.md).
+ * ------------------------------------------------------------------------------------------*/
+typedef struct wekws_hip_stream_frontend_cfg {
+  wekws_hip_fbank_cfg fbank; /* as for wekws_hip_fbank_create; frame_shift <= frame_length */
+  int32_t left, right;       /* context: 0 / 0, or left == right >= 1 */
+  int32_t skip;              /* >= 1 */
+  int32_t max_streams;       /* stream ids 0 .. max_streams - 1 */
+  int32_t max_chunk;         /* largest nmax of a push: sizes the fresh-frame workspace, so no push allocates or synchronises */
+  int32_t device;
+  int32_t reserved[2];
+} wekws_hip_stream_frontend_cfg;
+
+int wekws_hip_stream_frontend_create(const wekws_hip_stream_frontend_cfg* cfg, void** out);
+void wekws_hip_stream_frontend_destroy(void* h);
+/* The plan of one push for one stream, on the host alone (no device, no handle): counts_in = {rem, fr (-1 = none yet), off},
+ * plan_out = {status, held, nf, rem_out, pad_first, fr_in, rows_ctx, rows_out, fr_out, off_out}.  Returns EINVAL for a
+ * configuration or counts that no stream can have; a computed plan returns 0 and carries in status WEKWS_HIP_EINVAL where
+ * the reference would trip its assertion (step 3).  This is the function push decides every row with. */
+int wekws_hip_stream_frontend_plan(const wekws_hip_stream_frontend_cfg* cfg, const int32_t counts_in[3], int nsamp,
+                                   int32_t plan_out[10]);
+/* A row capacity Tcap that always suffices for chunks of up to nmax samples, whatever the streams hold. */
+int wekws_hip_stream_frontend_max_frames(void* h, int nmax);
+/*
+ * pcm         (B, nmax) device int16, as the reference receives it; row b continues stream stream_ids[b] with its first
+ *             nsamp[b] samples (0 .. nmax)
+ * stream_ids  (B) HOST int32, distinct, any subset in any order;  nsamp (B) HOST int32
+ * feats       (B, Tcap, D) device float32, D = num_bins without context, else (left + right + 1) * num_bins; row b receives
+ *             its frames[b] rows, the rest of the row is left as it was
+ * frames      (B) HOST int32 out: rows of each stream; -1 = held, 0 = the reference's empty result (no model call)
+ * The whole call is planned on the host first: a bad or repeated stream id, nsamp[b] outside 0 .. nmax, nmax > max_chunk,
+ * Tcap too small for a row, or a row where the reference would assert returns WEKWS_HIP_EINVAL, launches nothing and changes
+ * no stream.  Pushes may be queued back to back on `stream` without a synchronise (the per-row plan travels in stream
+ * order through a ring of pinned tables; not inside a stream capture).  Calls on one handle are serialised by a mutex and by
+ * the caller's stream: use one stream per handle.
+ */
+int wekws_hip_stream_frontend_push(void* h, const int16_t* pcm, int B, int nmax, const int32_t* stream_ids, const int32_t* nsamp,
+                                   float* feats, int Tcap, int32_t* frames, void* stream);
+/* The n streams in ids (HOST int32) start over: no leftover, no remembered frames (the first-chunk pad comes back), phase 0. */
+int wekws_hip_stream_frontend_reset(void* h, const int32_t* ids, int n);
+/* counts_out = {rem, fr (-1 = none), off, rows delivered since creation / reset} of stream id. */
+int wekws_hip_stream_frontend_counts(void* h, int id, int32_t counts_out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,7 @@
 """Secondary measurements for the other BASELINE.json configs (one JSON line each, not the bench.py contract):
 batch throughput of every backbone, streaming per-frame latency (B=1, 10-frame chunks, carried cache), fbank
 front-end throughput.  GPU only.   python tools/bench_configs.py > gpurun_out/configs.jsonl"""
+# (also: the streaming front end, filter `stream_frontend`)
 import json
 import os
 import sys
@@ -195,6 +196,40 @@ def main():
             ms = (time.perf_counter() - t0) / n * 1e3
             out.append(dict(kind="pcie", mode=label, model="ds_tcn_h256", B=B, ms=round(ms, 4),
                             utts_per_s=round(B / ms * 1e3, 1), h2d_GBs=round(B * T * 40 * 4 / ms / 1e6, 1)))
+            print(json.dumps(out[-1]), flush=True)
+    # streaming front end: 4096 streams in steady state, 4800-sample chunks (30 frames per push) -- time per push of the front end
+    # alone, of PCM -> detection (front end -> fsmn_ctc300 with carried caches -> CTC decoder), and in the same run the one-shot
+    # Fbank + splice_skip on the same rows x frames held as whole signals (30 frames = 5040 samples)
+    if only in "stream_frontend":
+        from wekws_amd.frontend import StreamingFrontEnd, splice_skip
+        from wekws_amd.stream import BatchedKeyWordSpotter
+        B, n = 4096, 4800
+        g = torch.Generator(device="cuda").manual_seed(7)
+        chunk = torch.randint(-20000, 20000, (B, n), device="cuda", generator=g, dtype=torch.int32).to(torch.int16)
+        whole = torch.randint(-20000, 20000, (B, 400 + 29 * 160), device="cuda", generator=g, dtype=torch.int32).to(torch.int16)
+        for label, bins, window, left, right, skip in (("80/povey/(2,2)/skip3", 80, "povey", 2, 2, 3),
+                                                       ("40/hamming/no context", 40, "hamming", 0, 0, 1)):
+            fe = StreamingFrontEnd(B, bins, window, left, right, skip, max_chunk=n)
+            buf = torch.zeros((B, fe.max_frames(n), fe.feat_dim), device="cuda")
+            frames = fe.push(chunk, out=buf)[1]
+            frames = fe.push(chunk, out=buf)[1]                     # steady state: every stream holds its leftover and frames
+            med, p10, p90 = timeit(lambda: fe.push(chunk, out=buf), reps=10, group=10)
+            fb1 = Fbank(bins, window=window)
+            one = (lambda: splice_skip(fb1(whole), left, right, skip)) if (left or skip > 1) else (lambda: fb1(whole))
+            omed, op10, op90 = timeit(one, reps=10, group=10)
+            row = dict(kind="stream_frontend", config=label, B=B, chunk=n, frames_per_push=int(frames[0]), ms_push=round(med, 4),
+                       p10=round(p10, 4), p90=round(p90, 4), ms_oneshot_same_frames=round(omed, 4), oneshot_p10=round(op10, 4),
+                       oneshot_p90=round(op90, 4), push_over_oneshot=round(med / omed, 3),
+                       chunks_per_s=round(B / med * 1e3, 1))
+            if left:
+                _, m = build("fsmn_ctc300")
+                kws = BatchedKeyWordSpotter(m, {"k0": (1, 2, 3)}, 0.5, B, num_bins=bins, window=window, left=left, right=right,
+                                            skip=skip, max_chunk=n)
+                kws.forward(chunk)
+                dmed, dp10, dp90 = timeit(lambda: kws.forward(chunk), warm=2, reps=5, group=4)
+                row.update(ms_pcm_to_detection=round(dmed, 4), detection_p10=round(dp10, 4), detection_p90=round(dp90, 4),
+                           model="fsmn_ctc300")
+            out.append(row)
             print(json.dumps(out[-1]), flush=True)
     fb = Fbank(40)
     for B in ((1024, 8192) if only in "fbank" else ()):

@@ -34,6 +34,11 @@ class CtcKwsDesc(C.Structure):
                 ("prefix_capacity", C.c_int32), ("device", C.c_int32), ("threshold", C.c_double)]
 
 
+class StreamFrontendCfg(C.Structure):
+    _fields_ = [("fbank", FbankCfg)] + [(n, C.c_int32) for n in ("left", "right", "skip", "max_streams", "max_chunk", "device")] + \
+               [("reserved", C.c_int32 * 2)]
+
+
 class CtcKwsResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("status", "valid", "state", "keyword", "start", "end")] + [("score", C.c_double)]
 
@@ -83,6 +88,14 @@ SIGNATURES = {
     "wekws_hip_ctc_kws_beam_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "wekws_hip_ctc_kws_read_beam": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "wekws_hip_ctc_kws_status": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p]),
+    "wekws_hip_stream_frontend_create": (C.c_int, [C.POINTER(StreamFrontendCfg), C.POINTER(C.c_void_p)]),
+    "wekws_hip_stream_frontend_destroy": (None, [C.c_void_p]),
+    "wekws_hip_stream_frontend_plan": (C.c_int, [C.POINTER(StreamFrontendCfg), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]),
+    "wekws_hip_stream_frontend_max_frames": (C.c_int, [C.c_void_p, C.c_int]),
+    "wekws_hip_stream_frontend_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int, C.c_void_p, C.c_void_p]),
+    "wekws_hip_stream_frontend_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "wekws_hip_stream_frontend_counts": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
 }
 
 OPTIONS = {"w16": 0, "mdtc16": 1, "stream": 2, "mm": 3, "head_slices": 4, "g16": 5, "envelope": 6, "gru_pipe": 7}   # enum wekws_hip_option

@@ -331,6 +331,218 @@ __host__ __device__ inline bool fbank_pair_ok(int nsamp, int frame_shift, int fr
   return (nsamp % 2 == 0) && (frame_shift % 2 == 0) && (frame_length % 2 == 0) && (reinterpret_cast<uintptr_t>(pcm) % (2 * sizeof(S)) == 0);
 }
 
+// Per-lane constants of a whole launch (registers): the window of the lane's 8 samples, the stage and untangle twiddles, its mel
+// slots, the strip positions of its FFT elements.  One set for fbank_kernel and for the streaming kernel (stream_frontend.hip.h).
+template <int ROUNDS>
+struct FbankLane {
+  float wn[8];
+  fb_f2 tws[3][3];                                          // stages 0..2: w^j, w^2j, w^3j of the stage's block size
+  fb_f2 twh[2];                                             // untangle twiddles of bins lane, lane + 64: u = -i w^k / 2 (exact); bins + 128: -i u
+  int sfirst[ROUNDS], sbin[ROUNDS], scount[ROUNDS];          // scount: slots of the filter if this slot is its first, else 0
+  float sw[ROUNDS][16];
+  int zpos[4][4];                                            // stage st exchanges elements base + k q (k = 0..3); stage 3 writes natural order
+  int zout[4], unpos[4];
+  __device__ __forceinline__ void init(const FbankParams& P, int lane) {
+    const float* __restrict__ tab = P.tables;
+    const float2* tw256 = reinterpret_cast<const float2*>(tab);
+    const float2* tw512 = reinterpret_cast<const float2*>(tab + 512);
+    const float* win = tab + 1024;
+    // ---- per-lane constants of the whole launch (registers): window of its 8 samples, stage twiddles, untangle twiddles,
+    //      scatter targets of its 4 FFT bins
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int n = lane + 64 * m;
+      wn[2 * m] = win[2 * n];
+      wn[2 * m + 1] = win[2 * n + 1];
+    }
+#pragma unroll
+    for (int st = 0; st < 3; ++st) {
+      const int q = 64 >> (2 * st), L = 4 * q, j = lane % q, tstep = 256 / L;
+#pragma unroll
+      for (int r = 1; r <= 3; ++r) {
+        const float2 t = tw256[(r * j * tstep) & 255];
+        tws[st][r - 1] = fb_f2{t.x, t.y};
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const float2 t = tw512[lane + 64 * m];
+      twh[m] = fb_f2{0.5f * t.y, -0.5f * t.x};
+    }
+    // mel slots of this lane: first FFT bin, mel bin, 16 weights (zero padded)
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+      const int slot = lane + 64 * r;
+      const bool ok = slot < P.nslots;
+      sfirst[r] = ok ? int(tab[P.slot_first_off + slot]) : 0;
+      sbin[r] = ok ? int(tab[P.slot_bin_off + slot]) : -1;
+      scount[r] = 0;
+      if (ok && (slot == 0 || int(tab[P.slot_bin_off + slot - 1]) != sbin[r])) {
+        int n = 1;
+        while (slot + n < P.nslots && int(tab[P.slot_bin_off + slot + n]) == sbin[r]) ++n;
+        scount[r] = n;
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u) sw[r][u] = ok ? tab[P.slot_w_off + slot * 16 + u] : 0.f;
+    }
+    // where the last stage puts its four outputs: X[64 m + rev3(lane)], natural order
+    const int rev3 = ((lane & 3) << 4) | (lane & 12) | (lane >> 4);
+    // Round 6: the swizzled strip positions of a lane are the same for every frame -- computed ONCE and held (made opaque, or the
+    // compiler re-derives them per frame: ~100 of the ~320 vector instructions of a frame were this address arithmetic).
+#pragma unroll
+    for (int st = 0; st < 4; ++st) {
+      const int q = 64 >> (2 * st), blk = lane / q, j = lane - blk * q, base = blk * 4 * q + j;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        zpos[st][k] = pz(base + k * q);
+        asm volatile("" : "+v"(zpos[st][k]));
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      zout[m] = pz(64 * m + rev3);
+      unpos[m] = pz((256 - (lane + 64 * m)) & 255);
+      asm volatile("" : "+v"(zout[m]), "+v"(unpos[m]));
+    }
+  }
+};
+
+// The arithmetic of FW frames of one wave, from the DC removal to the logarithm: vn holds the frames' sample pairs (lane l:
+// pairs l + 64 m), `prefetch` is called once the pairs are copied out (it may refill vn with the wave's next frames: their loads
+// then fly under this transform), `dst(w, row)` says whether frame w is stored and where its num_bins floats go.  Only the fetch
+// and the store address belong to the caller: every kernel that calls this computes the same bits for the same samples.
+template <int ROUNDS, int FW, typename Prefetch, typename Dst>
+__device__ __forceinline__ void fbank_frames(const FbankLane<ROUNDS>& K, float* const strip, const int lane, const float inv_fl,
+                                             float2 (&vn)[FW][4], Prefetch prefetch, Dst dst) {
+  const auto& wn = K.wn; const auto& tws = K.tws; const auto& twh = K.twh;
+  const auto& sfirst = K.sfirst; const auto& sbin = K.sbin; const auto& scount = K.scount; const auto& sw = K.sw;
+  const auto& zpos = K.zpos; const auto& zout = K.zout; const auto& unpos = K.unpos;
+  const int (&upos)[4] = zpos[0];                           // (stage 0 writes elements lane + 64 k: the untangle's own bins)
+  // ---- DC removal (fbank.h:155-160)
+  float2 v[FW][4];
+  float mean[FW];
+#pragma unroll
+  for (int w = 0; w < FW; ++w) {
+    float s = 0.f;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      v[w][m] = vn[w][m];
+      s += v[w][m].x + v[w][m].y;
+    }
+    mean[w] = s;
+  }
+  prefetch();
+#pragma unroll
+  for (int w = 0; w < FW; ++w) mean[w] = fb_wave_sum(mean[w]);
+  // ---- pre-emphasis 0.97 (fbank.h:122-127: y[i] = x[i] - 0.97 x[i-1], y[0] = x[0] - 0.97 x[0]), window
+  //      (fbank.h:130-135).  x[2n-1] is the odd sample of element n-1: the lane below (lane 0: lane 63 of m-1)
+  float2 a[FW][4];
+#pragma unroll
+  for (int w = 0; w < FW; ++w) {
+    const float mu = mean[w] * inv_fl;   // (one rounding away from the quotient; the sum's order differs from the reference's serial one anyway)
+    // (no range masks: samples past the frame were fetched as zeros and their window values ARE zero -- whatever the
+    //  mean subtraction and the pre-emphasis make of them is multiplied away; round 3 spent 27 selects per frame on them)
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const float xe = v[w][m].x - mu;
+      const float xo = v[w][m].y - mu;
+      float prev = fb_dppx<0x138, 0xf, true>(xo);                           // wave_shr:1: odd sample of element n - 1
+      if (m > 0) {
+        const float top = v[w][m - 1].y - mu;                                // lane 0: lane 63 of the row of elements before
+        const float wrap = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, top), 63));
+        prev = lane == 0 ? wrap : prev;
+      } else {
+        prev = lane == 0 ? xe : prev;                                       // i = 0: its own value
+      }
+      a[w][m].x = (xe - 0.97f * prev) * wn[2 * m];
+      a[w][m].y = (xo - 0.97f * xe) * wn[2 * m + 1];
+    }
+  }
+  // ---- 256-point complex FFT, radix-4 DIF, 4 stages (stage st exchanges elements q = 64 >> 2 st apart)
+#pragma unroll
+  for (int st = 0; st < 4; ++st) {
+#pragma unroll
+    for (int w = 0; w < FW; ++w) {
+      fb_f2* const z = reinterpret_cast<fb_f2*>(strip + w * kFbankStrip);
+      fb_f2 a0, a1, a2, a3, o0, o1, o2, o3;
+      if (st > 0) {
+        a0 = z[zpos[st][0]]; a1 = z[zpos[st][1]]; a2 = z[zpos[st][2]]; a3 = z[zpos[st][3]];
+      } else {
+        a0 = fb_f2{a[w][0].x, a[w][0].y}; a1 = fb_f2{a[w][1].x, a[w][1].y};
+        a2 = fb_f2{a[w][2].x, a[w][2].y}; a3 = fb_f2{a[w][3].x, a[w][3].y};
+      }
+      if (st < 3) {
+        fb_bfly<true>(a0, a1, a2, a3, tws[st][0], tws[st][1], tws[st][2], o0, o1, o2, o3);
+        z[zpos[st][0]] = o0; z[zpos[st][1]] = o1; z[zpos[st][2]] = o2; z[zpos[st][3]] = o3;
+      } else {
+        // positions 4 lane + m hold X[rev4(4 lane + m)] = X[64 m + rev3(lane)]: stored in natural order
+        fb_bfly<false>(a0, a1, a2, a3, a0, a0, a0, o0, o1, o2, o3);
+        z[zout[0]] = o0; z[zout[1]] = o1; z[zout[2]] = o2; z[zout[3]] = o3;
+      }
+    }
+    wave_sync();
+  }
+  // ---- real-FFT untangle + power (fbank.h:173-175)
+  float pw[FW][4];
+#pragma unroll
+  for (int w = 0; w < FW; ++w) {
+    const fb_f2* const z = reinterpret_cast<const fb_f2*>(strip + w * kFbankStrip);
+#pragma unroll
+    for (int m = 0; m < 4; m += 2) {
+      fb_f2 xa, xb;
+      if (m == 0) fb_untangle2<false>(z[upos[0]], z[unpos[0]], twh[0], z[upos[1]], z[unpos[1]], twh[1], xa, xb);
+      else fb_untangle2<true>(z[upos[2]], z[unpos[2]], twh[0], z[upos[3]], z[unpos[3]], twh[1], xa, xb);
+      pw[w][m] = xa.x * xa.x + xa.y * xa.y;
+      pw[w][m + 1] = xb.x * xb.x + xb.y * xb.y;
+    }
+  }
+  wave_sync();                                          // every lane has read its Z values: the strips are free
+#pragma unroll
+  for (int w = 0; w < FW; ++w) {
+    float* const pwr = strip + w * kFbankStrip;            // 256 power bins (+ 16 zeros of slack for the padded slots)
+#pragma unroll
+    for (int m = 0; m < 4; ++m) pwr[lane + 64 * m] = pw[w][m];
+    if (lane < 16) pwr[256 + lane] = 0.f;
+  }
+  wave_sync();
+  // ---- mel (fbank.h:179-186): one slot per lane and round, ascending k, then the slots of a filter in order
+#pragma unroll
+  for (int w = 0; w < FW; ++w) {
+    const float* const pwr = strip + w * kFbankStrip;
+    float* const melacc = strip + w * kFbankStrip + 512;
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+      float e = 0.f;
+#pragma unroll
+      for (int u = 0; u < 16; ++u) e = fmaf(sw[r][u], pwr[sfirst[r] + u], e);
+      melacc[lane + 64 * r] = e;                            // slot sums (slots past nslots: 0)
+    }
+  }
+  wave_sync();
+  // ---- log (fbank.h:187-190), store.  Slots are sorted by filter: a filter's slots are neighbours.
+#pragma unroll
+  for (int w = 0; w < FW; ++w) {
+    float* row;
+    if (dst(w, row)) {
+      const float* const melacc = strip + w * kFbankStrip + 512;
+#pragma unroll
+      for (int r = 0; r < ROUNDS; ++r) {
+        const int slot = lane + 64 * r;
+        if (scount[r] > 0) {
+          float e = melacc[slot];
+          for (int n = 1; n < scount[r]; ++n) e += melacc[slot + n];
+#ifdef WEKWS_FBANK_FASTLOG
+          row[sbin[r]] = __logf(fmaxf(e, FLT_EPSILON));
+#else
+          row[sbin[r]] = fb_logf(fmaxf(e, FLT_EPSILON));
+#endif
+        }
+      }
+    }
+  }
+  wave_sync();
+}
+
 // ROUNDS == 3 (129 .. 192 slots) has not been found REACHABLE through wekws_hip_fbank_create: over 16 sample rates from 2 to 96 kHz
 // (the usual audio rates, not every integer rate), every bin count 1 .. 128 and the three transform lengths that frames of 65 .. 512
 // samples select, no bank without an empty filter has more than 128 slots (tests/test_fbank_matrix.py sweeps fbank_build_tables and
@@ -343,78 +555,11 @@ __global__ __launch_bounds__(64 * kFbankWaves, ROUNDS == 2 ? 4 : 1) void fbank_k
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   float* const strip = lds + wave * FW * kFbankStrip;       // [FW] strips of this wave
-  const float* __restrict__ tab = P.tables;
-  const float2* tw256 = reinterpret_cast<const float2*>(tab);
-  const float2* tw512 = reinterpret_cast<const float2*>(tab + 512);
-  const float* win = tab + 1024;
   const int FL = P.frame_length;
   const float inv_fl = 1.f / float(FL);
 
-  // ---- per-lane constants of the whole launch (registers): window of its 8 samples, stage twiddles, untangle twiddles,
-  //      scatter targets of its 4 FFT bins
-  float wn[8];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int n = lane + 64 * m;
-    wn[2 * m] = win[2 * n];
-    wn[2 * m + 1] = win[2 * n + 1];
-  }
-  fb_f2 tws[3][3];                                          // stages 0..2: w^j, w^2j, w^3j of the stage's block size
-#pragma unroll
-  for (int st = 0; st < 3; ++st) {
-    const int q = 64 >> (2 * st), L = 4 * q, j = lane % q, tstep = 256 / L;
-#pragma unroll
-    for (int r = 1; r <= 3; ++r) {
-      const float2 t = tw256[(r * j * tstep) & 255];
-      tws[st][r - 1] = fb_f2{t.x, t.y};
-    }
-  }
-  fb_f2 twh[2];                                             // untangle twiddles of bins lane, lane + 64: u = -i w^k / 2 (exact); bins + 128: -i u
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const float2 t = tw512[lane + 64 * m];
-    twh[m] = fb_f2{0.5f * t.y, -0.5f * t.x};
-  }
-  // mel slots of this lane: first FFT bin, mel bin, 16 weights (zero padded)
-  int sfirst[ROUNDS], sbin[ROUNDS], scount[ROUNDS];          // scount: slots of the filter if this slot is its first, else 0
-  float sw[ROUNDS][16];
-#pragma unroll
-  for (int r = 0; r < ROUNDS; ++r) {
-    const int slot = lane + 64 * r;
-    const bool ok = slot < P.nslots;
-    sfirst[r] = ok ? int(tab[P.slot_first_off + slot]) : 0;
-    sbin[r] = ok ? int(tab[P.slot_bin_off + slot]) : -1;
-    scount[r] = 0;
-    if (ok && (slot == 0 || int(tab[P.slot_bin_off + slot - 1]) != sbin[r])) {
-      int n = 1;
-      while (slot + n < P.nslots && int(tab[P.slot_bin_off + slot + n]) == sbin[r]) ++n;
-      scount[r] = n;
-    }
-#pragma unroll
-    for (int u = 0; u < 16; ++u) sw[r][u] = ok ? tab[P.slot_w_off + slot * 16 + u] : 0.f;
-  }
-  // where the last stage puts its four outputs: X[64 m + rev3(lane)], natural order
-  const int rev3 = ((lane & 3) << 4) | (lane & 12) | (lane >> 4);
-  // Round 6: the swizzled strip positions of a lane are the same for every frame -- computed ONCE and held (made opaque, or the
-  // compiler re-derives them per frame: ~100 of the ~320 vector instructions of a frame were this address arithmetic).
-  int zpos[4][4];                                            // stage st exchanges elements base + k q (k = 0..3); stage 3 writes natural order
-#pragma unroll
-  for (int st = 0; st < 4; ++st) {
-    const int q = 64 >> (2 * st), blk = lane / q, j = lane - blk * q, base = blk * 4 * q + j;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      zpos[st][k] = pz(base + k * q);
-      asm volatile("" : "+v"(zpos[st][k]));
-    }
-  }
-  int zout[4], unpos[4];
-  const int (&upos)[4] = zpos[0];                           // (stage 0 writes elements lane + 64 k: the untangle's own bins)
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    zout[m] = pz(64 * m + rev3);
-    unpos[m] = pz((256 - (lane + 64 * m)) & 255);
-    asm volatile("" : "+v"(zout[m]), "+v"(unpos[m]));
-  }
+  FbankLane<ROUNDS> K;
+  K.init(P, lane);
 
   // Frame g of the launch is frame g % nframes of utterance g / nframes.  The wave walks g = g0, g0 + stride, ...: the pair
   // (utterance, frame) is carried and advanced by (stride / nframes, stride % nframes) with a carry -- round 3 divided a
@@ -470,131 +615,14 @@ __global__ __launch_bounds__(64 * kFbankWaves, ROUNDS == 2 ? 4 : 1) void fbank_k
     // (utterance, frame) of the wave's next first frame
     int nb = ub + sq, nfr = ufr + sr;
     if (nfr >= nframes) { nfr -= nframes; ++nb; }
-    // ---- DC removal (fbank.h:155-160)
-    float2 v[FW][4];
-    float mean[FW];
-#pragma unroll
-    for (int w = 0; w < FW; ++w) {
-      float s = 0.f;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        v[w][m] = vn[w][m];
-        s += v[w][m].x + v[w][m].y;
-      }
-      mean[w] = s;
-    }
-    fetch(nb, nfr);
-#pragma unroll
-    for (int w = 0; w < FW; ++w) mean[w] = fb_wave_sum(mean[w]);
-    // ---- pre-emphasis 0.97 (fbank.h:122-127: y[i] = x[i] - 0.97 x[i-1], y[0] = x[0] - 0.97 x[0]), window
-    //      (fbank.h:130-135).  x[2n-1] is the odd sample of element n-1: the lane below (lane 0: lane 63 of m-1)
-    float2 a[FW][4];
-#pragma unroll
-    for (int w = 0; w < FW; ++w) {
-      const float mu = mean[w] * inv_fl;   // (one rounding away from the quotient; the sum's order differs from the reference's serial one anyway)
-      // (no range masks: samples past the frame were fetched as zeros and their window values ARE zero -- whatever the
-      //  mean subtraction and the pre-emphasis make of them is multiplied away; round 3 spent 27 selects per frame on them)
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const float xe = v[w][m].x - mu;
-        const float xo = v[w][m].y - mu;
-        float prev = fb_dppx<0x138, 0xf, true>(xo);                           // wave_shr:1: odd sample of element n - 1
-        if (m > 0) {
-          const float top = v[w][m - 1].y - mu;                                // lane 0: lane 63 of the row of elements before
-          const float wrap = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, top), 63));
-          prev = lane == 0 ? wrap : prev;
-        } else {
-          prev = lane == 0 ? xe : prev;                                       // i = 0: its own value
-        }
-        a[w][m].x = (xe - 0.97f * prev) * wn[2 * m];
-        a[w][m].y = (xo - 0.97f * xe) * wn[2 * m + 1];
-      }
-    }
-    // ---- 256-point complex FFT, radix-4 DIF, 4 stages (stage st exchanges elements q = 64 >> 2 st apart)
-#pragma unroll
-    for (int st = 0; st < 4; ++st) {
-#pragma unroll
-      for (int w = 0; w < FW; ++w) {
-        fb_f2* const z = reinterpret_cast<fb_f2*>(strip + w * kFbankStrip);
-        fb_f2 a0, a1, a2, a3, o0, o1, o2, o3;
-        if (st > 0) {
-          a0 = z[zpos[st][0]]; a1 = z[zpos[st][1]]; a2 = z[zpos[st][2]]; a3 = z[zpos[st][3]];
-        } else {
-          a0 = fb_f2{a[w][0].x, a[w][0].y}; a1 = fb_f2{a[w][1].x, a[w][1].y};
-          a2 = fb_f2{a[w][2].x, a[w][2].y}; a3 = fb_f2{a[w][3].x, a[w][3].y};
-        }
-        if (st < 3) {
-          fb_bfly<true>(a0, a1, a2, a3, tws[st][0], tws[st][1], tws[st][2], o0, o1, o2, o3);
-          z[zpos[st][0]] = o0; z[zpos[st][1]] = o1; z[zpos[st][2]] = o2; z[zpos[st][3]] = o3;
-        } else {
-          // positions 4 lane + m hold X[rev4(4 lane + m)] = X[64 m + rev3(lane)]: stored in natural order
-          fb_bfly<false>(a0, a1, a2, a3, a0, a0, a0, o0, o1, o2, o3);
-          z[zout[0]] = o0; z[zout[1]] = o1; z[zout[2]] = o2; z[zout[3]] = o3;
-        }
-      }
-      wave_sync();
-    }
-    // ---- real-FFT untangle + power (fbank.h:173-175)
-    float pw[FW][4];
-#pragma unroll
-    for (int w = 0; w < FW; ++w) {
-      const fb_f2* const z = reinterpret_cast<const fb_f2*>(strip + w * kFbankStrip);
-#pragma unroll
-      for (int m = 0; m < 4; m += 2) {
-        fb_f2 xa, xb;
-        if (m == 0) fb_untangle2<false>(z[upos[0]], z[unpos[0]], twh[0], z[upos[1]], z[unpos[1]], twh[1], xa, xb);
-        else fb_untangle2<true>(z[upos[2]], z[unpos[2]], twh[0], z[upos[3]], z[unpos[3]], twh[1], xa, xb);
-        pw[w][m] = xa.x * xa.x + xa.y * xa.y;
-        pw[w][m + 1] = xb.x * xb.x + xb.y * xb.y;
-      }
-    }
-    wave_sync();                                          // every lane has read its Z values: the strips are free
-#pragma unroll
-    for (int w = 0; w < FW; ++w) {
-      float* const pwr = strip + w * kFbankStrip;            // 256 power bins (+ 16 zeros of slack for the padded slots)
-#pragma unroll
-      for (int m = 0; m < 4; ++m) pwr[lane + 64 * m] = pw[w][m];
-      if (lane < 16) pwr[256 + lane] = 0.f;
-    }
-    wave_sync();
-    // ---- mel (fbank.h:179-186): one slot per lane and round, ascending k, then the slots of a filter in order
-#pragma unroll
-    for (int w = 0; w < FW; ++w) {
-      const float* const pwr = strip + w * kFbankStrip;
-      float* const melacc = strip + w * kFbankStrip + 512;
-#pragma unroll
-      for (int r = 0; r < ROUNDS; ++r) {
-        float e = 0.f;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) e = fmaf(sw[r][u], pwr[sfirst[r] + u], e);
-        melacc[lane + 64 * r] = e;                            // slot sums (slots past nslots: 0)
-      }
-    }
-    wave_sync();
-    // ---- log (fbank.h:187-190), store.  Slots are sorted by filter: a filter's slots are neighbours.
-#pragma unroll
-    for (int w = 0; w < FW; ++w) {
-      int b = ub, fr = ufr + w;
-      if (fr >= nframes) { fr -= nframes; ++b; }
-      if (b < B) {
-        const int64_t g = int64_t(b) * nframes + fr;
-        const float* const melacc = strip + w * kFbankStrip + 512;
-#pragma unroll
-        for (int r = 0; r < ROUNDS; ++r) {
-          const int slot = lane + 64 * r;
-          if (scount[r] > 0) {
-            float e = melacc[slot];
-            for (int n = 1; n < scount[r]; ++n) e += melacc[slot + n];
-#ifdef WEKWS_FBANK_FASTLOG
-            feats[g * P.num_bins + sbin[r]] = __logf(fmaxf(e, FLT_EPSILON));
-#else
-            feats[g * P.num_bins + sbin[r]] = fb_logf(fmaxf(e, FLT_EPSILON));
-#endif
-          }
-        }
-      }
-    }
-    wave_sync();
+    fbank_frames<ROUNDS, FW>(K, strip, lane, inv_fl, vn, [&]() __attribute__((always_inline)) { fetch(nb, nfr); },
+                             [&](int w, float*& row) __attribute__((always_inline)) {
+                               int b = ub, fr = ufr + w;
+                               if (fr >= nframes) { fr -= nframes; ++b; }
+                               if (b >= B) return false;
+                               row = feats + (int64_t(b) * nframes + fr) * P.num_bins;
+                               return true;
+                             });
     ub = nb; ufr = nfr;
   }
 }

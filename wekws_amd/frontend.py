@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from wekws_amd import _capi
@@ -141,3 +142,112 @@ class Mfcc:
 
     def __call__(self, pcm: torch.Tensor) -> torch.Tensor:
         return dct_lifter(self.fbank(pcm), self.num_ceps, self.cepstral_lifter)
+
+
+class StreamingFrontEnd:
+    """``KeyWordSpotter.accept_wave`` (wekws/bin/stream_kws_ctc.py:335-398) for ``num_streams`` streams at once, on the
+    device: leftover samples, Kaldi fbank of (leftover + chunk), the remembered frames of the context expansion and the
+    frame-skip phase are carried per stream by the library (wekws_hip_stream_frontend_*); a push is two launches.
+
+        fe = StreamingFrontEnd(4096, num_bins=80, window="povey", left=2, right=2, skip=3, max_chunk=4800)
+        feats, frames = fe.push(pcm)            # pcm (B, nmax) int16 on the device: row b continues stream b
+
+    Context is off (left = right = 0) or ``left == right >= 1``; anything else is refused (the streaming reference is
+    coherent only there).  int16 input only, as the reference receives it."""
+
+    def __init__(self, num_streams: int, num_bins: int = 40, window: str = "hamming", left: int = 0, right: int = 0,
+                 skip: int = 1, max_chunk: int = 16000, sample_rate: int = 16000, frame_length: Optional[int] = None,
+                 frame_shift: Optional[int] = None, device="cuda"):
+        if window not in WINDOWS:
+            raise ValueError(f"window must be one of {sorted(WINDOWS)}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("wekws_amd.frontend.StreamingFrontEnd runs on the MI355X HIP path only (no CPU fallback)")
+        self.num_streams, self.num_bins, self.max_chunk = int(num_streams), int(num_bins), int(max_chunk)
+        self.left, self.right, self.skip = int(left), int(right), int(skip)
+        self.feat_dim = self.num_bins * (self.left + self.right + 1)
+        cfg = _capi.StreamFrontendCfg()
+        cfg.fbank.num_bins, cfg.fbank.sample_rate = self.num_bins, int(sample_rate)
+        cfg.fbank.frame_length = int(frame_length) if frame_length is not None else sample_rate // 1000 * 25
+        cfg.fbank.frame_shift = int(frame_shift) if frame_shift is not None else sample_rate // 1000 * 10
+        cfg.fbank.window = WINDOWS[window]
+        cfg.left, cfg.right, cfg.skip = self.left, self.right, self.skip
+        cfg.max_streams, cfg.max_chunk = self.num_streams, self.max_chunk
+        cfg.device = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", cfg.device)
+        self.cfg = cfg
+        self._lib = _capi.load()
+        self._ptr = ctypes.c_void_p()
+        _capi.check(self._lib.wekws_hip_stream_frontend_create(ctypes.byref(cfg), ctypes.byref(self._ptr)),
+                    "wekws_hip_stream_frontend_create")
+
+    def __del__(self):
+        try:
+            if self._ptr:
+                self._lib.wekws_hip_stream_frontend_destroy(self._ptr)
+                self._ptr = ctypes.c_void_p()
+        except Exception:
+            pass
+
+    def max_frames(self, nmax: int) -> int:
+        """A row capacity that always suffices for chunks of up to ``nmax`` samples."""
+        return int(self._lib.wekws_hip_stream_frontend_max_frames(self._ptr, int(nmax)))
+
+    def push(self, pcm, samples=None, streams=None, capacity: Optional[int] = None, out: Optional[torch.Tensor] = None):
+        """``pcm``: a (B, nmax) int16 device tensor, or a list of ``bytes`` / int16 arrays (uploaded as ONE padded tensor);
+        ``samples``: the valid samples per row (default: all, or each list entry's own length); ``streams``: the stream of
+        each row (default 0 .. B-1).  Returns ``(feats, frames)``: feats (B, max(frames, 0), D) float32 on the device, zero
+        past each row's count; frames a host list, -1 = held (the reference's None), 0 = its empty result.
+        ``capacity``: rows to allocate per stream (default: ``max_frames(nmax)``), for a caller that wants one shape.
+        ``out``: a (B, capacity, D) float32 device tensor to write into instead (rows past a count keep what they held)."""
+        if not torch.is_tensor(pcm):
+            arrs = [np.frombuffer(c, dtype="<i2") if isinstance(c, (bytes, bytearray, memoryview)) else np.asarray(c) for c in pcm]
+            if any(a.dtype != np.int16 or a.ndim != 1 for a in arrs):
+                raise ValueError("chunks must be bytes or 1-d int16 arrays")
+            if samples is None:
+                samples = [int(a.size) for a in arrs]
+            host = np.zeros((len(arrs), max([int(a.size) for a in arrs] + [0])), dtype=np.int16)
+            for i, a in enumerate(arrs):
+                host[i, :a.size] = a
+            pcm = torch.from_numpy(host).to(self.device)
+        if pcm.dim() != 2 or not pcm.is_cuda or pcm.dtype != torch.int16:
+            raise ValueError("pcm must be a (B, nmax) int16 tensor on a ROCm device")
+        pcm = pcm.contiguous()
+        B, nmax = int(pcm.size(0)), int(pcm.size(1))
+        # host arguments as int32 arrays (thousands of rows: no per-row Python objects on the way in)
+        ids = np.arange(B, dtype=np.int32) if streams is None else np.asarray([int(s) for s in streams], dtype=np.int64)
+        ns = np.full(B, nmax, dtype=np.int32) if samples is None else np.asarray([int(n) for n in samples], dtype=np.int64)
+        if ids.shape != (B,) or ns.shape != (B,):
+            raise ValueError("streams / samples must have one entry per row of pcm")
+        lim = np.iinfo(np.int32)
+        ids = np.ascontiguousarray(np.clip(ids, lim.min, lim.max), dtype=np.int32)     # (out of range stays out of range: EINVAL)
+        ns = np.ascontiguousarray(np.clip(ns, lim.min, lim.max), dtype=np.int32)
+        if out is not None:
+            if out.dim() != 3 or out.size(0) != B or out.size(2) != self.feat_dim or out.dtype != torch.float32 or \
+                    out.device != pcm.device or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous ({B}, capacity, {self.feat_dim}) float32 tensor on the device of pcm")
+            cap, feats, capacity = int(out.size(1)), out, int(out.size(1))
+        else:
+            cap = self.max_frames(nmax) if capacity is None else int(capacity)
+            feats = torch.zeros((B, cap, self.feat_dim), dtype=torch.float32, device=pcm.device)
+        got = np.zeros(max(B, 1), dtype=np.int32)
+        stream = torch.cuda.current_stream(pcm.device).cuda_stream
+        _capi.check(self._lib.wekws_hip_stream_frontend_push(
+            self._ptr, pcm.data_ptr() if nmax else None, B, nmax, ids.ctypes.data if B else None, ns.ctypes.data if B else None,
+            feats.data_ptr() if cap else None, cap, got.ctypes.data, ctypes.c_void_p(stream)),
+            "wekws_hip_stream_frontend_push")
+        frames = got[:B].tolist()
+        if capacity is None:
+            feats = feats[:, :max(frames + [0])]
+        return feats, frames
+
+    def reset(self, streams=None) -> None:
+        ids = list(range(self.num_streams)) if streams is None else [int(s) for s in streams]
+        _capi.check(self._lib.wekws_hip_stream_frontend_reset(self._ptr, (ctypes.c_int32 * max(len(ids), 1))(*ids), len(ids)),
+                    "wekws_hip_stream_frontend_reset")
+
+    def counts(self, stream: int) -> Tuple[int, int, int, int]:
+        """(leftover samples, remembered frames or -1, skip phase, rows delivered) of a stream: host values, no device read."""
+        out = (ctypes.c_int32 * 4)()
+        _capi.check(self._lib.wekws_hip_stream_frontend_counts(self._ptr, int(stream), out), "wekws_hip_stream_frontend_counts")
+        return tuple(int(v) for v in out)
