@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "../../include/wekws_hip.h"
+#include "blob_layout.h"
 #include "conv_stack.hip.h"
 
 namespace wekws {
@@ -288,7 +289,8 @@ inline int generic_forward(const GenericModel& m, const float* x, int B, int T, 
   float* tm = reinterpret_cast<float*>(ws + 2 * mat);
   float* zs = reinterpret_cast<float*>(ws + 3 * mat);
   float* ub = reinterpret_cast<float*>(ws + 4 * mat);
-  const float* p = m.w;
+  const BlobLayout L = blob_layout(d);                        // where the tensors lie: blob_layout.h
+  const float* w = m.w;
   const int act = d.activation == WEKWS_HIP_ACT_SIGMOID ? GEN_SIGMOID : 0;
   float* h = hA;                                              // the current activation tile (rows, width of the layer)
   float* o = hB;
@@ -296,19 +298,15 @@ inline int generic_forward(const GenericModel& m, const float* x, int B, int T, 
 
   if (d.backbone == WEKWS_HIP_BACKBONE_FSMN) {
     // fsmn.py:462-495 (preprocessing none, identity head: fsmn_ctc.yaml:36-56)
-    const int A0 = d.aux[0], A1 = d.aux[1], D = d.num_stack, lo = d.kernel_size, ro = d.stack_size, P = lo - 1 + ro, L = d.num_layers;
-    gen_linear(st, x, p, p + size_t(A0) * d.idim, nullptr, h, rows, d.idim, A0, 0);                   // in_linear1
-    p += size_t(A0) * d.idim + A0;
-    gen_linear(st, h, p, p + size_t(C) * A0, nullptr, o, rows, A0, C, GEN_RELU);                      // in_linear2 + ReLU
-    p += size_t(C) * A0 + C;
+    const int A0 = d.aux[0], A1 = d.aux[1], D = d.num_stack, lo = d.kernel_size, ro = d.stack_size, P = lo - 1 + ro, NL = d.num_layers;
+    gen_linear(st, x, w + L.in1_w().off, w + L.in1_b().off, nullptr, h, rows, d.idim, A0, 0);         // in_linear1
+    gen_linear(st, h, w + L.in2_w().off, w + L.in2_b().off, nullptr, o, rows, A0, C, GEN_RELU);       // in_linear2 + ReLU
     swap();
-    for (int l = 0; l < L; ++l) {
-      const float* wproj = p; p += size_t(D) * C;
-      const float* taps = p; p += size_t(D) * (lo + ro);
-      const float* waff = p; p += size_t(C) * D;
-      const float* baff = p; p += C;
+    for (int l = 0; l < NL; ++l) {
+      const FsmnWeights lw = L.fsmn_layer(l);
+      const float *wproj = w + lw.wproj.off, *taps = w + lw.taps.off, *waff = w + lw.waff.off, *baff = w + lw.baff.off;
       gen_linear(st, h, wproj, nullptr, nullptr, tm, rows, C, D, 0);                                  // LinearTransform, no bias
-      const GenCacheMap cm{int64_t(D) * P * L, int64_t(P) * L, L, l};
+      const GenCacheMap cm{int64_t(D) * P * NL, int64_t(P) * NL, NL, l};
       hipLaunchKernelGGL(gen_ctx_kernel, dim3(gen_grid(int64_t(B) * (P + T) * D)), dim3(256), 0, st, ub, tm, int64_t(T) * D, int64_t(D),
                          in_cache, out_cache, cm, B, T, D, P);
       hipLaunchKernelGGL(gen_dw_kernel, dim3(gen_grid(rows * D)), dim3(256), 0, st, tm, ub, taps, static_cast<const float*>(nullptr), B, T,
@@ -316,29 +314,25 @@ inline int generic_forward(const GenericModel& m, const float* x, int B, int T, 
       gen_linear(st, tm, waff, baff, nullptr, o, rows, D, C, GEN_RELU);                               // AffineTransform + ReLU
       swap();
     }
-    gen_linear(st, h, p, p + size_t(A1) * C, nullptr, o, rows, C, A1, 0);                             // out_linear1
-    p += size_t(A1) * C + A1;
-    gen_linear(st, o, p, p + size_t(d.odim) * A1, nullptr, y, rows, A1, d.odim, act);                 // out_linear2
+    gen_linear(st, h, w + L.out1_w().off, w + L.out1_b().off, nullptr, o, rows, C, A1, 0);            // out_linear1
+    gen_linear(st, o, w + L.out2_w().off, w + L.out2_b().off, nullptr, y, rows, A1, d.odim, act);     // out_linear2
     return done();
   }
 
   // ---- preprocessing: LinearSubsampling1 (subsampling.py:53-57) or the CMVN-only diagonal (preproc_relu = 0)
   if (m.pre_diag)
-    hipLaunchKernelGGL(gen_diag_kernel, dim3(gen_grid(rows * C)), dim3(256), 0, st, h, x, p, p + size_t(C) * d.idim, rows, C, d.idim,
-                       d.preproc_relu);
+    hipLaunchKernelGGL(gen_diag_kernel, dim3(gen_grid(rows * C)), dim3(256), 0, st, h, x, w + L.pre_w().off, w + L.pre_b().off, rows, C,
+                       d.idim, d.preproc_relu);
   else
-    gen_linear(st, x, p, p + size_t(C) * d.idim, nullptr, h, rows, d.idim, C, d.preproc_relu ? GEN_RELU : 0);
-  p += size_t(C) * d.idim + C;
+    gen_linear(st, x, w + L.pre_w().off, w + L.pre_b().off, nullptr, h, rows, d.idim, C, d.preproc_relu ? GEN_RELU : 0);
 
   if (d.backbone == WEKWS_HIP_BACKBONE_GRU) {
-    const int H = C, L = d.num_layers;
+    const int H = C, NL = d.num_layers;
     float* gh = reinterpret_cast<float*>(reinterpret_cast<char*>(ub) + gen_al(size_t(B) * T * H * 4));   // (ub itself is unused here)
     float* hst = reinterpret_cast<float*>(reinterpret_cast<char*>(gh) + gen_al(size_t(B) * 3 * H * 4));
-    for (int l = 0; l < L; ++l) {
-      const float* wih = p; p += size_t(3) * H * H;
-      const float* whh = p; p += size_t(3) * H * H;
-      const float* bih = p; p += 3 * H;
-      const float* bhh = p; p += 3 * H;
+    for (int l = 0; l < NL; ++l) {
+      const GruWeights lw = L.gru_layer(l);
+      const float *wih = w + lw.w_ih.off, *whh = w + lw.w_hh.off, *bih = w + lw.b_ih.off, *bhh = w + lw.b_hh.off;
       gen_linear(st, h, wih, bih, nullptr, tm, rows, H, 3 * H, 0);                                    // gi for all steps
       if (in_cache) (void)hipMemcpyAsync(hst, in_cache + size_t(l) * B * H, size_t(B) * H * 4, hipMemcpyDeviceToDevice, st);
       else (void)hipMemsetAsync(hst, 0, size_t(B) * H * 4, st);
@@ -355,36 +349,26 @@ inline int generic_forward(const GenericModel& m, const float* x, int B, int T, 
     bool zinit = true;
     for (int i = 0; i < sched.nb; ++i) {
       const ConvBlock blk = sched.block(i);
+      const ConvWeights bw = L.block(i);
+      const float *wd = w + bw.wd.off, *bd = w + bw.bd.off, *w1 = w + bw.w1.off, *b1 = w + bw.b1.off;
       const int dil = blk.dil, pad = blk.pad;
       const GenCacheMap cm{int64_t(C) * Pc, Pc, 1, blk.cache_off};
       hipLaunchKernelGGL(gen_ctx_kernel, dim3(gen_grid(int64_t(B) * (pad + T) * C)), dim3(256), 0, st, ub, h, int64_t(T) * C, int64_t(C),
                          in_cache, out_cache, cm, B, T, C, pad);
       if (d.backbone == WEKWS_HIP_BACKBONE_DS_TCN) {
-        const float* wd = p; p += size_t(C) * ks;
-        const float* bd = p; p += C;
-        const float* wp = p; p += size_t(C) * C;
-        const float* bp = p; p += C;
         hipLaunchKernelGGL(gen_dw_kernel, dim3(gen_grid(rows * C)), dim3(256), 0, st, tm, ub, wd, bd, B, T, C, ks, dil, 1);
-        gen_linear(st, tm, wp, bp, h, o, rows, C, C, GEN_RELU | GEN_RES_AFTER);                       // tcn.py:101-114, :60
+        gen_linear(st, tm, w1, b1, h, o, rows, C, C, GEN_RELU | GEN_RES_AFTER);                       // tcn.py:101-114, :60
       } else if (d.backbone == WEKWS_HIP_BACKBONE_TCN) {
-        const float* wc = p; p += size_t(C) * C * ks;                                                  // W[o][c][j]
-        const float* bc = p; p += C;
         for (int j = 0; j < ks; ++j) {                                                                 // tap j reads u rows t + j dil
           const bool lastj = j == ks - 1;
-          gen_gemm(st, ub + int64_t(j) * dil * C, int64_t(pad + T) * C, C, wc + j, int64_t(C) * ks, ks, lastj ? bc : nullptr,
+          gen_gemm(st, ub + int64_t(j) * dil * C, int64_t(pad + T) * C, C, w1 + j, int64_t(C) * ks, ks, lastj ? b1 : nullptr,
                    lastj ? h : nullptr, int64_t(T) * C, C, o, int64_t(T) * C, C, B, T, C, C,
-                   (j ? GEN_ACCUM : 0) | (lastj ? (GEN_RELU | GEN_RES_AFTER) : GEN_PARTIAL));         // tcn.py:75-84, :60
+                   (j ? GEN_ACCUM : 0) | (lastj ? (GEN_RELU | GEN_RES_AFTER) : GEN_PARTIAL));         // W[o][c][j]; tcn.py:75-84, :60
         }
       } else {                                                                                          // MDTC, mdtc.py:95-121
-        const float* wd = p; p += size_t(C) * ks;
-        const float* bd = p; p += C;
-        const float* w1 = p; p += size_t(C) * C;
-        const float* b1 = p; p += C;
-        const float* w2 = p; p += size_t(C) * C;
-        const float* b2 = p; p += C;
         hipLaunchKernelGGL(gen_dw_kernel, dim3(gen_grid(rows * C)), dim3(256), 0, st, tm, ub, wd, bd, B, T, C, ks, dil, 0);
         gen_linear(st, tm, w1, b1, nullptr, o, rows, C, C, GEN_RELU);
-        gen_linear(st, o, w2, b2, h, tm, rows, C, C, GEN_RELU | GEN_RES_BEFORE);
+        gen_linear(st, o, w + bw.w2.off, w + bw.b2.off, h, tm, rows, C, C, GEN_RELU | GEN_RES_BEFORE);
         std::swap(tm, o);                                                                               // (the block's output is in `o` again)
         if (blk.zadd) {                                                                                 // end of a stack: mdtc.py:270-273
           hipLaunchKernelGGL(gen_add_kernel, dim3(gen_grid(rows * C)), dim3(256), 0, st, zs, o, rows * C, zinit ? 1 : 0);
@@ -398,7 +382,7 @@ inline int generic_forward(const GenericModel& m, const float* x, int B, int T, 
 
   // ---- classifier (classifier.py:26-28, :38-40, :63-67) + activation (kws_model.py:196-210)
   if (d.head == WEKWS_HIP_HEAD_LINEAR) {
-    gen_linear(st, h, p, p + size_t(d.odim) * C, nullptr, y, rows, C, d.odim, act);
+    gen_linear(st, h, w + L.head_w().off, w + L.head_b().off, nullptr, y, rows, C, d.odim, act);
   } else if (d.head == WEKWS_HIP_HEAD_IDENTITY) {
     hipLaunchKernelGGL(gen_add_kernel, dim3(gen_grid(rows * C)), dim3(256), 0, st, y, h, rows * C, act ? 2 : 1);
   } else {
@@ -406,9 +390,8 @@ inline int generic_forward(const GenericModel& m, const float* x, int B, int T, 
     float* pooled = tm;                                       // (tm and o are free here)
     hipLaunchKernelGGL(gen_pool_kernel, dim3(gen_grid(int64_t(B) * C)), dim3(256), 0, st, pooled, h, B, T, C, d.head == WEKWS_HIP_HEAD_LAST ? 1 : 0);
     float* hid = o;
-    gen_linear(st, pooled, p, p + size_t(HH) * C, nullptr, hid, B, C, HH, GEN_RELU);
-    p += size_t(HH) * C + HH;
-    gen_linear(st, hid, p, p + size_t(d.odim) * HH, nullptr, y, B, HH, d.odim, act);
+    gen_linear(st, pooled, w + L.head_w().off, w + L.head_b().off, nullptr, hid, B, C, HH, GEN_RELU);
+    gen_linear(st, hid, w + L.head_w2().off, w + L.head_b2().off, nullptr, y, B, HH, d.odim, act);
   }
   return done();
 }

@@ -141,8 +141,13 @@ __device__ inline void nf_release(const NfCtx* R, int slot) {
   if (threadIdx.x == 0) atomicExch(&R->slots[slot], 0u);
 }
 
+// THE BLOB WALKS BELOW (p += ...) restate the order of blob_layout.h instead of reading it.  Deliberately: these routines are the
+// bodies of noinline calls inside the hot kernels, and the compiler allocates a caller's registers around the registers its callee
+// uses.  Reading the offsets from a BlobLayout in NfCtx moved the conv routine from 150 to 146 VGPRs, its frame from 60 to 44 bytes
+// and its SGPRs from 86 to 98 -- and with that the instructions of 113 kernels, ds256_g16's among them; computing the layout here took
+// it to 181 VGPRs.  A change to these walks is a change to every kernel: compare tools/kernel_regs.sh before and after.
 // ---- conv backbones (DS-TCN, TCN, MDTC), one utterance `b` of one call tile: the operator sequence of generic_forward()
-// (generic.hip.h:315-398) on (T, C) row-major activations in the slot.  Pointers are those of the kernel's CallArgs:
+// (generic.hip.h) on (T, C) row-major activations in the slot.  Pointers are those of the kernel's CallArgs:
 //   x        first frame of the tile, utterance 0 (+ b * xs_b);   y / ys_b likewise
 //   in_cache / out_cache   (B, C, P) or nullptr;  gsum: GLOBAL head over several tiles (conv_stack_head's protocol)
 __device__ inline void nf_repair_conv(const NfCtx* R, const float* x, int64_t xs_b, const float* in_cache, float* out_cache, float* y,

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/wekws_hip.h"
+#include "blob_layout.h"
 #include "route.h"
 
 namespace {
@@ -186,65 +187,66 @@ static void scale_rows_inv(float* W, int K, int n, float* bias, const std::vecto
 }
 static void balance_operand_channels(const wekws_hip_desc& d, float* w) {
   const int C = d.hdim, ks = d.kernel_size;
+  const wekws::BlobLayout L = wekws::blob_layout(d);         // where the tensors lie: blob_layout.h
   if (d.backbone == WEKWS_HIP_BACKBONE_DS_TCN) {
-    float* p = w + size_t(C) * d.idim + C;
-    for (int i = 0; i < d.num_layers; ++i) {                 // [wd C x ks][bd C][Wp C x C][bp C]
-      float* wd = p; float* bd = wd + size_t(C) * ks; float* Wp = bd + C;
+    for (int i = 0; i < L.units; ++i) {
+      const wekws::ConvWeights b = L.block(i);
+      float* Wp = w + b.w1.off;
       const std::vector<float> c = column_balance(Wp, C, C, C);
       scale_columns(Wp, C, C, C, c);
-      scale_rows_inv(wd, C, ks, bd, c);                      // a_k = ReLU(dw_k(u) + b_k): c_k > 0 commutes with the ReLU
-      p = Wp + size_t(C) * C + C;
+      scale_rows_inv(w + b.wd.off, C, ks, w + b.bd.off, c);  // a_k = ReLU(dw_k(u) + b_k): c_k > 0 commutes with the ReLU
     }
   } else if (d.backbone == WEKWS_HIP_BACKBONE_MDTC) {
-    float* p = w + size_t(C) * d.idim + C;
-    for (int i = 0; i < wekws::route_blocks(d); ++i) {                  // [wd C x ks][bd C][W1 C x C][b1 C][W2 C x C][b2 C]
-      float* wd = p; float* bd = wd + size_t(C) * ks; float* W1 = bd + C; float* b1 = W1 + size_t(C) * C;
-      float* W2 = b1 + C;
+    for (int i = 0; i < L.units; ++i) {
+      const wekws::ConvWeights b = L.block(i);
+      float* W1 = w + b.w1.off; float* W2 = w + b.w2.off;
       const std::vector<float> c2 = column_balance(W2, C, C, C);
       scale_columns(W2, C, C, C, c2);
-      scale_rows_inv(W1, C, C, b1, c2);                      // mid_m = ReLU(W1[m] a + b1[m])
+      scale_rows_inv(W1, C, C, w + b.b1.off, c2);            // mid_m = ReLU(W1[m] a + b1[m])
       const std::vector<float> c1 = column_balance(W1, C, C, C);
       scale_columns(W1, C, C, C, c1);
-      scale_rows_inv(wd, C, ks, bd, c1);                     // a_k = BN(dw_k(u)) (linear)
-      p = W2 + size_t(C) * C + C;
+      scale_rows_inv(w + b.wd.off, C, ks, w + b.bd.off, c1); // a_k = BN(dw_k(u)) (linear)
     }
   } else if (d.backbone == WEKWS_HIP_BACKBONE_FSMN) {
-    const int I = d.idim, A1 = d.aux[0], A2 = d.aux[1], D = d.num_stack, K = d.odim, nt = d.kernel_size + d.stack_size;
-    float* in1 = w; float* in1b = in1 + size_t(A1) * I; float* in2 = in1b + A1; float* in2b = in2 + size_t(C) * A1;
-    float* lay = in2b + C;
-    const size_t lstride = size_t(D) * C + size_t(D) * nt + size_t(C) * D + C;   // Wproj, taps, Waff, baff
-    float* out1 = lay + lstride * d.num_layers; float* out1b = out1 + size_t(A2) * C;
-    float* out2 = out1b + A2;
-    auto waff = [&](int l) { return lay + lstride * l + size_t(D) * C + size_t(D) * nt; };
+    const int I = d.idim, A1 = d.aux[0], A2 = d.aux[1], D = d.num_stack, K = d.odim;
+    float* in1 = w + L.in1_w().off; float* in2 = w + L.in2_w().off;
+    float* out1 = w + L.out1_w().off; float* out2 = w + L.out2_w().off;
+    // the affine of layer l, rescaled by its consumer's balancing
+    auto scale_affine = [&](int l, const std::vector<float>& c) {
+      const wekws::FsmnWeights lw = L.fsmn_layer(l);
+      scale_rows_inv(w + lw.waff.off, C, D, w + lw.baff.off, c);
+    };
     {
       const std::vector<float> c = column_balance(out2, K, A2, A2);            // out_linear2 <- out_linear1 (linear)
       scale_columns(out2, K, A2, A2, c);
-      scale_rows_inv(out1, A2, C, out1b, c);
+      scale_rows_inv(out1, A2, C, w + L.out1_b().off, c);
     }
     {
       const std::vector<float> c = column_balance(out1, A2, C, C);             // out_linear1 <- ReLU(affine of the last layer)
       scale_columns(out1, A2, C, C, c);
-      float* wa = waff(d.num_layers - 1);
-      scale_rows_inv(wa, C, D, wa + size_t(C) * D, c);
+      scale_affine(d.num_layers - 1, c);
     }
     for (int l = d.num_layers - 1; l >= 0; --l) {                               // Wproj(l) <- ReLU(affine(l-1)) | ReLU(in_linear2)
-      float* wp = lay + lstride * l;
+      float* wp = w + L.fsmn_layer(l).wproj.off;
       const std::vector<float> c = column_balance(wp, D, C, C);
       scale_columns(wp, D, C, C, c);
-      if (l > 0) {
-        float* wa = waff(l - 1);
-        scale_rows_inv(wa, C, D, wa + size_t(C) * D, c);
-      } else {
-        scale_rows_inv(in2, C, A1, in2b, c);
-      }
+      if (l > 0) scale_affine(l - 1, c);
+      else scale_rows_inv(in2, C, A1, w + L.in2_b().off, c);
       // (Waff(l)'s columns are fed by the memory block of Wproj(l)'s output, which is the layer's CACHE: not rescaled)
     }
     {
       const std::vector<float> c = column_balance(in2, C, A1, A1);             // in_linear2 <- in_linear1 (linear)
       scale_columns(in2, C, A1, A1, c);
-      scale_rows_inv(in1, A1, I, in1b, c);
+      scale_rows_inv(in1, A1, I, w + L.in1_b().off, c);
     }
   }
+}
+
+// the tensors of a model's blob, in blob order (blob_layout.h)
+static std::vector<wekws::BlobTensor> blob_tensors(const wekws_hip_desc& d) {
+  std::vector<wekws::BlobTensor> v;
+  wekws::for_each_tensor(wekws::blob_layout(d), [&](const wekws::BlobTensor& t) { v.push_back(t); });
+  return v;
 }
 
 // Conv backbones whose hidden_dim C is not one of the built widths (32 / 64 / 128 / 256) run as the next built width Cp with
@@ -255,51 +257,17 @@ static void balance_operand_channels(const wekws_hip_desc& d, float* w) {
 // Likewise a kernel size ks below the built one ksp: a causal dilated conv with ks taps IS the ksp-tap conv whose first
 // (oldest) ksp - ks taps are zero; only the streaming cache differs (ksp - 1 instead of ks - 1 dilations per block: the
 // extra, older frames meet zero taps) -- wekws_hip_forward copies the caller's slices into / out of the tails of the wider ones.
-static std::vector<float> pad_conv_shape(const wekws_hip_desc& d, const float* p, int Cp, int ksp) {
-  const int C = d.hdim, ks = d.kernel_size, K = d.odim;
-  std::vector<float> out;
-  auto taps = [&](int R, int Rp, int cols, int colsp) {      // [R][cols][ks] -> [Rp][colsp][ksp], taps right-aligned
-    const size_t base = out.size();
-    out.resize(base + size_t(Rp) * colsp * ksp, 0.f);
-    for (int r = 0; r < R; ++r)
-      for (int c = 0; c < cols; ++c)
-        std::memcpy(&out[base + (size_t(r) * colsp + c) * ksp + (ksp - ks)], p + (size_t(r) * cols + c) * ks, ks * sizeof(float));
-    p += size_t(R) * cols * ks;
-  };
-  auto rows = [&](int R, int Rp, int cols, int colsp, int inner) {     // [R][cols][inner] -> [Rp][colsp][inner], zero padded
-    const size_t base = out.size();
-    out.resize(base + size_t(Rp) * colsp * inner, 0.f);
-    for (int r = 0; r < R; ++r)
-      for (int c = 0; c < cols; ++c)
-        std::memcpy(&out[base + (size_t(r) * colsp + c) * inner], p + (size_t(r) * cols + c) * inner, inner * sizeof(float));
-    p += size_t(R) * cols * inner;
-  };
-  rows(C, Cp, d.idim, d.idim, 1);                            // preprocessing W [C][idim], b [C]
-  rows(C, Cp, 1, 1, 1);
-  for (int i = 0; i < wekws::route_blocks(d); ++i) {
-    if (d.backbone == WEKWS_HIP_BACKBONE_TCN) {
-      taps(C, Cp, C, Cp);                                    // dense conv [C][C][ks], b [C]
-      rows(C, Cp, 1, 1, 1);
-    } else {
-      taps(C, Cp, 1, 1);                                     // depthwise taps [C][ks], bias [C]
-      rows(C, Cp, 1, 1, 1);
-      rows(C, Cp, C, Cp, 1);                                 // pointwise [C][C], b [C]
-      rows(C, Cp, 1, 1, 1);
-      if (d.backbone == WEKWS_HIP_BACKBONE_MDTC) {
-        rows(C, Cp, C, Cp, 1);                               // conv2 [C][C], b [C]
-        rows(C, Cp, 1, 1, 1);
-      }
-    }
-  }
-  if (d.head == WEKWS_HIP_HEAD_LINEAR) {
-    rows(K, K, C, Cp, 1);                                    // Wc [K][C], bc [K]
-    rows(K, K, 1, 1, 1);
-  } else if (d.head == WEKWS_HIP_HEAD_GLOBAL || d.head == WEKWS_HIP_HEAD_LAST) {
-    const int HH = d.head_hidden;
-    rows(HH, HH, C, Cp, 1);                                  // W1 [HH][C], b1, W2 [K][HH], b2
-    rows(HH, HH, 1, 1, 1);
-    rows(K, K, HH, HH, 1);
-    rows(K, K, 1, 1, 1);
+// `built`: the descriptor of the shape it runs as (hdim Cp, kernel_size ksp).  Tensor by tensor in blob order, each into the corner of
+// its built shape: rows and columns from 0, the inner axis RIGHT-aligned -- the taps of a conv are its inner axis.
+static std::vector<float> pad_conv_shape(const wekws_hip_desc& d, const float* p, const wekws_hip_desc& built) {
+  const std::vector<wekws::BlobTensor> from = blob_tensors(d), to = blob_tensors(built);
+  std::vector<float> out(size_t(wekws::blob_layout(built).total), 0.f);
+  for (size_t k = 0; k < from.size(); ++k) {
+    const wekws::BlobTensor &u = from[k], &b = to[k];
+    for (int64_t r = 0; r < u.rows; ++r)
+      for (int c = 0; c < u.cols; ++c)
+        std::memcpy(&out[size_t(b.off) + (size_t(r) * b.cols + c) * b.inner + (b.inner - u.inner)],
+                    p + u.off + (size_t(r) * u.cols + c) * u.inner, u.inner * sizeof(float));
   }
   return out;
 }
@@ -307,25 +275,18 @@ static std::vector<float> pad_conv_shape(const wekws_hip_desc& d, const float* p
 // GRU (torch.nn.GRU, kws_model.py:128-133) with a hidden size H below the built 128: the extra units have zero weights and
 // biases in all three gates, so r = z = 1/2, n = tanh(0) = 0 and h' = (1 - z) n + z h stays 0 from a zero-padded h0 -- the
 // real units never see them (zero columns).  Gate blocks [r | z | n] are padded one by one.
-static std::vector<float> pad_gru_hidden(const wekws_hip_desc& d, const float* p, int Hp) {
-  const int H = d.hdim, K = d.odim;
-  std::vector<float> out;
-  auto rows = [&](int R, int Rp, int cols, int colsp) {
-    const size_t base = out.size();
-    out.resize(base + size_t(Rp) * colsp, 0.f);
-    for (int r = 0; r < R; ++r) std::memcpy(&out[base + size_t(r) * colsp], p + size_t(r) * cols, cols * sizeof(float));
-    p += size_t(R) * cols;
-  };
-  rows(H, Hp, d.idim, d.idim);
-  rows(H, Hp, 1, 1);
-  for (int l = 0; l < d.num_layers; ++l) {
-    for (int g = 0; g < 3; ++g) rows(H, Hp, H, Hp);          // W_ih
-    for (int g = 0; g < 3; ++g) rows(H, Hp, H, Hp);          // W_hh
-    for (int g = 0; g < 3; ++g) rows(H, Hp, 1, 1);           // b_ih
-    for (int g = 0; g < 3; ++g) rows(H, Hp, 1, 1);           // b_hh
+static std::vector<float> pad_gru_hidden(const wekws_hip_desc& d, const float* p, const wekws_hip_desc& built) {
+  const int H = d.hdim, Hp = built.hdim;
+  const std::vector<wekws::BlobTensor> from = blob_tensors(d), to = blob_tensors(built);
+  std::vector<float> out(size_t(wekws::blob_layout(built).total), 0.f);
+  for (size_t k = 0; k < from.size(); ++k) {
+    const wekws::BlobTensor &u = from[k], &b = to[k];
+    // rows that grow are hidden units: one block of H (preprocessing) or the three gate blocks of a layer's tensor
+    const int64_t gates = b.rows == u.rows ? 1 : u.rows / H, R = u.rows / gates, Rp = b.rows == u.rows ? R : Hp;
+    for (int64_t g = 0; g < gates; ++g)
+      for (int64_t r = 0; r < R; ++r)
+        std::memcpy(&out[size_t(b.off) + size_t(g * Rp + r) * b.cols], p + u.off + size_t(g * R + r) * u.cols, u.cols * sizeof(float));
   }
-  rows(K, K, H, Hp);
-  rows(K, K, 1, 1);
   return out;
 }
 

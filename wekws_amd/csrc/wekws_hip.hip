@@ -35,6 +35,7 @@
 #include "gru_pipe.hip.h"
 #include "generic.hip.h"
 #include "route.h"
+#include "blob_layout.h"
 #include "mfcc.hip.h"
 #include "splice.hip.h"
 #include "topk.hip.h"
@@ -114,7 +115,7 @@ bool desc_conv(const wekws_hip_desc& d) {
          d.backbone == WEKWS_HIP_BACKBONE_MDTC;
 }
 
-// validates and returns the blob size (floats); 0 with g_err set if invalid
+// validates and returns the blob size (floats: blob_layout.h); 0 with g_err set if invalid
 size_t blob_elems(const wekws_hip_desc& d) {
   if (d.abi_version != WEKWS_HIP_ABI_VERSION) { fail(WEKWS_HIP_EINVAL, "desc.abi_version %d != %d", d.abi_version, WEKWS_HIP_ABI_VERSION); return 0; }
   if (d.idim <= 0 || d.hdim <= 0 || d.odim <= 0) { fail(WEKWS_HIP_EINVAL, "idim/hdim/odim must be positive"); return 0; }
@@ -125,9 +126,7 @@ size_t blob_elems(const wekws_hip_desc& d) {
     fail(WEKWS_HIP_EINVAL, "softmax activation needs a per-frame head (forward_softmax is softmax over axis 2)");
     return 0;
   }
-  const size_t C = d.hdim, K = d.odim, ks = d.kernel_size;
   if (d.backbone == WEKWS_HIP_BACKBONE_FSMN) {
-    const size_t A1 = d.aux[0], A2 = d.aux[1], D = d.num_stack, ro = d.stack_size;
     if (d.num_layers <= 0 || d.num_stack <= 0 || d.kernel_size <= 0 || d.stack_size <= 0 || d.aux[0] <= 0 || d.aux[1] <= 0) {
       fail(WEKWS_HIP_EINVAL, "fsmn: num_layers/proj_dim/left_order/right_order/affine dims must be positive");
       return 0;
@@ -136,37 +135,28 @@ size_t blob_elems(const wekws_hip_desc& d) {
       fail(WEKWS_HIP_EINVAL, "fsmn: preprocessing none, identity classifier and identity activation only");
       return 0;
     }
-    return A1 * d.idim + A1 + C * A1 + C + size_t(d.num_layers) * (D * C + D * (ks + ro) + C * D + C) + A2 * C + A2 +
-           K * A2 + K;
+    return size_t(wekws::blob_layout(d).total);
   }
-  size_t n = C * d.idim + C;  // preprocessing
   switch (d.backbone) {
     case WEKWS_HIP_BACKBONE_DS_TCN:
-      if (d.num_layers <= 0 || d.kernel_size <= 0) { fail(WEKWS_HIP_EINVAL, "tcn: num_layers/kernel_size"); return 0; }
-      n += size_t(d.num_layers) * (C * ks + C + C * C + C);
-      break;
     case WEKWS_HIP_BACKBONE_TCN:
       if (d.num_layers <= 0 || d.kernel_size <= 0) { fail(WEKWS_HIP_EINVAL, "tcn: num_layers/kernel_size"); return 0; }
-      n += size_t(d.num_layers) * (C * C * ks + C);
       break;
     case WEKWS_HIP_BACKBONE_MDTC:
       if (d.num_stack <= 0 || d.stack_size <= 0 || d.kernel_size <= 0) { fail(WEKWS_HIP_EINVAL, "mdtc: num_stack/stack_size/kernel_size"); return 0; }
-      n += size_t(wekws::route_blocks(d)) * (C * ks + C + 2 * (C * C + C));
       break;
     case WEKWS_HIP_BACKBONE_GRU:
       if (d.num_layers <= 0) { fail(WEKWS_HIP_EINVAL, "gru: num_layers"); return 0; }
-      n += size_t(d.num_layers) * (2 * 3 * C * C + 2 * 3 * C);
       break;
     default:
       fail(WEKWS_HIP_EINVAL, "unknown backbone %d", d.backbone);
       return 0;
   }
   switch (d.head) {
-    case WEKWS_HIP_HEAD_LINEAR: n += K * C + K; break;
+    case WEKWS_HIP_HEAD_LINEAR: break;
     case WEKWS_HIP_HEAD_GLOBAL:
     case WEKWS_HIP_HEAD_LAST:
       if (d.head_hidden <= 0) { fail(WEKWS_HIP_EINVAL, "head_hidden must be positive"); return 0; }
-      n += size_t(d.head_hidden) * C + d.head_hidden + K * size_t(d.head_hidden) + K;
       break;
     case WEKWS_HIP_HEAD_IDENTITY:
       if (d.odim != d.hdim) { fail(WEKWS_HIP_EINVAL, "identity head needs odim == hdim"); return 0; }
@@ -175,7 +165,7 @@ size_t blob_elems(const wekws_hip_desc& d) {
       fail(WEKWS_HIP_EINVAL, "unknown head %d", d.head);
       return 0;
   }
-  return n;
+  return size_t(wekws::blob_layout(d).total);   // blob_layout.h: the one statement of the layout
 }
 
 }  // namespace
@@ -538,7 +528,7 @@ static int create_fsmn(const wekws_hip_desc& d, const float* blob_in, size_t n_e
   std::vector<float> balanced(blob_in, blob_in + n_elems);
   balance_operand_channels(d, balanced.data());
   const float* blob = balanced.data();
-  const int I = d.idim, A1 = d.aux[0], A2 = d.aux[1], C = d.hdim, D = d.num_stack, K = d.odim;
+  const int I = d.idim, D = d.num_stack, K = d.odim;
   const int ntaps = d.kernel_size + d.stack_size;
   wekws::FsmnParams q{};
   q.idim = I; q.odim = K; q.proj = D;
@@ -547,40 +537,38 @@ static int create_fsmn(const wekws_hip_desc& d, const float* blob_in, size_t n_e
 
   Image img;
   img.reserve(4);
-  const float* p = blob;
-  // a dense layer W[O][Ksrc] (+ bias[O]): A operand padded to (Op x Kp); bias padded with zeros to Op
+  const wekws::BlobLayout L = wekws::blob_layout(d);
+  // a dense layer W[O][Ksrc] (+ bias[O], or none): A operand padded to (Op x Kp); bias padded with zeros to Op
   // block floating point (fsmn_f16.hip.h): matrix scale, and the output bound |W a + b| <= alpha max|a| + beta
-  auto dense = [&](int O, int Ksrc, int Op, bool has_bias, uint32_t* a_off, uint32_t* b_off, wekws::FsmnDense* fd) {
+  auto dense = [&](const wekws::BlobTensor& w, const wekws::BlobTensor* b, int Op, uint32_t* a_off, uint32_t* b_off, wekws::FsmnDense* fd) {
+    const int O = int(w.rows), Ksrc = w.cols;
+    const float* W = blob + w.off;
     std::vector<float> wp(size_t(Op) * Ksrc, 0.f);
-    std::memcpy(wp.data(), p, size_t(O) * Ksrc * sizeof(float));
+    std::memcpy(wp.data(), W, size_t(O) * Ksrc * sizeof(float));
     *a_off = img.put_packed_a16(wp.data(), Op, Ksrc, Ksrc, &fd->inv_s);
     // (1.0001: summation order / rounding of the device's accumulation)
-    l1_bound<double>(p, O, Ksrc, Ksrc, has_bias ? p + size_t(O) * Ksrc : nullptr, 1.0001f, &fd->alpha, &fd->beta);
-    p += size_t(O) * Ksrc;
-    if (has_bias) {
+    l1_bound<double>(W, O, Ksrc, Ksrc, b ? blob + b->off : nullptr, 1.0001f, &fd->alpha, &fd->beta);
+    if (b) {
       std::vector<float> bp(Op, 0.f);
-      std::memcpy(bp.data(), p, size_t(O) * sizeof(float));
+      std::memcpy(bp.data(), blob + b->off, size_t(O) * sizeof(float));
       *b_off = img.put(bp.data(), Op);
-      p += O;
     }
   };
-  dense(A1, I, q.a1p, true, &q.in1_a, &q.in1_b, &q.in1);
-  dense(C, A1, q.linp, true, &q.in2_a, &q.in2_b, &q.in2);
+  dense(L.in1_w(), &L.in1_b(), q.a1p, &q.in1_a, &q.in1_b, &q.in1);
+  dense(L.in2_w(), &L.in2_b(), q.linp, &q.in2_a, &q.in2_b, &q.in2);
   for (int l = 0; l < d.num_layers; ++l) {
-    uint32_t none = 0;
-    dense(D, C, q.dp, false, &q.layer[l].wp_a, &none, &q.layer[l].wp);
+    const wekws::FsmnWeights lw = L.fsmn_layer(l);
+    const float* taps = blob + lw.taps.off;
+    dense(lw.wproj, nullptr, q.dp, &q.layer[l].wp_a, nullptr, &q.layer[l].wp);
     std::vector<float> tp(size_t(q.dp) * q.taps_ld, 0.f);
-    for (int c = 0; c < D; ++c) std::memcpy(&tp[size_t(c) * q.taps_ld], p + size_t(c) * ntaps, ntaps * sizeof(float));
+    for (int c = 0; c < D; ++c) std::memcpy(&tp[size_t(c) * q.taps_ld], taps + size_t(c) * ntaps, ntaps * sizeof(float));
     float no_bias;
-    l1_bound<float>(p, D, ntaps, ntaps, nullptr, 1.00001f, &q.layer[l].taps_l1, &no_bias);
+    l1_bound<float>(taps, D, ntaps, ntaps, nullptr, 1.00001f, &q.layer[l].taps_l1, &no_bias);
     q.layer[l].taps = img.put(tp.data(), tp.size());
-    p += size_t(D) * ntaps;
-    dense(C, D, q.linp, true, &q.layer[l].wa_a, &q.layer[l].wa_b, &q.layer[l].wa);
+    dense(lw.waff, &lw.baff, q.linp, &q.layer[l].wa_a, &q.layer[l].wa_b, &q.layer[l].wa);
   }
-  dense(A2, C, q.a2p, true, &q.out1_a, &q.out1_b, &q.out1);
-  dense(K, A2, q.op, true, &q.out2_a, &q.out2_b, &q.out2);
-  if (size_t(p - blob) != n_elems)
-    return fail(WEKWS_HIP_EINVAL, "internal: blob walk consumed %zu of %zu floats", size_t(p - blob), n_elems);
+  dense(L.out1_w(), &L.out1_b(), q.a2p, &q.out1_a, &q.out1_b, &q.out1);
+  dense(L.out2_w(), &L.out2_b(), q.op, &q.out2_a, &q.out2_b, &q.out2);
   if (img.spread_log2 > WEKWS_HIP_F16X3_ENVELOPE_LOG2) {
     // a weight matrix spreads its row / column magnitudes beyond the envelope in which the split-fp16 kernel keeps fp32-level
     // accuracy: exact f32 instead (wekws_hip_effective_precision reports F32, wekws_hip_weight_spread_log2 the spread)
@@ -839,7 +827,7 @@ static int create_padded(const wekws_hip_desc& d, const wekws::ShapePlan& plan, 
   wekws_hip_desc dd = d;
   dd.hdim = plan.C;
   if (conv) dd.kernel_size = plan.ks;
-  const std::vector<float> wide = conv ? pad_conv_shape(d, blob, plan.C, plan.ks) : pad_gru_hidden(d, blob, plan.C);
+  const std::vector<float> wide = conv ? pad_conv_shape(d, blob, dd) : pad_gru_hidden(d, blob, dd);
   if (wide.size() != blob_elems(dd)) return fail(WEKWS_HIP_EINVAL, "internal: widened blob has %zu floats, expected %zu", wide.size(), blob_elems(dd));
   const int rc = wekws_hip_create(&dd, wide.data(), wide.size(), device, out);
   if (rc != WEKWS_HIP_OK) return rc;
@@ -866,18 +854,16 @@ static int create_padded(const wekws_hip_desc& d, const wekws::ShapePlan& plan, 
 }
 
 // The weight image of a conv model (preprocessing, residual blocks, classifier) and the kernels' parameters and block tables;
-// returns where the walk over the blob ended.
-static const float* pack_conv(const wekws_hip_desc& d, const float* blob, Image& img, wekws_hip_model* m,
-                              std::vector<wekws::BlockDesc>& blocks, std::vector<wekws::DenseBlock>& dblocks) {
+// every tensor from where blob_layout.h says it lies.
+static void pack_conv(const wekws_hip_desc& d, const float* blob, Image& img, wekws_hip_model* m,
+                      std::vector<wekws::BlockDesc>& blocks, std::vector<wekws::DenseBlock>& dblocks) {
   const int C = d.hdim, ks = d.kernel_size, K = d.odim;
-  const float* p = blob;
+  const wekws::BlobLayout L = wekws::blob_layout(d);
   wekws::StackParams& sp = m->sp;
-  sp.pre_a = img.put_packed_a(p, C, d.idim, d.idim);
+  sp.pre_a = img.put_packed_a(blob + L.pre_w().off, C, d.idim, d.idim);
   sp.pre_inv_s = 1.f;
-  sp.pre_a16 = img.put_packed_a16(p, C, d.idim, d.idim, &sp.pre_inv_s);
-  p += size_t(C) * d.idim;
-  sp.pre_b = img.put(p, C);
-  p += C;
+  sp.pre_a16 = img.put_packed_a16(blob + L.pre_w().off, C, d.idim, d.idim, &sp.pre_inv_s);
+  sp.pre_b = img.put(blob + L.pre_b().off, C);
   sp.idim = d.idim;
   sp.kpre = round_up(d.idim, 16);
   sp.ksize = ks;
@@ -888,59 +874,53 @@ static const float* pack_conv(const wekws_hip_desc& d, const float* blob, Image&
   const wekws::ConvSchedule sched = wekws::conv_schedule(d);
   for (int i = 0; i < sched.nb; ++i) {
     const wekws::ConvBlock cb = sched.block(i);
+    const wekws::ConvWeights bw = L.block(i);
+    const float *wd = blob + bw.wd.off, *bd = blob + bw.bd.off, *w1 = blob + bw.w1.off, *b1 = blob + bw.b1.off;
     wekws::BlockDesc b{};
     b.inv_s1 = b.inv_s2 = b.dw_tap_s = b.dw_tap_inv = 1.f;
     b.dil = cb.dil; b.pad = cb.pad; b.cache_off = cb.cache_off; b.zadd = cb.zadd;
     wekws::DenseBlock db{};
     db.dil = b.dil; db.pad = b.pad; db.cache_off = b.cache_off; db.zadd = b.zadd; db.inv_s1 = 1.f;
     if (d.backbone == WEKWS_HIP_BACKBONE_TCN) {
-      b.a1 = img.put_packed_a(p, C, C * ks, C * ks);
-      b.a1_16 = img.put_packed_a16(p, C, C * ks, C * ks, &b.inv_s1);
+      b.a1 = img.put_packed_a(w1, C, C * ks, C * ks);
+      b.a1_16 = img.put_packed_a16(w1, C, C * ks, C * ks, &b.inv_s1);
       {  // dense-stack kernel: K reordered to (tap, channel)
         std::vector<float> mw(size_t(C) * C * ks);
         for (int o = 0; o < C; ++o)
           for (int c = 0; c < C; ++c)
-            for (int j = 0; j < ks; ++j) mw[(size_t(o) * ks + j) * C + c] = p[(size_t(o) * C + c) * ks + j];
+            for (int j = 0; j < ks; ++j) mw[(size_t(o) * ks + j) * C + c] = w1[(size_t(o) * C + c) * ks + j];
         db.a1 = img.put_packed_a16(mw.data(), C, C * ks, C * ks, &db.inv_s1);
       }
-      p += size_t(C) * C * ks;
-      b.b1 = img.put(p, C);
+      b.b1 = img.put(b1, C);
       db.b1 = b.b1;
-      p += C;
     } else {
-      b.dw_w = img.put(p, size_t(C) * ks);
-      b.dw_b = img.put(p + size_t(C) * ks, C);
+      b.dw_w = img.put(wd, size_t(C) * ks);
+      b.dw_b = img.put(bd, C);
       {  // taps + bias of a channel side by side, padded to whole float4s (one or three 16-byte loads per row)
         const int dwp = round_up(ks + 1, 4);
         std::vector<float> pk(size_t(C) * dwp, 0.f);
         for (int c = 0; c < C; ++c) {
-          for (int j = 0; j < ks; ++j) pk[size_t(c) * dwp + j] = p[size_t(c) * ks + j];
-          pk[size_t(c) * dwp + ks] = p[size_t(C) * ks + c];
+          for (int j = 0; j < ks; ++j) pk[size_t(c) * dwp + j] = wd[size_t(c) * ks + j];
+          pk[size_t(c) * dwp + ks] = bd[c];
         }
         b.dw_pk = img.put(pk.data(), pk.size());
       }
       // block floating point: the depthwise output obeys |dw(u) + b| <= dw_alpha * max|u| + dw_beta (1.0000005: rounding of the
       // tap sum and of the device's FMA chain); the taps enter the matrix cores (ds256_mm) scaled to the top of the fp16 range
-      l1_bound<float>(p, C, ks, ks, p + size_t(C) * ks, 1.0000005f, &b.dw_alpha, &b.dw_beta);
+      l1_bound<float>(wd, C, ks, ks, bd, 1.0000005f, &b.dw_alpha, &b.dw_beta);
       float tmax = 0.f;
       for (size_t e = 0; e < size_t(C) * ks; ++e)
-        if (std::isfinite(p[e]) && std::fabs(p[e]) > tmax) tmax = std::fabs(p[e]);
+        if (std::isfinite(wd[e]) && std::fabs(wd[e]) > tmax) tmax = std::fabs(wd[e]);
       b.dw_tap_s = pow2_scale_host(tmax, &b.dw_tap_inv);
-      p += size_t(C) * ks;
-      p += C;
-      b.a1 = img.put_packed_a(p, C, C, C);
-      b.a1_16 = img.put_packed_a16(p, C, C, C, &b.inv_s1);
+      b.a1 = img.put_packed_a(w1, C, C, C);
+      b.a1_16 = img.put_packed_a16(w1, C, C, C, &b.inv_s1);
       // |W1 a + b1| <= mid_alpha * max|a| + mid_beta (MDTC mid tile)
-      l1_bound<float>(p, C, C, C, p + size_t(C) * C, 1.0001f, &b.mid_alpha, &b.mid_beta);
-      p += size_t(C) * C;
-      b.b1 = img.put(p, C);
-      p += C;
+      l1_bound<float>(w1, C, C, C, b1, 1.0001f, &b.mid_alpha, &b.mid_beta);
+      b.b1 = img.put(b1, C);
       if (d.backbone == WEKWS_HIP_BACKBONE_MDTC) {
-        b.a2 = img.put_packed_a(p, C, C, C);
-        b.a2_16 = img.put_packed_a16(p, C, C, C, &b.inv_s2);
-        p += size_t(C) * C;
-        b.b2 = img.put(p, C);
-        p += C;
+        b.a2 = img.put_packed_a(blob + bw.w2.off, C, C, C);
+        b.a2_16 = img.put_packed_a16(blob + bw.w2.off, C, C, C, &b.inv_s2);
+        b.b2 = img.put(blob + bw.b2.off, C);
       }
     }
     blocks.push_back(b);
@@ -955,23 +935,24 @@ static const float* pack_conv(const wekws_hip_desc& d, const float* blob, Image&
   sp.sigmoid = d.activation == WEKWS_HIP_ACT_SIGMOID;
   wekws::DenseParams& dp = m->dp;
   dp.head_inv_s = 1.f;
+  const float* hw = blob + L.head_w().off;
   if (d.head == WEKWS_HIP_HEAD_LINEAR) {
     if (K > 16) {  // wide (CTC) heads: rows padded to a multiple of 32 so that o-tiles come in pairs (ds256_mm.hip.h)
       const int Kp = round_up(K, 32);
       std::vector<float> wp(size_t(Kp) * C, 0.f);
-      std::memcpy(wp.data(), p, size_t(K) * C * sizeof(float));
+      std::memcpy(wp.data(), hw, size_t(K) * C * sizeof(float));
       dp.head_a16 = img.put_packed_a16(wp.data(), Kp, C, C, &dp.head_inv_s);
     } else {
-      dp.head_a16 = img.put_packed_a16(p, K, C, C, &dp.head_inv_s);
+      dp.head_a16 = img.put_packed_a16(hw, K, C, C, &dp.head_inv_s);
     }
-    sp.head_w = img.put(p, size_t(K) * C); p += size_t(K) * C;
-    sp.head_b = img.put(p, K); p += K;
+    sp.head_w = img.put(hw, size_t(K) * C);
+    sp.head_b = img.put(blob + L.head_b().off, K);
   } else if (d.head == WEKWS_HIP_HEAD_GLOBAL || d.head == WEKWS_HIP_HEAD_LAST) {
     const int HH = d.head_hidden;
-    sp.head_w = img.put(p, size_t(HH) * C); p += size_t(HH) * C;
-    sp.head_b = img.put(p, HH); p += HH;
-    sp.head_w2 = img.put(p, size_t(K) * HH); p += size_t(K) * HH;
-    sp.head_b2 = img.put(p, K); p += K;
+    sp.head_w = img.put(hw, size_t(HH) * C);
+    sp.head_b = img.put(blob + L.head_b().off, HH);
+    sp.head_w2 = img.put(blob + L.head_w2().off, size_t(K) * HH);
+    sp.head_b2 = img.put(blob + L.head_b2().off, K);
   }
   // dense-stack kernel parameters (plain TCN): same scalars, its own block table
   dp.nblocks = sched.nb; dp.idim = d.idim; dp.kpre16 = sp.kpre16; dp.ksize = ks; dp.odim = K; dp.pre_relu = d.preproc_relu;
@@ -981,18 +962,16 @@ static const float* pack_conv(const wekws_hip_desc& d, const float* blob, Image&
   sp.head_inv_s = dp.head_inv_s;
   // what this shape can run on: one pure function of the descriptor (route.h), shared with the CPU tests
   m->rf = wekws::conv_route_flags(d, int(wekws::ds256_stream_lds_bytes(off)), int(wekws::mdtc64_stream_lds_bytes(off)));
-  return p;
 }
 
 // ... and of a GRU (preprocessing, layers, classifier; the exact-f32 operands and the split-fp16 ones)
-static const float* pack_gru(const wekws_hip_desc& d, const float* blob, Image& img, wekws_hip_model* m) {
+static void pack_gru(const wekws_hip_desc& d, const float* blob, Image& img, wekws_hip_model* m) {
   const int C = d.hdim, K = d.odim;
-  const float* p = blob;
+  const wekws::BlobLayout L = wekws::blob_layout(d);
+  const float *wpre = blob + L.pre_w().off, *bpre = blob + L.pre_b().off, *hw = blob + L.head_w().off;
   wekws::GruParams& gp = m->gp;
-  gp.pre_a = img.put_packed_a(p, C, d.idim, d.idim);
-  p += size_t(C) * d.idim;
-  gp.pre_b = img.put(p, C);
-  p += C;
+  gp.pre_a = img.put_packed_a(wpre, C, d.idim, d.idim);
+  gp.pre_b = img.put(bpre, C);
   gp.idim = d.idim;
   gp.kpre = round_up(d.idim, 16);
   gp.odim = K;
@@ -1000,10 +979,8 @@ static const float* pack_gru(const wekws_hip_desc& d, const float* blob, Image& 
   gp.nlayers = d.num_layers;
   gp.sigmoid = d.activation == WEKWS_HIP_ACT_SIGMOID;
   for (int l = 0; l < d.num_layers; ++l) {
-    const float* wih = p; p += size_t(3) * C * C;
-    const float* whh = p; p += size_t(3) * C * C;
-    const float* bih = p; p += 3 * C;
-    const float* bhh = p; p += 3 * C;
+    const wekws::GruWeights lw = L.gru_layer(l);
+    const float *wih = blob + lw.w_ih.off, *whh = blob + lw.w_hh.off, *bih = blob + lw.b_ih.off, *bhh = blob + lw.b_hh.off;
     gp.layer[l].a_ih = img.put_packed_a(wih, 3 * C, C, C);
     gp.layer[l].a_hh = img.put_packed_a(whh, 3 * C, C, C);
     m->gq.a_ih16[l] = img.put_packed_a16(wih, 3 * C, C, C, &m->gq.ih_inv_s[l]);
@@ -1011,15 +988,14 @@ static const float* pack_gru(const wekws_hip_desc& d, const float* blob, Image& 
     gp.layer[l].b_ih = img.put(bih, 3 * C);
     gp.layer[l].b_hh = img.put(bhh, 3 * C);
   }
-  m->gq.head_a16 = img.put_packed_a16(p, K, C, C, &m->gq.head_inv_s);
-  gp.head_w = img.put(p, size_t(K) * C); p += size_t(K) * C;
-  gp.head_b = img.put(p, K); p += K;
+  m->gq.head_a16 = img.put_packed_a16(hw, K, C, C, &m->gq.head_inv_s);
+  gp.head_w = img.put(hw, size_t(K) * C);
+  gp.head_b = img.put(blob + L.head_b().off, K);
   m->gq.kpre16 = round_up(d.idim, 32);
-  m->gq.pre_a16 = img.put_packed_a16(blob, C, d.idim, d.idim, &m->gq.pre_inv_s);
+  m->gq.pre_a16 = img.put_packed_a16(wpre, C, d.idim, d.idim, &m->gq.pre_inv_s);
   // |Wpre x + b| <= pre_alpha * max|x| + pre_beta
-  l1_bound<float>(blob, C, d.idim, d.idim, blob + size_t(C) * d.idim, 1.00001f, &m->gq.pre_alpha, &m->gq.pre_beta);
+  l1_bound<float>(wpre, C, d.idim, d.idim, bpre, 1.00001f, &m->gq.pre_alpha, &m->gq.pre_beta);
   m->cache_len = 0;
-  return p;
 }
 
 // fbank of float or int16 samples
@@ -1077,11 +1053,8 @@ int wekws_hip_create(const wekws_hip_desc* desc, const float* blob, size_t n_ele
   img.reserve(4);  // offset 0 is never a valid section
   std::vector<wekws::BlockDesc> blocks;
   std::vector<wekws::DenseBlock> dblocks;
-  const float* const end = desc_conv(d) ? pack_conv(d, blob, img, m, blocks, dblocks) : pack_gru(d, blob, img, m);
-  if (size_t(end - blob) != n_elems) {
-    delete m;
-    return fail(WEKWS_HIP_EINVAL, "internal: blob walk consumed %zu of %zu floats", size_t(end - blob), n_elems);
-  }
+  if (desc_conv(d)) pack_conv(d, blob, img, m, blocks, dblocks);
+  else pack_gru(d, blob, img, m);
   // the promise of DEFAULT / F16X3 is fp32-level accuracy: weights outside the envelope in which the split-fp16 kernels
   // keep it (Image::spread_log2) are served by the exact-f32 kernels instead (wekws_hip_effective_precision says so)
   m->spread_log2 = img.spread_log2;

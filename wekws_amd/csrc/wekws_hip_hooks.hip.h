@@ -1,5 +1,5 @@
 // The test hooks of libwekws_hip_hooks.so (make hooks: wekws_hip.hip compiled with -DWEKWS_TEST_HOOKS, which includes this file):
-// the route trace of a forward, the routing functions of route.h without a device, the GRU epoch, a CU hog, the fbank's plan and
+// the route trace of a forward, the routing functions of route.h and the blob layout of blob_layout.h without a device, the GRU epoch, a CU hog, the fbank's plan and
 // table, the row softmax on chosen logits.  Not part of the ABI in include/wekws_hip.h: the product library exports nothing outside the header.
 #pragma once
 
@@ -174,6 +174,40 @@ extern "C" int wekws_hip_debug_fsmn_route(const wekws_hip_desc* desc, const int*
   out[12] = wekws::effective_precision(*desc, f, o, call[3]);
   say(why, why_len, r.why_not ? r.why_not : "fsmn_f16");
   return WEKWS_HIP_OK;
+}
+// The weight blob's layout (blob_layout.h), WITHOUT a device (tests/test_blob_layout.py, hooks library only): desc: any descriptor
+// wekws_hip_blob_elems accepts.  out (int64, 4 per tensor): offset in floats, rows, cols, inner of every tensor in blob order, at most
+// max_tensors of them.  Returns the number of tensors of the blob, or WEKWS_HIP_EINVAL.
+extern "C" int wekws_hip_debug_blob_layout(const wekws_hip_desc* desc, int64_t* out, int max_tensors) {
+  if (!desc || !blob_elems(*desc) || (max_tensors > 0 && !out)) return WEKWS_HIP_EINVAL;
+  int n = 0;
+  wekws::for_each_tensor(wekws::blob_layout(*desc), [&](const wekws::BlobTensor& t) {
+    if (n < max_tensors) { out[4 * n] = t.off; out[4 * n + 1] = t.rows; out[4 * n + 2] = t.cols; out[4 * n + 3] = t.inner; }
+    ++n;
+  });
+  return n;
+}
+// ... and one tensor BY NAME, through the accessor the library's own code reads it with: `name` of block / layer `unit` (ignored
+// outside the units).  out[4] as above; a tensor the model does not have has rows = 0.  Returns 0, or WEKWS_HIP_EINVAL (unknown name).
+extern "C" int wekws_hip_debug_blob_tensor(const wekws_hip_desc* desc, const char* name, int unit, int64_t* out) {
+  if (!desc || !name || !out || !blob_elems(*desc)) return WEKWS_HIP_EINVAL;
+  const wekws::BlobLayout L = wekws::blob_layout(*desc);
+  const wekws::ConvWeights c = L.block(unit);
+  const wekws::GruWeights g = L.gru_layer(unit);
+  const wekws::FsmnWeights f = L.fsmn_layer(unit);
+  const struct { const char* name; wekws::BlobTensor t; } table[] = {
+      {"pre_w", L.pre_w()}, {"pre_b", L.pre_b()}, {"in1_w", L.in1_w()}, {"in1_b", L.in1_b()}, {"in2_w", L.in2_w()}, {"in2_b", L.in2_b()},
+      {"wd", c.wd}, {"bd", c.bd}, {"w1", c.w1}, {"b1", c.b1}, {"w2", c.w2}, {"b2", c.b2},
+      {"w_ih", g.w_ih}, {"w_hh", g.w_hh}, {"b_ih", g.b_ih}, {"b_hh", g.b_hh},
+      {"wproj", f.wproj}, {"taps", f.taps}, {"waff", f.waff}, {"baff", f.baff},
+      {"head_w", L.head_w()}, {"head_b", L.head_b()}, {"head_w2", L.head_w2()}, {"head_b2", L.head_b2()},
+      {"out1_w", L.out1_w()}, {"out1_b", L.out1_b()}, {"out2_w", L.out2_w()}, {"out2_b", L.out2_b()}};
+  for (const auto& e : table)
+    if (!std::strcmp(name, e.name)) {
+      out[0] = e.t.off; out[1] = e.t.rows; out[2] = e.t.cols; out[3] = e.t.inner;
+      return WEKWS_HIP_OK;
+    }
+  return WEKWS_HIP_EINVAL;
 }
 // the route of every tile of the calling thread's last forward: out[0] = path (0: no forward yet; 1: the conv routes of route.h;
 // 2: the any-shape path of generic.hip.h; 3: the GRU route of route.h -- one record; 4: the FSMN routes of route.h), out[1] =

@@ -205,14 +205,13 @@ def _bn_affine(sd, prefix):
     return s, t
 
 
-def pack(configs: Mapping, sd: Mapping) -> Tuple[dict, np.ndarray]:
-    """-> (descriptor dict with DESC_FIELDS, float32 blob)."""
+def _parts(configs: Mapping, sd: Mapping) -> Tuple[dict, List[Tuple[str, np.ndarray]]]:
+    """-> (parsed config, [(name, folded float64 tensor)] in blob order).  The names are those of the layout's accessors
+    (wekws_amd/csrc/blob_layout.h); tests/test_blob_layout.py holds the two against each other."""
     d = parse_config(configs)
     C, I = d["hdim"], d["idim"]
-    parts: List[np.ndarray] = []
-
     if d["kind"] == "fsmn":
-        return _pack_fsmn(d, sd)
+        return d, _fsmn_parts(d, sd)
 
     # ---- preprocessing (+ CMVN):  W (x - mean) * istd + b = (W * istd) x + (b - (W * istd) mean)
     if d["prep"] == "linear":
@@ -224,10 +223,11 @@ def pack(configs: Mapping, sd: Mapping) -> Tuple[dict, np.ndarray]:
         istd = _f64(sd, "global_cmvn.istd") if d["norm_var"] else np.ones(I)
         W = W * istd[None, :]
         b = b - W @ mean
-    parts += [W, b]
+    names, parts = ["pre_w", "pre_b"], [W, b]
 
     if d["kind"] == "gru":
         for l in range(d["num_layers"]):
+            names += ["w_ih", "w_hh", "b_ih", "b_hh"]
             parts += [_f64(sd, f"backbone.weight_ih_l{l}"), _f64(sd, f"backbone.weight_hh_l{l}"),
                       _f64(sd, f"backbone.bias_ih_l{l}"), _f64(sd, f"backbone.bias_hh_l{l}")]
     elif d["kind"] == "ds_tcn":
@@ -237,11 +237,13 @@ def pack(configs: Mapping, sd: Mapping) -> Tuple[dict, np.ndarray]:
             s2, t2 = _bn_affine(sd, p + "4")
             wd, bd = _f64(sd, p + "0.weight")[:, 0, :], _f64(sd, p + "0.bias")
             wp, bp = _f64(sd, p + "3.weight")[:, :, 0], _f64(sd, p + "3.bias")
+            names += ["wd", "bd", "w1", "b1"]
             parts += [wd * s1[:, None], bd * s1 + t1, wp * s2[:, None], bp * s2 + t2]
     elif d["kind"] == "tcn":
         for i in range(d["num_layers"]):
             p = f"backbone.network.{i}.cnn."
             s1, t1 = _bn_affine(sd, p + "1")
+            names += ["w1", "b1"]
             parts += [_f64(sd, p + "0.weight") * s1[:, None, None], _f64(sd, p + "0.bias") * s1 + t1]
     else:
         for p, _ in mdtc_blocks(d):
@@ -251,40 +253,51 @@ def pack(configs: Mapping, sd: Mapping) -> Tuple[dict, np.ndarray]:
             wd, bd = _f64(sd, p + "conv1.conv.weight")[:, 0, :], _f64(sd, p + "conv1.conv.bias")
             w1, b1 = _f64(sd, p + "conv1.pointwise.weight")[:, :, 0], _f64(sd, p + "conv1.pointwise.bias")
             w2, b2 = _f64(sd, p + "conv2.weight")[:, :, 0], _f64(sd, p + "conv2.bias")
+            names += ["wd", "bd", "w1", "b1", "w2", "b2"]
             parts += [wd * sa[:, None], bd * sa + ta, w1 * s1[:, None], b1 * s1 + t1, w2 * s2[:, None], b2 * s2 + t2]
 
     if d["head"] == HEAD["linear"]:
+        names += ["head_w", "head_b"]
         parts += [_f64(sd, "classifier.linear.weight"), _f64(sd, "classifier.linear.bias")]
     elif d["head"] in (HEAD["glob"], HEAD["last"]):
+        names += ["head_w", "head_b", "head_w2", "head_b2"]
         parts += [_f64(sd, "classifier.classifier.0.weight"), _f64(sd, "classifier.classifier.0.bias"),
                   _f64(sd, "classifier.classifier.3.weight"), _f64(sd, "classifier.classifier.3.bias")]
-    blob = np.concatenate([np.ravel(p) for p in parts]).astype(np.float32)
+    return d, list(zip(names, parts))
+
+
+def pack(configs: Mapping, sd: Mapping) -> Tuple[dict, np.ndarray]:
+    """-> (descriptor dict with DESC_FIELDS, float32 blob)."""
+    d, parts = _parts(configs, sd)
+    blob = np.concatenate([np.ravel(p) for _, p in parts]).astype(np.float32)
     desc = {k: int(d[k]) for k in DESC_FIELDS}
     return desc, np.ascontiguousarray(blob)
 
 
-def _pack_fsmn(d: dict, sd: Mapping) -> Tuple[dict, np.ndarray]:
+def _fsmn_parts(d: dict, sd: Mapping) -> List[Tuple[str, np.ndarray]]:
     """FSMN blob: in1 W(A1,I) b | in2 W(C,A1) b | per layer: Wp(D,C), taps(D, lo+ro), Wa(C,D), ba | out1 W(A2,C) b |
     out2 W(K,A2) b.  CMVN folds into in_linear1; the memory block's identity path (fsmn.py:236-237) folds into its
     taps: out[t] = sum_j taps[j] x_pad[t + j] with taps = [wl_0 .. wl_{lo-1} + 1 | wr_0 .. wr_{ro-1}]."""
-    I, lo, ro = d["idim"], d["kernel_size"], d["stack_size"]
+    I, lo = d["idim"], d["kernel_size"]
     W, b = _f64(sd, "backbone.in_linear1.linear.weight"), _f64(sd, "backbone.in_linear1.linear.bias")
     if d["cmvn"]:
         mean = _f64(sd, "global_cmvn.mean")
         istd = _f64(sd, "global_cmvn.istd") if d["norm_var"] else np.ones(I)
         W = W * istd[None, :]
         b = b - W @ mean
+    names = ["in1_w", "in1_b", "in2_w", "in2_b"]
     parts = [W, b, _f64(sd, "backbone.in_linear2.linear.weight"), _f64(sd, "backbone.in_linear2.linear.bias")]
     for l in range(d["num_layers"]):
         p = f"backbone.fsmn.{l}."
         taps = np.concatenate([_f64(sd, p + "1.conv_left.weight")[:, 0, :, 0],
                                _f64(sd, p + "1.conv_right.weight")[:, 0, :, 0]], axis=1)
         taps[:, lo - 1] += 1.0
+        names += ["wproj", "taps", "waff", "baff"]
         parts += [_f64(sd, p + "0.linear.weight"), taps, _f64(sd, p + "2.linear.weight"), _f64(sd, p + "2.linear.bias")]
+    names += ["out1_w", "out1_b", "out2_w", "out2_b"]
     parts += [_f64(sd, "backbone.out_linear1.linear.weight"), _f64(sd, "backbone.out_linear1.linear.bias"),
               _f64(sd, "backbone.out_linear2.linear.weight"), _f64(sd, "backbone.out_linear2.linear.bias")]
-    blob = np.concatenate([np.ravel(p) for p in parts]).astype(np.float32)
-    return {k: int(d[k]) for k in DESC_FIELDS}, np.ascontiguousarray(blob)
+    return list(zip(names, parts))
 
 
 def blob_elems(desc: Mapping) -> int:
