@@ -1,7 +1,7 @@
 // Probe (round 6, second version): the EXACT instruction sequence of the failing ds64_g4 build's head -- four register moves, seven
 // v_pk_fma_f32 "step 1" (op_sel_hi:[1,0,0], seven destinations), then the seven "step 2" of which the first is
 // v_pk_fma_f32 d, a, b, d op_sel:[0,1,0] -- beside waves of the same SIMD that run MFMA chains.  In the failing build lanes 48..63 of
-// that one instruction's LOW result came back without the product (the value of step 1), rarely; tools/probe/d64_dump.py.
+// that one instruction's LOW result came back without the product (the value of step 1), rarely; DESIGN.md 3.8.
 //   hipcc -O3 --offload-arch=gfx950 tools/probe/pk_opsel_probe2.hip -o /tmp/pk_probe2
 #include <hip/hip_runtime.h>
 #include <cstdio>

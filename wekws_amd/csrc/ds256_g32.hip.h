@@ -15,7 +15,8 @@
 // of a group's four MFMAs with one ds_read_b128, channel order inside a group = the host image's (put_packed_a: the A
 // fragment of step s, lane l is W[16 ot + (l & 15)][16 g + 4 s + (l >> 4)]).
 #pragma once
-#include "ds256_g16.hip.h"
+#include "ds256_g16.hip.h"                                   // (kernel skeleton, feature items, stamps)
+#include "lane_tile.hip.h"
 
 namespace wekws {
 
@@ -38,7 +39,7 @@ __device__ __forceinline__ void g32_mfma_group(f32x4 (&acc)[NT], const float4 a,
 }
 
 // Depthwise conv + folded BN + ReLU of the channel-row pair (2 P_, 2 P_ + 1) of the lane's four, all NT frames of the lane
-// (g16_dw_pair without the split): row r of column 16 tt + l15 is one float of item (group = wave, lq = r, column),
+// (dw_pair of lane_tile.hip.h without the split): row r of column 16 tt + l15 is one float of item (group = wave, lq = r, column),
 // step slot = the lane's own lq
 template <int D, int P_, int NT>
 __device__ __forceinline__ void g32_dw_pair(const f32x4 (&hv)[NT], const float* taps_o0, char* pst) {

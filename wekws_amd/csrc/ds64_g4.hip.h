@@ -11,14 +11,14 @@
 // 0.07 of the matrix roofline and 0.08 of HBM (round-3 review).  Here wave w owns output channels 16 w .. 16 w + 15 for all
 // frames in the accumulator layout of the 1x1 convolution, the residual tile lives in 4 NT registers, LDS holds the 28 KB of
 // operand planes, and FOUR independent workgroups share a CU (<= 128 registers): the overlap comes from the hardware scheduler.
-//   * frames lane-major with the utterance's END aligned to a lane boundary (mdtc64_g4.hip.h): the cache slices (the last
-//     7 d frames of every block's input) are whole lanes plus one lane's tail registers;
-//   * depthwise taps (k = 8): g16_dw_rows of ds256_g16.hip.h, one v_fmac_f32_dpp row_shr per tap and output;
+//   * frames lane-major (lane_tile.hip.h) with the utterance's END aligned to a lane boundary (mdtc64_g4.hip.h): the cache
+//     slices (the last 7 d frames of every block's input) are whole lanes plus one lane's tail registers;
+//   * depthwise taps (k = 8): g16_dw_rows of lane_tile.hip.h, one v_fmac_f32_dpp row_shr per tap and output;
 //   * the keyword head (per-frame linear, one or two outputs) from the registers.
 // Every other call (incoming cache, other heads, wider features): the generic kernel.  Same operand scaling, same products,
 // same sums per output as the generic kernel's (block floating point: conv_stack_f16.hip.h); the head's sum order differs.
 #pragma once
-#include "mdtc64_g4.hip.h"
+#include "g4_tile.hip.h"
 
 namespace wekws {
 
@@ -94,9 +94,6 @@ __global__ __launch_bounds__(kG4Threads, 4) void ds64_g4_kernel(const StackParam
 #pragma unroll
     for (int tt = 0; tt < NT; ++tt) acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();                                         // the feature maximum is published
-#ifdef WEKWS_D64_EARLY                                        // (diagnosis builds only: the placement that used to bring the rare wrong posteriors back)
-    if (amax_inputs_bad(amax_cells)) { nf_repair_call(A, blockIdx.x); return; }
-#endif
     float cpre;
     const float sx = pow2_scale(amax_read(amax_cells), &cpre);
     for (int k0 = 0; k0 < nk; k0 += 2) {
@@ -156,13 +153,10 @@ __global__ __launch_bounds__(kG4Threads, 4) void ds64_g4_kernel(const StackParam
     bd.b1 = __builtin_amdgcn_readfirstlane(bd.b1);
     const int pad = bd.pad;
     if (bi + 1 < P.nblocks) stage_taps(bi + 1, laneb);
-    auto uni = [](float v) __attribute__((always_inline)) {
-      return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
-    };
     float c1v;
-    const float au = CTX ? fmaxf(amax_read(amax_cells + 2 + bi), amax_read(amax_cells + 1)) : amax_read(amax_cells + 2 + bi);
-    const float sa = uni(pow2_scale(fmaf(bd.dw_alpha, au, bd.dw_beta), &c1v));
-    const float c1 = uni(c1v * bd.inv_s1);
+    const float au = g4_input_amax<CTX>(amax_cells, bi);
+    const float sa = g4_uni(pow2_scale(fmaf(bd.dw_alpha, au, bd.dw_beta), &c1v));
+    const float c1 = g4_uni(c1v * bd.inv_s1);
 
     // ---- CTX: the block's left context from its slice of the incoming cache (position q = NT lane + tt holds frame q - off;
     //      frame f < 0 is slice column pad + f): lane p of cx = lane p - 16 of the tile, lane 0's registers tt < off
@@ -258,7 +252,7 @@ __global__ __launch_bounds__(kG4Threads, 4) void ds64_g4_kernel(const StackParam
   //      1e-2 off in ONE output whenever several workgroups shared the CU, and could only move the effect around (where the sums
   //      were computed, where the non-finite check sat, the register budget).  Round 6 found it: the compiler had lowered this chain
   //      to v_pk_fma_f32 ... op_sel:[0,1,0], and gfx950 returns lanes 48..63 of that instruction's low result without the product
-  //      while another workgroup's waves issue MFMAs on the SIMD (tools/probe/d64_dump.py, pk_opsel_probe4.hip).
+  //      while another workgroup's waves issue MFMAs on the SIMD (tools/probe/pk_opsel_probe4.hip).
   {
     const int o0b = o0;
     {
@@ -272,14 +266,6 @@ __global__ __launch_bounds__(kG4Threads, 4) void ds64_g4_kernel(const StackParam
         head_fma4(pp, hw.x, hw.y, hw.z, hw.w, hv[tt]);
         yp[tt][0] = pp.x; yp[tt][1] = pp.y;
       }
-#ifdef WEKWS_D64_DUMP                                         // (diagnosis builds only: the head's inputs and partial sums over the returned cache)
-      if (A.out_cache) {
-        float* dbg = A.out_cache + int64_t(b) * C * Pc + threadIdx.x * 16;
-        dbg[0] = yp[0][0]; dbg[1] = yp[0][1]; dbg[2] = hv[0][0]; dbg[3] = hv[0][1]; dbg[4] = hv[0][2]; dbg[5] = hv[0][3];
-        dbg[6] = w0.x; dbg[7] = w0.y; dbg[8] = w0.z; dbg[9] = w0.w;
-        if constexpr (NT > 1) { dbg[10] = yp[1][0]; dbg[11] = yp[1][1]; }
-      }
-#endif
     }
   }
   // ---- keyword head (per-frame linear, one or two outputs; classifier.py:63-67): the 16 partial sums per output (4 waves x 4
@@ -298,12 +284,6 @@ __global__ __launch_bounds__(kG4Threads, 4) void ds64_g4_kernel(const StackParam
     const int t = (th >> 1) - off, k = th & 1;               // thread = (column, output)
     if (th < 2 * TT && t >= 0 && t < T && k < K) {
       float v = W[P.head_b + k];
-#ifdef WEKWS_D64_DUMP
-      if (A.out_cache && th < 28) {                            // columns 0 .. 13 (lane 0's frames), both outputs: the 16 partial rows each
-        float* dbg = A.out_cache + int64_t(b) * C * Pc + 4096 + th * 16;
-        for (int i = 0; i < 16; ++i) dbg[i] = part[i * PS + th];
-      }
-#endif
 #pragma unroll
       for (int i = 0; i < 16; ++i) v += part[i * PS + th];
       if (P.sigmoid) v = sigmoidf_(v);
@@ -313,7 +293,7 @@ __global__ __launch_bounds__(kG4Threads, 4) void ds64_g4_kernel(const StackParam
   // A NaN / Inf feature or cache element (cells [0] / [1], untouched since the top, at or above 0x7f800000): what the kernel
   // computed for this utterance is garbage (and touched nothing else); the utterance is re-computed with the reference's arithmetic
   // HERE, where nothing is live.  (An early exit near the top is equally right since the head's packed FMAs are written out --
-  // -DWEKWS_D64_EARLY builds that placement, the one that used to bring the rare wrong posteriors back: 0 differing utterances in
+  // that placement is the one that used to bring the rare wrong posteriors back, DESIGN.md 3.8: 0 differing utterances in
   // tools/probe/d64_diag.py now -- but saves nothing for finite inputs.)
   if (amax_inputs_bad(amax_cells)) {                         // (workgroup-uniform, scalar)
     __syncthreads();

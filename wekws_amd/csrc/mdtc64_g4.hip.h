@@ -13,7 +13,7 @@
 // the depthwise output and the mid tile) plus taps -- so FOUR workgroups fit a CU (128 registers, 4 x 32 KB) and run
 // independently: while one utterance waits at a barrier or for a weight fragment, the other three use the units.  The
 // overlap the 16-wave kernels could not get out of waves in lockstep comes from the hardware scheduler for free.
-//   * frame layout as in ds256_g16.hip.h: column 16 tt + l of the matrix products holds frame NT l + tt - off, i.e. every
+//   * frame layout of lane_tile.hip.h: column 16 tt + l of the matrix products holds frame NT l + tt - off, i.e. every
 //     lane owns NT consecutive frames; off = (-T) mod NT aligns the END of the utterance with a lane boundary (frames below
 //     zero are kept at zero = the causal left context), so the cache slices (the last 4 d frames) are whole lanes plus one
 //     lane's last (4 d) mod NT registers: wide stores;
@@ -25,97 +25,9 @@
 //   * the keyword head (per-frame linear, one or two outputs) from the registers; every other head, inputs with a cache,
 //     feature widths above 96: mdtc64_w16.
 #pragma once
-#include "ds256_g16.hip.h"
-#include "mdtc64_w16.hip.h"
+#include "g4_tile.hip.h"
 
 namespace wekws {
-
-constexpr int kG4Threads = 256;
-
-// scale + split of TWO values (channel rows 2 p, 2 p + 1 of one column) into one packed hi and one packed lo register
-// (g16_split_pair without the ReLU)
-template <bool SPLIT>
-__device__ __forceinline__ void g4_split_pair(float v0, float v1, float s, unsigned& ph, unsigned& pl) {
-  const float t0 = v0 * s, t1 = v1 * s;
-  const g16_f16x2 h = __builtin_convertvector(g16_f32x2{t0, t1}, g16_f16x2);
-  ph = __builtin_bit_cast(unsigned, h);
-  if constexpr (SPLIT) {
-    const float d0 = t0 - static_cast<float>(h[0]), d1 = t1 - static_cast<float>(h[1]);
-    pl = __builtin_bit_cast(unsigned, __builtin_convertvector(g16_f32x2{d0, d1}, g16_f16x2));
-  }
-}
-
-// Depthwise dilated conv + folded BN (no ReLU) of the channel-row pair (2 P_, 2 P_ + 1) of the lane's four, all NT frames of
-// the lane; taps of a channel: 8-float record {w0 .. w4, bias, -, -}; tap j multiplies the frame (4 - j) dilations back
-template <int D, int P_, int NT, bool SPLIT, bool CTX = false>
-__device__ __forceinline__ void g4_dw_pair(const f32x4 (&hv)[NT], const f32x4 (&cx)[NT], const float* taps_o0, float sa, char* pst, int lo_off) {
-  const float4* src = reinterpret_cast<const float4*>(taps_o0 + 2 * P_ * 8);
-  const float4 a0 = src[0], a1 = src[1], b0 = src[2], b1 = src[3];
-  constexpr auto tiles = std::make_integer_sequence<int, NT>{};
-  constexpr int RA = 2 * P_, RB = 2 * P_ + 1;
-  float oa[NT], ob[NT];
-#pragma unroll
-  for (int tt = 0; tt < NT; ++tt) { oa[tt] = a1.y; ob[tt] = b1.y; }
-  if constexpr (CTX) {   // (an incoming cache: the taps that leave the 16-lane row continue in the context tile, ds256_g16.hip.h)
-    g16_tapc_tiles<4 * D, NT, RA>(oa, hv, cx, a0.x, tiles); g16_tapc_tiles<4 * D, NT, RB>(ob, hv, cx, b0.x, tiles);
-    g16_tapc_tiles<3 * D, NT, RA>(oa, hv, cx, a0.y, tiles); g16_tapc_tiles<3 * D, NT, RB>(ob, hv, cx, b0.y, tiles);
-    g16_tapc_tiles<2 * D, NT, RA>(oa, hv, cx, a0.z, tiles); g16_tapc_tiles<2 * D, NT, RB>(ob, hv, cx, b0.z, tiles);
-    g16_tapc_tiles<1 * D, NT, RA>(oa, hv, cx, a0.w, tiles); g16_tapc_tiles<1 * D, NT, RB>(ob, hv, cx, b0.w, tiles);
-    g16_tapc_tiles<0, NT, RA>(oa, hv, cx, a1.x, tiles);     g16_tapc_tiles<0, NT, RB>(ob, hv, cx, b1.x, tiles);
-  } else {
-  g16_tap_tiles<4 * D, NT, RA>(oa, hv, a0.x, tiles); g16_tap_tiles<4 * D, NT, RB>(ob, hv, b0.x, tiles);
-  g16_tap_tiles<3 * D, NT, RA>(oa, hv, a0.y, tiles); g16_tap_tiles<3 * D, NT, RB>(ob, hv, b0.y, tiles);
-  g16_tap_tiles<2 * D, NT, RA>(oa, hv, a0.z, tiles); g16_tap_tiles<2 * D, NT, RB>(ob, hv, b0.z, tiles);
-  g16_tap_tiles<1 * D, NT, RA>(oa, hv, a0.w, tiles); g16_tap_tiles<1 * D, NT, RB>(ob, hv, b0.w, tiles);
-  g16_tap_tiles<0, NT, RA>(oa, hv, a1.x, tiles);     g16_tap_tiles<0, NT, RB>(ob, hv, b1.x, tiles);
-  }
-#pragma unroll
-  for (int tt = 0; tt < NT; ++tt) {
-    // the pair's two halves of column 16 tt + l15: one 4-byte store per plane (holding them for an 8-byte store with the
-    // other pair costs 2 NT registers through the second pair's taps -- the kernel is at the 128-register limit)
-    unsigned ph, pl;
-    g4_split_pair<SPLIT>(oa[tt], ob[tt], sa, ph, pl);
-    *reinterpret_cast<unsigned*>(pst + tt * 256 + P_ * 4) = ph;
-    if constexpr (SPLIT) *reinterpret_cast<unsigned*>(pst + lo_off + tt * 256 + P_ * 4) = pl;
-  }
-}
-template <int D, int NT, bool SPLIT, bool CTX = false>
-__device__ __forceinline__ void g4_dw_rows(const f32x4 (&hv)[NT], const f32x4 (&cx)[NT], const float* taps_o0, float sa, char* pst, int lo_off) {
-  g4_dw_pair<D, 0, NT, SPLIT, CTX>(hv, cx, taps_o0, sa, pst, lo_off);
-  g4_dw_pair<D, 1, NT, SPLIT, CTX>(hv, cx, taps_o0, sa, pst, lo_off);
-}
-template <int D, int NT, bool SPLIT>
-__device__ __forceinline__ void g4_dw_rows(const f32x4 (&hv)[NT], const float* taps_o0, float sa, char* pst, int lo_off) {
-  g4_dw_rows<D, NT, SPLIT, false>(hv, hv, taps_o0, sa, pst, lo_off);
-}
-
-// The last S registers of row r (frames NT l + NT - S .. NT l + NT - 1 of the lane) to S consecutive floats
-template <int NT, int S>
-__device__ __forceinline__ void g4_store_tail(float* dst, const f32x4 (&hv)[NT], int r) {
-  struct __attribute__((packed, aligned(4))) V4 { float v[4]; };
-  struct __attribute__((packed, aligned(4))) V3 { float v[3]; };
-  struct __attribute__((packed, aligned(4))) V2 { float v[2]; };
-  static_assert(S >= 1 && S < NT, "a proper suffix");
-  constexpr int F = NT - S;
-  if constexpr (S >= 4) {
-    *reinterpret_cast<V4*>(dst) = V4{{hv[F][r], hv[F + 1][r], hv[F + 2][r], hv[F + 3][r]}};
-    if constexpr (S == 5) dst[4] = hv[F + 4][r];
-    if constexpr (S == 6) *reinterpret_cast<V2*>(dst + 4) = V2{{hv[F + 4][r], hv[F + 5][r]}};
-  } else if constexpr (S == 3) {
-    *reinterpret_cast<V3*>(dst) = V3{{hv[F][r], hv[F + 1][r], hv[F + 2][r]}};
-  } else if constexpr (S == 2) {
-    *reinterpret_cast<V2*>(dst) = V2{{hv[F][r], hv[F + 1][r]}};
-  } else {
-    dst[0] = hv[F][r];
-  }
-}
-template <int NT, int S = 1>
-__device__ __forceinline__ void g4_store_tail_n(int s, float* dst, const f32x4 (&hv)[NT], int r) {
-  if constexpr (S < NT) {
-    if (s == S) g4_store_tail<NT, S>(dst, hv, r);
-    else g4_store_tail_n<NT, S + 1>(s, dst, hv, r);
-  }
-}
 
 // POOLED: the head is GlobalClassifier / LastClassifier (classifier.py:26-28, :38-40) instead of the per-frame linear one.
 // ALIGNED: NT divides T (the 98-frame utterance at NT = 7), i.e. off = 0 at compile time: no frames below zero, so none of
@@ -287,16 +199,13 @@ __global__ __launch_bounds__(C * 4, 4) void mdtc_g4_kernel(const StackParams P, 
     // ---- operand scales (conv_stack_f16.hip.h): the depthwise rows are bounded through the maximum of the input tile,
     //      the mid tile through the bound chained behind it (BlockDesc::mid_alpha)
     //      (wave-uniform values, moved to scalar registers: the kernel is at the 128-register limit)
-    auto uni = [](float v) __attribute__((always_inline)) {
-      return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v)));
-    };
     float c1v, c2v;
-    const float au = CTX ? fmaxf(amax_read(amax_cells + 2 + bi), amax_read(amax_cells + 1)) : amax_read(amax_cells + 2 + bi);
+    const float au = g4_input_amax<CTX>(amax_cells, bi);
     const float ba = fmaf(bd.dw_alpha, au, bd.dw_beta);
-    const float sa = uni(pow2_scale(ba, &c1v));
-    const float c1 = uni(c1v * bd.inv_s1);
-    const float sm = uni(pow2_scale(fmaf(bd.mid_alpha, ba, bd.mid_beta), &c2v));
-    const float c2 = uni(c2v * bd.inv_s2);
+    const float sa = g4_uni(pow2_scale(ba, &c1v));
+    const float c1 = g4_uni(c1v * bd.inv_s1);
+    const float sm = g4_uni(pow2_scale(fmaf(bd.mid_alpha, ba, bd.mid_beta), &c2v));
+    const float c2 = g4_uni(c2v * bd.inv_s2);
 
     // ---- CTX: the block's left context from its slice of the incoming cache.  Position q = NT lane + tt holds frame q - off;
     //      frame f < 0 is slice column pad + f.  Lane p of cx holds lane p - 16 of the tile (whole lanes as 28-byte runs where
@@ -379,7 +288,7 @@ __global__ __launch_bounds__(C * 4, 4) void mdtc_g4_kernel(const StackParams P, 
 
     // ---- mid = ReLU(BN1(pointwise)) written in operand order over them (mdtc.py:113-114); its scale sm is a power of two
     //      and positive, so ReLU(acc c1 + b) sm = ReLU(acc (c1 sm) + b sm) bit for bit: folded into the constants
-    const float c1s = uni(c1 * sm);
+    const float c1s = g4_uni(c1 * sm);
     const float4 b1s = float4{bias1.x * sm, bias1.y * sm, bias1.z * sm, bias1.w * sm};
 #pragma unroll
     for (int tt = 0; tt < NT; ++tt) {
