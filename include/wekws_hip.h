@@ -276,6 +276,53 @@ int wekws_hip_forward(wekws_hip_model* m, const float* x, int B, int T, const fl
                       float* y, float* out_cache, int softmax, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * The streaming step for many streams at once  --  KeyWordSpotter.forward's model call with its carried cache
+ * (wekws/bin/stream_kws_ctc.py:486-487, `logits, self.in_cache = self.model(feats, self.in_cache)`), for any subset of the
+ * streams of a pool in one call, every row with its own number of frames.  It sits between wekws_hip_stream_frontend_push, whose
+ * `frames` it takes as they are, and wekws_hip_ctc_kws_step: a C caller has the whole pipeline, PCM in, detections out.
+ *
+ * The pool owns the streams' caches: (2, max_streams, wekws_hip_cache_elems(m, 1)) floats.  Every stream has two planes, one of
+ * them live; a step reads the live plane and writes the other one, and the host flips the stream's parity bit in call order,
+ * which is stream order.  No kernel reads and writes the same bytes (out_cache must not alias in_cache, as above), and a
+ * stream that a call skips or leaves out keeps its plane.  All zeros is the empty-cache sentinel of every backbone.
+ * A pool belongs to the model it was created for and must be destroyed before it.  Calls on one pool are serialised by a mutex and by
+ * the caller's stream: use one stream per pool.
+ * ------------------------------------------------------------------------------------------*/
+typedef struct wekws_hip_stream_cache wekws_hip_stream_cache;
+int wekws_hip_stream_cache_create(wekws_hip_model* m, int max_streams, wekws_hip_stream_cache** out);
+void wekws_hip_stream_cache_destroy(wekws_hip_stream_cache* p);
+/* ids: n stream ids, HOST int32 (NULL = every stream of the pool): those streams start from the empty-cache sentinel again.
+ * A bad id returns WEKWS_HIP_EINVAL and resets nothing. */
+int wekws_hip_stream_cache_reset(wekws_hip_stream_cache* p, const int32_t* ids, int n, void* stream);
+/* One stream's live cache, in wekws_hip_forward's geometry for B = 1 (wekws_hip_cache_elems(m, 1) floats), to / from a device
+ * buffer; ordered on `stream` like every other call. */
+int wekws_hip_stream_cache_read(wekws_hip_stream_cache* p, int id, float* out, void* stream);
+int wekws_hip_stream_cache_write(wekws_hip_stream_cache* p, int id, const float* in, void* stream);
+/*
+ * Row b of x (B, Tcap, idim) continues stream stream_ids[b] with its first frames[b] frames.
+ *   stream_ids, frames  (B) HOST int32, as wekws_hip_stream_frontend_push takes and returns them; distinct ids, any subset of the
+ *                       pool in any order.  frames[b] <= 0 (held, or nothing new): the row is skipped -- its stream's cache and its
+ *                       row of y stay as they were
+ *   y                   (B, Tcap, odim) device, or (B, odim) for GLOBAL / LAST heads: row b receives its frames[b] rows (its one row),
+ *                       the rest is left as it was
+ *   softmax             as for wekws_hip_forward, over the rows the call writes
+ * A row's result is what wekws_hip_forward gives for that row alone with frames[b] frames and the stream's cache.
+ * The whole call is checked on the host first: a bad or repeated id, frames[b] > Tcap, more rows than the pool has streams, or a
+ * pool created for another model returns WEKWS_HIP_EINVAL (wekws_hip_last_error names the row), launches nothing and changes no
+ * stream.  The per-row table travels to the device in stream order through a ring of pinned tables, so calls may be queued back to
+ * back: the call does not synchronise, and does not allocate on the table-driven path below.  NOT inside a stream capture
+ * (WEKWS_HIP_EINVAL): the table of a captured call would be rewritten by the next one.
+ * Which kernels run (csrc/route.h: plan_streams):
+ *   - DS-TCN hidden 256 with Tcap <= 16, and the FSMN kernel with Tcap within its tile: ONE launch that reads every row's frame
+ *     count and cache planes from the table -- no copy of a cache besides the kernel's own read and write;
+ *   - every other model, and longer rows: the rows are bucketed by frame count, and per bucket gathered out of the pool, run through
+ *     wekws_hip_forward's kernels and scattered back, inside the library.  Its scratch grows on demand (one synchronisation), like a
+ *     model's workspace.
+ */
+int wekws_hip_forward_streams(wekws_hip_model* m, wekws_hip_stream_cache* p, const float* x, int B, int Tcap,
+                              const int32_t* stream_ids, const int32_t* frames, float* y, int softmax, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * Fbank front-end  --  replaces wenet::Fbank::Compute (runtime/core/frontend/fbank.h:138-198)
  * with the framing rule of FeaturePipeline::AcceptWaveform (feature_pipeline.cc:30-47).
  * ------------------------------------------------------------------------------------------*/

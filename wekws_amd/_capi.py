@@ -63,6 +63,13 @@ SIGNATURES = {
     "wekws_hip_forward_status": (C.c_int, [C.c_void_p, C.c_void_p]),
     "wekws_hip_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_void_p]),
+    "wekws_hip_stream_cache_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "wekws_hip_stream_cache_destroy": (None, [C.c_void_p]),
+    "wekws_hip_stream_cache_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "wekws_hip_stream_cache_read": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "wekws_hip_stream_cache_write": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "wekws_hip_forward_streams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_void_p]),
     "wekws_hip_fbank_create": (C.c_int, [C.POINTER(FbankCfg), C.c_int, C.POINTER(C.c_void_p)]),
     "wekws_hip_fbank_destroy": (None, [C.c_void_p]),
     "wekws_hip_fbank_num_frames": (C.c_int, [C.c_void_p, C.c_int]),

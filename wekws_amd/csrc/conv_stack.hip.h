@@ -140,6 +140,18 @@ struct StackParams {
   float head_inv_s;         // same for a matrix-core classifier (head_a16: ds256_mm, dense_stack_f16)
 };
 
+// One live row of a table-driven launch (wekws_hip_forward_streams): the row's own features, frame count, output rows and the two
+// planes of its stream's cache in the pool -- `in` the live one, `out` the other (never the same bytes).  The host writes the
+// table; it reaches the device in stream order.
+struct StreamRow {
+  const float* x;         // the row's first frame
+  const float* in_cache;  // the stream's live plane
+  float* out_cache;       // its other plane
+  float* y;               // the row's first output row (pooled heads: its one row)
+  int32_t T;              // frames of the row (>= 1)
+  int32_t yrows;          // rows of y the call writes for it: T, or 1 for pooled heads
+};
+
 struct CallArgs {
   const float* x;         // first frame of this tile, utterance 0
   int64_t xs_b;           // floats between utterances in x
@@ -154,7 +166,37 @@ struct CallArgs {
   int32_t first_tile, last_tile;
   int32_t head_slices;    // ds256_mm, CTC-sized heads: gridDim.y workgroups per utterance share the head's o-tiles (0/1: off)
   const NfCtx* nf;        // utterances with a non-finite input are re-computed in exact IEEE f32 (nonfinite.hip.h)
+  const StreamRow* rows;  // table-driven launches only: workgroup w runs rows[w] -- x, y, T and the caches above are then unused
 };
+
+// An entry of a launch table at a workgroup-uniform address, read through the constant address space: the table is written before
+// the launch, so the entry arrives in scalar registers like the kernel's arguments do, not in a vector register per lane.
+template <class V>
+__device__ __forceinline__ V load_uniform(const V* p) {
+  static_assert(sizeof(V) % 4 == 0, "whole dwords");
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef const __attribute__((address_space(4))) uint32_t* ConstWords;
+  const ConstWords src = (ConstWords)(uintptr_t)p;
+  uint32_t w[sizeof(V) / 4];
+#pragma unroll
+  for (unsigned i = 0; i < sizeof(V) / 4; ++i) w[i] = src[i];
+  V v;
+  __builtin_memcpy(&v, w, sizeof(V));
+  return v;
+#else
+  return *p;
+#endif
+}
+
+// The arguments of workgroup w of a table-driven launch, as a call of ONE utterance (b = 0): its row's addresses and frame
+// count.  Everything behind it -- the classifier, the non-finite repair -- indexes with them as it does for any other call.
+__device__ __forceinline__ CallArgs row_call_args(const CallArgs& A, int w) {
+  const StreamRow r = load_uniform(A.rows + w);
+  CallArgs a = A;
+  a.x = r.x; a.in_cache = r.in_cache; a.out_cache = r.out_cache; a.y = r.y;
+  a.B = 1; a.T = r.T; a.T_total = r.T;
+  return a;
+}
 
 // Utterance b of this call has a NaN / Inf in its features or incoming cache: the reference's arithmetic instead of the kernel's.
 // NOT inlined: one copy per translation unit, called from a cold branch with nothing live (arguments by value, in registers).
@@ -780,11 +822,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_stack_kernel(const StackPara
 // row -- online (max, rescaled sum) with 16-byte loads through a 4-byte-aligned type (rows of an odd-width matrix are
 // only dword aligned), then normalise in place.  Non-finite logits as torch.softmax has them: a class masked with -Inf
 // adds nothing and gets 0; a NaN or +Inf anywhere, or -Inf everywhere, makes the whole row NaN.
-static __global__ __attribute__((unused)) void softmax_rows_kernel(float* y, int64_t rows, int K) {
-  const int64_t row = int64_t(blockIdx.x) * (blockDim.x / 64) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const int lane = threadIdx.x & 63;
-  float* p = y + row * K;
+static __device__ __forceinline__ void softmax_row(float* p, int K, int lane) {
   struct __attribute__((packed, aligned(4))) V4 { float v[4]; };
   const int K4 = K & ~3;
   float mx = -INFINITY, s = 0.f;
@@ -812,6 +850,22 @@ static __global__ __attribute__((unused)) void softmax_rows_kernel(float* y, int
     *reinterpret_cast<V4*>(p + k) = q;
   }
   if (K4 + lane < K) p[K4 + lane] = __expf(p[K4 + lane] - gm) * inv;
+}
+static __global__ __attribute__((unused)) void softmax_rows_kernel(float* y, int64_t rows, int K) {
+  const int64_t row = int64_t(blockIdx.x) * (blockDim.x / 64) + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  softmax_row(y + row * K, K, threadIdx.x & 63);
+}
+// The same rows of a table-driven call: workgroup (w, i) takes rows 4 i .. 4 i + 3 of table row w, of its yrows.
+static __global__ __attribute__((unused)) void softmax_stream_rows_kernel(const StreamRow* rows, int K) {
+  const StreamRow r = rows[blockIdx.x];
+  const int t = int(blockIdx.y) * (blockDim.x / 64) + (threadIdx.x >> 6);
+  if (t >= r.yrows) return;
+  softmax_row(r.y + int64_t(t) * K, K, threadIdx.x & 63);
+}
+static inline __attribute__((unused)) bool launch_softmax_stream_rows(const StreamRow* rows, int nrows, int max_yrows, int K, hipStream_t stream) {
+  hipLaunchKernelGGL(softmax_stream_rows_kernel, dim3(unsigned(nrows), unsigned((max_yrows + 3) / 4)), dim3(256), 0, stream, rows, K);
+  return hipGetLastError() == hipSuccess;
 }
 // the one launch statement of softmax_rows_kernel: four rows (waves) per workgroup
 static inline __attribute__((unused)) bool launch_softmax_rows(float* y, int64_t rows, int K, hipStream_t stream) {

@@ -30,8 +30,14 @@
 
 namespace wekws {
 
-template <bool SPLIT>
-__global__ __launch_bounds__(kW16Threads) void ds256_stream_kernel(const StackParams P, const CallArgs A) {
+//
+// ROWS (wekws_hip_forward_streams): the same kernel driven by a table -- workgroup w runs the StreamRow w, whose frame count,
+// feature and output rows and two cache planes replace the call's (conv_stack.hip.h: row_call_args).  T was already uniform
+// across the workgroup; nothing else changes, so a row's result is the uniform call's on that row alone, bit for bit.
+template <bool SPLIT, bool ROWS = false>
+__global__ __launch_bounds__(kW16Threads) void ds256_stream_kernel(const StackParams P, const CallArgs A_) {
+  const CallArgs rowA = ROWS ? row_call_args(A_, blockIdx.x) : CallArgs{};
+  const CallArgs& A = ROWS ? rowA : A_;
   using G = W16Geom<1>;
   constexpr int C = G::C, SS = G::SS, TT = G::TT, PB = G::PB, KS = 8, NT = 1;
   extern __shared__ __attribute__((aligned(16))) float strm_lds[];
@@ -44,7 +50,7 @@ __global__ __launch_bounds__(kW16Threads) void ds256_stream_kernel(const StackPa
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, lq = lane >> 4;
   const int T = A.T;                                         // <= 16
-  const int b = blockIdx.x;                                  // one stream per workgroup
+  const int b = ROWS ? 0 : blockIdx.x;                       // one stream per workgroup
   const float* __restrict__ W = P.w;
   const int Pc = P.cache_len;
   const int pc = tid >> 2, g = tid & 3;                      // producer: channel, quarter
@@ -303,5 +309,7 @@ inline size_t ds256_stream_lds_bytes(int cache_len) {       // slab 16 KB + chun
 
 // Runs the ds256_stream route (a chunk of <= 16 frames, the stream's cache in LDS).  Defined in ds256_stream.hip.
 int launch_ds256_stream(const Route& r, const StackParams& P, const CallArgs& A, hipStream_t stream);
+// ... and its table-driven variant: r.grid rows of A.rows, one workgroup each.  Defined in ds256_stream_rows.hip.
+int launch_ds256_stream_rows(const Route& r, const StackParams& P, const CallArgs& A, hipStream_t stream);
 
 }  // namespace wekws

@@ -92,6 +92,15 @@ struct FsmnArgs {
   int32_t B, T;           // T: valid frames in this tile (1..16*NT)
   int32_t head_slices;    // >= 1: gridDim.y workgroups per tile share the o-tiles of out_linear2 (small calls, below)
   const NfCtx* nf;        // utterances with a non-finite input are re-computed in exact IEEE f32 (nonfinite.hip.h)
+  const StreamRow* rows;  // table-driven launches only (wekws_hip_forward_streams): the call's live rows ...
+  const struct FsmnGroup* groups;   // ... and, per workgroup, its frame count and which rows fill its U slots
+};
+// One workgroup of a table-driven launch: up to U rows of EQUAL frame count T (indices into FsmnArgs::rows; -1: an empty slot, which
+// the kernel treats as it treats b >= B)
+struct FsmnGroup {
+  int32_t T;
+  int32_t row[4];
+  int32_t reserved[3];
 };
 static __device__ __attribute__((noinline, unused)) void nf_repair_fsmn_call(const NfCtx* nf, const float* x, int64_t xs_b, const float* ic,
                                                                              float* oc, float* y, int64_t ys_b, int T, int b) {
@@ -209,7 +218,9 @@ __device__ __attribute__((always_inline)) void fsmn_gemm_held(const float* __res
 
 // NT frame tiles per workgroup = U utterances x NT / U tiles each (short inputs are packed U to a workgroup so that a
 // weight fragment, whose trip through the CU's 64 B/clk L1 path is the fixed cost of a workgroup, feeds NT MFMA tiles)
-template <int NT, int U>
+// ROWS (wekws_hip_forward_streams): workgroup w runs FsmnGroup w -- its frame count and the rows in its U slots come from the table,
+// every slot's features, output rows and two cache planes from its StreamRow (kept in LDS); the arithmetic is untouched.
+template <int NT, int U, bool ROWS = false>
 __global__ __launch_bounds__(kFsmnThreads) void fsmn_f16_kernel(const FsmnParams P, const FsmnArgs A) {
   constexpr int TT = 16 * NT, NTU = NT / U, TTU = 16 * NTU;
   static_assert(NTU * U == NT, "tiles split evenly over the packed utterances");
@@ -221,7 +232,22 @@ __global__ __launch_bounds__(kFsmnThreads) void fsmn_f16_kernel(const FsmnParams
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: o-tile loops and their branches go scalar
   const int l15 = lane & 15, lq = lane >> 4;
   const int b0 = blockIdx.x * U;                              // first utterance of this workgroup
-  const int T = A.T;
+  StreamRow* srow = nullptr;                                  // ROWS: the slots' rows (T = 0: an empty slot)
+  int T_ = A.T;
+  if constexpr (ROWS) {
+    __shared__ StreamRow slot_rows[U];
+    T_ = load_uniform(&A.groups[blockIdx.x].T);
+    if (tid < U) {
+      const int gi = A.groups[blockIdx.x].row[tid];
+      slot_rows[tid] = gi >= 0 ? A.rows[gi] : StreamRow{};
+    }
+    srow = slot_rows;
+  }
+  const int T = T_;
+  auto live = [&](int u) __attribute__((always_inline)) {
+    if constexpr (ROWS) return srow[u].T > 0;
+    else return b0 + u < A.B;
+  };
   const float* __restrict__ W = P.w;
   const int frag_off = (lq * TT + l15) * 16;
 
@@ -231,11 +257,16 @@ __global__ __launch_bounds__(kFsmnThreads) void fsmn_f16_kernel(const FsmnParams
   amax_zero<kFsmnThreads>(cells, U * kFsmnCells);
   __syncthreads();
   for (int u = 0; u < U; ++u)
-    if (b0 + u < A.B) {
+    if (live(u)) {
+      if constexpr (ROWS) {
+        amax_publish(cells + u * kFsmnCells, amax_span_bits<kFsmnThreads>(srow[u].x, T * P.idim, 0.f));
+        amax_publish(cells + u * kFsmnCells + 1, amax_span_bits<kFsmnThreads>(srow[u].in_cache, P.proj * P.P * P.nlayers, 0.f));
+      } else {
       amax_publish(cells + u * kFsmnCells, amax_span_bits<kFsmnThreads>(A.x + int64_t(b0 + u) * A.xs_b, T * P.idim, 0.f));
       if (A.in_cache)
         amax_publish(cells + u * kFsmnCells + 1,
                      amax_span_bits<kFsmnThreads>(A.in_cache + int64_t(b0 + u) * P.proj * P.P * P.nlayers, P.proj * P.P * P.nlayers, 0.f));
+      }
     }
   __syncthreads();                                           // the staging below scales x with its maximum
   {                                                          // a NaN / Inf feature or cache element among this workgroup's utterances:
@@ -245,7 +276,10 @@ __global__ __launch_bounds__(kFsmnThreads) void fsmn_f16_kernel(const FsmnParams
     if (bad) {
       if (blockIdx.y == 0)                                   // (head slices: every slice sees it, one of them re-computes)
         for (int u = 0; u < U; ++u)
-          if (b0 + u < A.B) nf_repair_fsmn_call(A.nf, A.x, A.xs_b, A.in_cache, A.out_cache, A.y, A.ys_b, T, b0 + u);
+          if (live(u)) {
+            if constexpr (ROWS) nf_repair_fsmn_call(A.nf, srow[u].x, 0, srow[u].in_cache, srow[u].out_cache, srow[u].y, 0, T, 0);
+            else nf_repair_fsmn_call(A.nf, A.x, A.xs_b, A.in_cache, A.out_cache, A.y, A.ys_b, T, b0 + u);
+          }
       return;
     }
   }
@@ -315,9 +349,11 @@ __global__ __launch_bounds__(kFsmnThreads) void fsmn_f16_kernel(const FsmnParams
       const int f = th * 8 + tl;                              // frame slot of the tile
       const int u = f / TTU, t = f - u * TTU;
       const int k0 = koct * 8;
-      const float* xr = A.x + int64_t(b0 + u) * A.xs_b + int64_t(t) * P.idim + k0;
+      const float* xr;
+      if constexpr (ROWS) xr = srow[u].x + int64_t(t) * P.idim + k0;
+      else xr = A.x + int64_t(b0 + u) * A.xs_b + int64_t(t) * P.idim + k0;
       f32x8 xv = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (t < T && b0 + u < A.B) {
+      if (t < T && live(u)) {
         if (xvec && k0 + 8 <= P.idim) {
           const f32x4 lo4 = *reinterpret_cast<const f32x4*>(xr), hi4 = *reinterpret_cast<const f32x4*>(xr + 4);
           xv = f32x8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
@@ -367,6 +403,9 @@ __global__ __launch_bounds__(kFsmnThreads) void fsmn_f16_kernel(const FsmnParams
         const int c = e / (U * per), r = e - c * (U * per);
         const int u = r / per, j = r - u * per;
         float v = 0.f;
+        if constexpr (ROWS) {
+          if (j < Pc && c < P.proj && live(u)) v = srow[u].in_cache[(int64_t(c) * Pc + j) * L + l];
+        } else
         if (j < Pc && A.in_cache && c < P.proj && b0 + u < A.B)
           v = A.in_cache[((int64_t(b0 + u) * P.proj + c) * Pc + j) * L + l];
         pt[c * SS + u * SEG + (j < Pc ? j : TTU + j)] = v;
@@ -437,10 +476,13 @@ __global__ __launch_bounds__(kFsmnThreads) void fsmn_f16_kernel(const FsmnParams
         }
       }
       // new cache = last P valid columns of x_pad
-      if (A.out_cache && blockIdx.y == 0) {               // head slices recompute the backbone; one of them hands over
+      if ((ROWS || A.out_cache) && blockIdx.y == 0) {     // head slices recompute the backbone; one of them hands over
         for (int e = tid; e < U * P.proj * Pc; e += kFsmnThreads) {
           const int u = e / (P.proj * Pc), r = e - u * (P.proj * Pc);
           const int c = r / Pc, j = r - c * Pc;
+          if constexpr (ROWS) {
+            if (live(u)) srow[u].out_cache[(int64_t(c) * Pc + j) * L + l] = pt[c * SS + u * SEG + T + j];
+          } else
           if (b0 + u < A.B)
             A.out_cache[((int64_t(b0 + u) * P.proj + c) * Pc + j) * L + l] = pt[c * SS + u * SEG + T + j];
         }
@@ -474,8 +516,10 @@ __global__ __launch_bounds__(kFsmnThreads) void fsmn_f16_kernel(const FsmnParams
                       for (int tt = 0; tt < NT; ++tt) {
                         const int u = tt / NTU, t = (tt % NTU) * 16 + l15;
                         const f32x4 v = acc[ow][tt] * cin[u] + bias[ow];
-                        float* yr = A.y + int64_t(b0 + u) * A.ys_b + int64_t(t) * K + o;
-                        const bool ok = t < T && b0 + u < A.B;
+                        float* yr;
+                        if constexpr (ROWS) yr = srow[u].y + int64_t(t) * K + o;
+                        else yr = A.y + int64_t(b0 + u) * A.ys_b + int64_t(t) * K + o;
+                        const bool ok = t < T && live(u);
                         if (whole) {
                           if (ok) *reinterpret_cast<F32x4U*>(yr) = F32x4U{{v[0], v[1], v[2], v[3]}};
                         } else if (ok) {
@@ -512,8 +556,22 @@ inline int launch_fsmn_nt(const FsmnRoute& r, const FsmnParams& P, const FsmnArg
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
+// The table-driven variant: r.grid workgroups of A.groups, r.head_slices workgroups each
+template <int NT, int U>
+inline int launch_fsmn_rows_nt(const FsmnRoute& r, const FsmnParams& P, const FsmnArgs& A, hipStream_t stream) {
+  const int lds = FsmnLds::make(P, 16 * NT, U).bytes();
+  if (lds > kFsmnLdsLimit || lds != r.lds_bytes || !A.rows || !A.groups || r.grid <= 0 || A.head_slices != r.head_slices) return -4;
+  static DynLdsGrant grant;
+  auto kern = fsmn_f16_kernel<NT, U, true>;
+  if (grant_dynamic_lds(kern, lds, grant)) return -3;
+  hipLaunchKernelGGL(kern, dim3(r.grid, r.head_slices > 1 ? r.head_slices : 1), dim3(kFsmnThreads), lds, stream, P, A);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 // runs a tile's route of select_fsmn_route (route.h): r.nt frame tiles per utterance, r.u utterances per workgroup (u in
 // {1, 2, 4}, nt * u <= 4); A.head_slices is the route's
 int launch_fsmn_f16(const FsmnRoute& r, const FsmnParams& P, const FsmnArgs& A, hipStream_t stream);
+// ... and of plan_streams (route.h): the same instances, driven by A.rows / A.groups.  Defined in fsmn_f16_rows.hip.
+int launch_fsmn_f16_rows(const FsmnRoute& r, const FsmnParams& P, const FsmnArgs& A, hipStream_t stream);
 
 }  // namespace wekws

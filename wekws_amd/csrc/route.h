@@ -10,7 +10,9 @@
 //     wavefront), its launch geometry, where the non-finite pass runs and the scratch bytes; gru_reserve_bytes() for a reservation;
 //   * fsmn_shape_plan() / select_fsmn_route(): the FSMN kernel's tile and, per tile, its frame tiles, utterances per workgroup, head
 //     slices, grid and LDS bytes;
-//   * effective_precision(): what wekws_hip_effective_precision reports, from the routes a model can take.
+//   * effective_precision(): what wekws_hip_effective_precision reports, from the routes a model can take;
+//   * plan_streams(): the plan of a wekws_hip_forward_streams call -- one table-driven launch (which kernel instance, which rows
+//     share a workgroup) or the grouped path (which rows share a bucket).
 // wekws_hip_forward (forward_conv / forward_gru / forward_fsmn) hands a route to its family's launcher, which executes it: the kernel variant, grid, threads and LDS from the
 // route.  A launcher tests no eligibility of its own; it only refuses (-4, an internal error) a route whose threads or LDS bytes are
 // not its kernel's or that names a variant it does not build.  So the geometry below restates every kernel header's (or the kernel
@@ -19,6 +21,8 @@
 // wekws_hip_debug_gru_route, wekws_hip_debug_fsmn_route); tests/test_hip_route_matrix.py checks the traced routes on the device.
 #pragma once
 #include <stdint.h>
+
+#include <algorithm>
 
 #include "../../include/wekws_hip.h"
 
@@ -651,6 +655,62 @@ inline FsmnRoute select_fsmn_route(const FsmnPlan& p, const wekws_hip_desc& d, c
   }
   r.lds_bytes = fsmn_lds_bytes(p.q, 16 * r.nt * r.u, r.u);
   return r;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// wekws_hip_forward_streams: row b of a call continues its stream with frames[b] of the Tcap frames of its row; rows with
+// frames[b] <= 0 are skipped.  The plan of a call is
+//   STREAMS_DS256    one launch of ds256_stream's table-driven variant, a workgroup per live row;
+//   STREAMS_FSMN     one launch of fsmn_f16's table-driven variant: the instance (nt, u) of select_fsmn_route for (live rows,
+//                    largest frame count); a workgroup takes up to u rows of EQUAL frame count (a short group leaves slots empty);
+//   STREAMS_GROUPED  every other model, and every call whose Tcap exceeds the table-driven kernel's tile: per bucket of rows with
+//                    equal frame count a gather from the pool, the uniform forward, a scatter back.
+// In every kind the live rows are ordered by frame count, largest first, ties in call order (`order`), and cut into groups
+// (`group_start`, ngroups + 1 offsets into `order`; `group_T`): workgroups for the first two kinds, buckets for the third.
+enum : int { STREAMS_GROUPED = 0, STREAMS_DS256 = 1, STREAMS_FSMN = 2 };
+constexpr int kDs256StreamTile = 16;
+struct StreamsPlan {
+  int32_t kind, live, max_T, ngroups;
+  int32_t slots;                  // rows a group holds at most (STREAMS_FSMN: u; STREAMS_DS256: 1; STREAMS_GROUPED: 0 = any number)
+  Route conv;                     // STREAMS_DS256: the kernel instance (grid = live rows)
+  FsmnRoute fsmn;                 // STREAMS_FSMN: the kernel instance (grid = ngroups)
+  const char* why;                // STREAMS_GROUPED with live rows: why no table-driven kernel takes the call
+};
+// d / f / o / fp: the model's built-shape descriptor, flags, options and (FSMN) shape plan; plain: the model runs its kernels on
+// the caller's own geometry (not zero-padded, not on the any-shape path).  order, group_T: B ints; group_start: B + 1 ints.
+inline StreamsPlan plan_streams(const wekws_hip_desc& d, const RouteFlags& f, const RouteOptions& o, const FsmnPlan& fp, bool plain,
+                                int cus, int B, int Tcap, const int32_t* frames, int32_t* order, int32_t* group_start, int32_t* group_T) {
+  StreamsPlan p{};
+  for (int b = 0; b < B; ++b)
+    if (frames[b] > 0) {
+      order[p.live++] = b;
+      p.max_T = frames[b] > p.max_T ? frames[b] : p.max_T;
+    }
+  std::stable_sort(order, order + p.live, [&](int32_t a, int32_t b) { return frames[a] > frames[b]; });
+  group_start[0] = 0;
+  if (!p.live) return p;
+  const bool conv = d.backbone == WEKWS_HIP_BACKBONE_DS_TCN || d.backbone == WEKWS_HIP_BACKBONE_TCN || d.backbone == WEKWS_HIP_BACKBONE_MDTC;
+  if (!plain) p.why = "a zero-padded model or the any-shape path";
+  else if (conv) {
+    // (the pool's planes are 16-byte aligned; a row whose features are not takes the kernel's own element-wise staging)
+    const Route r = select_conv_route(d, f, o, RouteCall{p.live, p.max_T, 1, 1, 1, 1, 1, cus});
+    if (r.family != ROUTE_DS256_STREAM) p.why = "no table-driven kernel for this conv model";
+    else if (Tcap > kDs256StreamTile) p.why = "rows longer than ds256_stream's tile of 16 frames";
+    else { p.kind = STREAMS_DS256; p.conv = r; }
+  } else if (d.backbone == WEKWS_HIP_BACKBONE_FSMN) {
+    if (select_fsmn_route(fp, d, o, p.live, Tcap, 0, cus).ntiles != 1) p.why = "rows longer than the FSMN kernel's tile";
+    else { p.kind = STREAMS_FSMN; p.fsmn = select_fsmn_route(fp, d, o, p.live, p.max_T, 0, cus); }
+  } else p.why = "no table-driven GRU kernel";
+  p.slots = p.kind == STREAMS_DS256 ? 1 : p.kind == STREAMS_FSMN ? p.fsmn.u : 0;
+  for (int i = 0; i < p.live; ++i) {
+    const int T = frames[order[i]];
+    const bool open = p.ngroups > 0 && group_T[p.ngroups - 1] == T && (!p.slots || i - group_start[p.ngroups - 1] < p.slots);
+    if (!open) { group_start[p.ngroups] = i; group_T[p.ngroups++] = T; }
+  }
+  group_start[p.ngroups] = p.live;
+  if (p.kind == STREAMS_DS256) p.conv.grid = p.ngroups;
+  if (p.kind == STREAMS_FSMN) p.fsmn.grid = p.ngroups;
+  return p;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

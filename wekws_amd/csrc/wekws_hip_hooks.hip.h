@@ -175,6 +175,45 @@ extern "C" int wekws_hip_debug_fsmn_route(const wekws_hip_desc* desc, const int*
   say(why, why_len, r.why_not ? r.why_not : "fsmn_f16");
   return WEKWS_HIP_OK;
 }
+// The plan of a wekws_hip_forward_streams call (route.h: plan_streams), WITHOUT a device (hooks library only): desc: any descriptor
+// wekws_hip_create accepts; opts / nopts as above; call[3]: B, Tcap, cus; frames[B].  out[16]: kind (0 grouped, 1 ds256_stream, 2
+// fsmn_f16), live rows, largest frame count, groups, rows a group holds at most (0: any number), then conv family, split, grid, LDS
+// bytes (kind 1), then nt, u, head slices, grid, LDS bytes (kind 2), 0, 0.  order[B]: the live rows in launch order; group_start[B + 1]:
+// ngroups + 1 offsets into order; group_T[B]: the frame count of every group.  why: the reason of a grouped plan.  Returns 0.
+extern "C" int wekws_hip_debug_streams_plan(const wekws_hip_desc* desc, const int* opts, int nopts, const int* call, const int32_t* frames,
+                                            int* out, int32_t* order, int32_t* group_start, int32_t* group_T, char* why, int why_len) {
+  if (!desc || !call || !frames || !out || !order || !group_start || !group_T || (nopts && !opts) || call[0] < 0 || !blob_elems(*desc))
+    return WEKWS_HIP_EINVAL;
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  if (why && why_len > 0) why[0] = 0;
+  wekws_hip_desc d = *desc;
+  wekws::RouteFlags f{};
+  wekws::FsmnPlan fp{};
+  bool plain = false;
+  if (desc_conv(d)) {
+    const wekws::ShapePlan sp = wekws::conv_shape_plan(d, wekws::kAmaxMaxBlocks);
+    plain = sp.kind == wekws::SHAPE_AS_IS;
+    if (sp.kind != wekws::SHAPE_GENERIC) {
+      d.hdim = sp.C; d.kernel_size = sp.ks;
+      const int cache_len = wekws::conv_route_flags(d, 0, 0).cache_len;
+      f = wekws::conv_route_flags(d, int(wekws::ds256_stream_lds_bytes(cache_len)), int(wekws::mdtc64_stream_lds_bytes(cache_len)));
+    }
+  } else if (d.backbone == WEKWS_HIP_BACKBONE_FSMN) {
+    fp = wekws::fsmn_shape_plan(d);
+    plain = fp.kind == wekws::SHAPE_AS_IS;
+  } else {
+    plain = wekws::gru_shape_plan(d).kind == wekws::SHAPE_AS_IS;
+  }
+  wekws::RouteOptions o = wekws::route_defaults(d, f);
+  for (int i = 0; i < nopts; ++i)
+    if (wekws::apply_route_option(o, d, f, opts[2 * i], opts[2 * i + 1])) return WEKWS_HIP_EINVAL;
+  const wekws::StreamsPlan p = wekws::plan_streams(d, f, o, fp, plain, call[2], call[0], call[1], frames, order, group_start, group_T);
+  const int v[16] = {p.kind, p.live, p.max_T, p.ngroups, p.slots, p.conv.family, p.conv.split, p.conv.grid, p.conv.lds_bytes,
+                     p.fsmn.nt, p.fsmn.u, p.fsmn.head_slices, p.fsmn.grid, p.fsmn.lds_bytes, 0, 0};
+  for (int i = 0; i < 16; ++i) out[i] = v[i];
+  say(why, why_len, p.why);
+  return WEKWS_HIP_OK;
+}
 // The weight blob's layout (blob_layout.h), WITHOUT a device (tests/test_blob_layout.py, hooks library only): desc: any descriptor
 // wekws_hip_blob_elems accepts.  out (int64, 4 per tensor): offset in floats, rows, cols, inner of every tensor in blob order, at most
 // max_tensors of them.  Returns the number of tensors of the blob, or WEKWS_HIP_EINVAL.

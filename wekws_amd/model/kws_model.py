@@ -26,7 +26,7 @@ from torch import nn
 
 from wekws_amd import _capi, pack
 
-__all__ = ["KWSModel", "init_model"]
+__all__ = ["KWSModel", "StreamCachePool", "init_model"]
 
 _BUFFER_LEAVES = ("running_mean", "running_var", "num_batches_tracked", "mean", "istd")
 
@@ -335,10 +335,122 @@ class KWSModel(nn.Module):
         so this is that call under the name BASELINE.json's north_star uses."""
         return self._run(x, in_cache, False)
 
+    def _run_streams(self, x: torch.Tensor, frames, streams, pool: "StreamCachePool", softmax: bool,
+                     out: Optional[torch.Tensor]) -> torch.Tensor:
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.size(2) != self.idim:
+            raise ValueError(f"expected x of shape (B, Tcap, {self.idim}), got {tuple(x.shape) if hasattr(x, 'shape') else x}")
+        if not x.is_cuda:
+            raise RuntimeError("wekws_amd.KWSModel runs on the MI355X HIP path only (no CPU fallback): "
+                               "move the model and its inputs to a ROCm device")
+        if x.dtype != torch.float32:
+            raise TypeError(f"x must be float32, got {x.dtype}")
+        dev = x.device
+        B, Tcap = int(x.size(0)), int(x.size(1))
+        h = self._get_handle(dev)
+        if h is not pool._handle:
+            raise RuntimeError("this StreamCachePool was created for another model, or before the model's weights, precision or "
+                               "options changed: create the pool from the model as it runs")
+        fr, ids = _host_i32(frames, B, "frames"), _host_i32(range(B) if streams is None else streams, B, "streams")
+        per_frame = self._d["head"] in (pack.HEAD["linear"], pack.HEAD["identity"])
+        shape = (B, Tcap, self.odim) if per_frame else (B, self.odim)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {shape} float32 tensor on the device of x")
+        if B > 0 and Tcap > 0:
+            x = x.contiguous()
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _capi.check(_capi.load().wekws_hip_forward_streams(h.ptr, pool._ptr, x.data_ptr(), B, Tcap, ids.ctypes.data, fr.ctypes.data,
+                                                               out.data_ptr(), 1 if softmax else 0, ctypes.c_void_p(stream)),
+                        "wekws_hip_forward_streams")
+        return out
+
+    def forward_streams(self, x: torch.Tensor, frames, streams, pool: "StreamCachePool",
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One streaming step for many streams (wekws_hip_forward_streams): row b of ``x`` (B, Tcap, idim) continues stream
+        ``streams[b]`` (default 0 .. B-1; distinct, any subset of the pool in any order) with its first ``frames[b]`` frames --
+        what ``StreamingFrontEnd.push`` returned.  The streams' caches live in ``pool`` and move in place.  Returns y
+        (B, Tcap, odim), or (B, odim) for pooled heads: row b holds its ``frames[b]`` rows, the rest (and the rows of skipped
+        streams, ``frames[b] <= 0``) is whatever ``out`` held."""
+        return self._run_streams(x, frames, streams, pool, False, out)
+
+    def forward_softmax_streams(self, x: torch.Tensor, frames, streams, pool: "StreamCachePool",
+                                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if self._d["head"] in (pack.HEAD["glob"], pack.HEAD["last"]):
+            raise IndexError("Dimension out of range (expected to be in range of [-2, 1], but got 2)")  # x.softmax(2) on (B, K)
+        return self._run_streams(x, frames, streams, pool, True, out)
+
     def fuse_modules(self):
         """Reference: kws_model.py:92-94 (quantisation-time Conv+BN+ReLU fusion).  Here BN is always folded
         at pack time, so this is a no-op kept for API compatibility."""
         return None
+
+
+def _host_i32(values, n: int, what: str) -> np.ndarray:
+    """`values` as n int32 on the host (out of range stays out of range: the library refuses it)"""
+    if isinstance(values, np.ndarray) and values.dtype.kind in "iu":     # (thousands of rows per step: no per-row Python objects)
+        v = values.astype(np.int64, copy=False).reshape(-1)
+    else:
+        v = np.asarray([int(e) for e in values], dtype=np.int64)
+    if v.shape != (n,):
+        raise ValueError(f"{what} must have one entry per row")
+    lim = np.iinfo(np.int32)
+    return np.ascontiguousarray(np.clip(v, lim.min, lim.max), dtype=np.int32)
+
+
+class StreamCachePool:
+    """The carried caches of ``num_streams`` streams of ``model``, owned by the library (wekws_hip_stream_cache_*): what
+    ``KWSModel.forward_streams`` steps in place.  A fresh pool, and a stream after ``reset``, hold the empty-cache sentinel."""
+
+    def __init__(self, model: KWSModel, num_streams: int, device: Optional[torch.device] = None):
+        self.device = device or next(model.parameters()).device
+        if self.device.type != "cuda":
+            raise RuntimeError("StreamCachePool lives on a ROCm device: move the model there first")
+        self.num_streams = int(num_streams)
+        self._lib = _capi.load()
+        self._handle = model._get_handle(self.device)       # (kept alive: the pool belongs to this wekws_hip_model)
+        self._shape = pack.cache_shape(model._d, 1)
+        self._ptr = ctypes.c_void_p()
+        _capi.check(self._lib.wekws_hip_stream_cache_create(self._handle.ptr, self.num_streams, ctypes.byref(self._ptr)),
+                    "wekws_hip_stream_cache_create")
+
+    def __del__(self):
+        try:
+            if self._ptr:
+                self._lib.wekws_hip_stream_cache_destroy(self._ptr)
+                self._ptr = ctypes.c_void_p()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def reset(self, streams=None) -> None:
+        """The given streams (default all) start from the empty cache again."""
+        if streams is None:
+            rc = self._lib.wekws_hip_stream_cache_reset(self._ptr, None, 0, self._stream())
+        else:
+            ids = _host_i32(streams, len(streams), "streams")
+            rc = self._lib.wekws_hip_stream_cache_reset(self._ptr, ids.ctypes.data if ids.size else None, int(ids.size), self._stream())
+            if not ids.size:
+                return
+        _capi.check(rc, "wekws_hip_stream_cache_reset")
+
+    def read(self, stream: int) -> torch.Tensor:
+        """The stream's live cache, in ``KWSModel.forward``'s geometry for one stream."""
+        out = torch.empty(self._shape, dtype=torch.float32, device=self.device)
+        if out.numel():
+            _capi.check(self._lib.wekws_hip_stream_cache_read(self._ptr, int(stream), out.data_ptr(), self._stream()),
+                        "wekws_hip_stream_cache_read")
+        return out
+
+    def write(self, stream: int, cache: torch.Tensor) -> None:
+        if tuple(cache.shape) != tuple(self._shape):
+            raise ValueError(f"cache shape {tuple(cache.shape)} != {tuple(self._shape)}")
+        c = cache.to(device=self.device, dtype=torch.float32).contiguous()
+        if c.numel():
+            _capi.check(self._lib.wekws_hip_stream_cache_write(self._ptr, int(stream), c.data_ptr(), self._stream()),
+                        "wekws_hip_stream_cache_write")
 
 
 def init_model(configs: Mapping) -> KWSModel:

@@ -4,13 +4,13 @@ model with its carried cache, and the CTC prefix beam search with the keyword de
 (wekws_amd.ctc.StreamingKeywordSpotter).  No sample or feature crosses to the host except the chunk itself."""
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from typing import Dict, List
 
 import torch
 
-from wekws_amd import pack
 from wekws_amd.ctc import StreamingKeywordSpotter
 from wekws_amd.frontend import StreamingFrontEnd
+from wekws_amd.model.kws_model import StreamCachePool
 
 
 class BatchedKeyWordSpotter:
@@ -36,40 +36,37 @@ class BatchedKeyWordSpotter:
         shift_ms = 1000.0 * self.frontend.cfg.fbank.frame_shift / self.frontend.cfg.fbank.sample_rate
         self.spotter = StreamingKeywordSpotter(self.num_streams, keywords, threshold, downsampling=self.frontend.skip,
                                                frame_shift_ms=shift_ms, device=self.device, **settings)
-        d = model._d
-        # the carried cache of every stream; zeros are the empty-cache sentinel of a fresh stream
-        self.cache = torch.zeros(pack.cache_shape(d, self.num_streams), dtype=torch.float32, device=self.device)
-        self.cache_axis = 1 if d["kind"] == "gru" else 0
+        # the carried cache of every stream, owned by the library; a fresh pool holds the empty-cache sentinel
+        self.pool = StreamCachePool(model, self.num_streams, self.device)
+        self.cache_axis = 1 if model._d["kind"] == "gru" else 0
+
+    @property
+    def cache(self) -> torch.Tensor:
+        """The live cache of every stream, assembled in ``KWSModel.forward``'s geometry for ``num_streams`` rows (a copy)."""
+        return torch.cat([self.pool.read(s) for s in range(self.num_streams)], dim=self.cache_axis)
 
     def forward(self, chunks, streams=None, samples=None, return_probs: bool = False):
         """One chunk per row; row b continues stream ``streams[b]`` (default 0 .. B-1).  Returns, per row,
         ``KeyWordSpotter.forward``'s dict -- ``{}`` for a row that was held or yielded no frame.  With ``return_probs`` also
         a list with each row's (frames, V) posteriors on the device (None for a row without frames) and the features the
-        model was given."""
-        feats, frames = self.frontend.push(chunks, samples=samples, streams=streams)
+        model was given.  Three device calls: the front end's push, the model step over the pool, the decoder's step."""
+        if torch.is_tensor(chunks):
+            nmax = int(chunks.size(1)) if chunks.dim() == 2 else 0
+        else:
+            nmax = max([len(c) // 2 if isinstance(c, (bytes, bytearray, memoryview)) else len(c) for c in chunks] + [0])
+        feats, frames = self.frontend.push(chunks, samples=samples, streams=streams, capacity=self.frontend.max_frames(nmax))
         B = len(frames)
         ids = list(range(B)) if streams is None else [int(s) for s in streams]
-        out: List[Dict] = [{} for _ in range(B)]
-        probs_out: List[Optional[torch.Tensor]] = [None] * B
-        feats_out: List[Optional[torch.Tensor]] = [None] * B
-        # rows grouped by frame count: one model call and one decoder step per group
-        groups: Dict[int, List[int]] = {}
-        for b, n in enumerate(frames):
-            if n > 0:
-                groups.setdefault(n, []).append(b)
-        for n, rows in sorted(groups.items()):
-            ridx = torch.tensor(rows, dtype=torch.long, device=self.device)
-            sidx = torch.tensor([ids[b] for b in rows], dtype=torch.long, device=self.device)
-            x = feats.index_select(0, ridx)[:, :n].contiguous()
-            cache = self.cache.index_select(self.cache_axis, sidx).contiguous()
-            probs, cache = self.model.forward_softmax(x, cache)
-            self.cache.index_copy_(self.cache_axis, sidx, cache)
-            res = self.spotter.step(probs, streams=[ids[b] for b in rows])
-            for j, b in enumerate(rows):
-                out[b] = res[j]
-                if return_probs:
-                    probs_out[b], feats_out[b] = probs[j], x[j]
-        return (out, probs_out, feats_out) if return_probs else out
+        if B == 0 or feats.size(1) == 0 or max(frames) <= 0:
+            out: List[Dict] = [{} for _ in range(B)]
+            return (out, [None] * B, [None] * B) if return_probs else out
+        probs = self.model.forward_softmax_streams(feats, frames, ids, self.pool)
+        out = self.spotter.step(probs, frames=[max(n, 0) for n in frames], streams=ids)
+        if not return_probs:
+            return out
+        probs_out = [probs[b, :n] if n > 0 else None for b, n in enumerate(frames)]
+        feats_out = [feats[b, :n] if n > 0 else None for b, n in enumerate(frames)]
+        return out, probs_out, feats_out
 
     __call__ = forward
 
@@ -82,8 +79,4 @@ class BatchedKeyWordSpotter:
         remembered frames and skip phase, and the streams' cache."""
         self.spotter.reset_all(streams)
         self.frontend.reset(streams)
-        if streams is None:
-            self.cache.zero_()
-        else:
-            sidx = torch.tensor([int(s) for s in streams], dtype=torch.long, device=self.device)
-            self.cache.index_fill_(self.cache_axis, sidx, 0.0)
+        self.pool.reset(streams)
