@@ -516,6 +516,66 @@ int wekws_hip_ctc_kws_read_beam(void* h, int id, void* out, void* stream);
 int wekws_hip_ctc_kws_status(void* h, int id, int32_t* status_out, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * Validation criterion  --  wekws/model/loss.py::criterion, forward only: what Executor.cv / Executor.test
+ * (wekws/utils/executor.py:70-115) call after every forward, so that an evaluation loop moves two numbers per run to the
+ * host instead of the (B, T, V) logits per batch.  Stateless; every pointer is a device pointer; no call synchronises or
+ * allocates.  Deterministic: a row's outputs depend on that row alone, the batch totals are one fixed-order reduction (the
+ * same inputs give the same bits on every run).  B, T, K, D, V >= 1.
+ * ------------------------------------------------------------------------------------------*/
+/*
+ * max_pooling_loss (loss.py:26-88).
+ *   scores      (B, T, K) device float32 posteriors;  target (B) device int32 (keyword column; < 0 or >= K: filler)
+ *   lengths     (B) device int32, clamped to [0, T]; NULL = T.  (The reference fails unless lengths.max() == T; here the
+ *               frames t >= lengths[b] are simply masked.)
+ *   pooled      (B, K): column target[b]: max_t clamp(p, 1e-8, 1) with frames t >= len or t < min_duration counted as 0;
+ *               every other column: min_t clamp(1 - p, 1e-8, 1) with frames t >= len counted as 1.  Bit-exact.
+ *   loss_terms  (B, K) = -log(pooled);  loss (1) = sum(loss_terms) / B
+ *   correct     (B) int32 0 / 1 by loss.py:74-85 (max over valid frames with masked frames 0, then over keywords, lower
+ *               index on ties; > 0.5 and idx == target, or < 0.5 and target < 0);  num_correct (1) int32 = sum(correct)
+ * A NaN in a valid frame makes that column's pooled value (and the loss) NaN and the utterance incorrect; a NaN in a masked
+ * frame changes nothing.
+ */
+int wekws_hip_criterion_max_pooling(const float* scores, int B, int T, int K, const int32_t* target, const int32_t* lengths,
+                                    int min_duration, float* pooled, float* loss_terms, int32_t* correct, float* loss,
+                                    int32_t* num_correct, void* stream);
+/*
+ * cross_entropy + acc_frame (loss.py:167-180, :91-99).
+ *   logits (B, D) device float32;  target (B) device int32
+ *   loss_rows (B) = logsumexp(row) - row[target] (row max subtracted);  loss (1) = mean
+ *   pred (B) int32 first arg-max;  correct (B) int32 = (pred == target);  num_correct (1) int32
+ * A target outside [0, D) (torch raises; the device cannot without a synchronise) and a NaN logit make the row's loss NaN
+ * and the row incorrect.
+ */
+int wekws_hip_criterion_ce(const float* logits, int B, int D, const int32_t* target, float* loss_rows, int32_t* pred,
+                           int32_t* correct, float* loss, int32_t* num_correct, void* stream);
+/*
+ * ctc_loss without the accuracy (loss.py:154-162): log_softmax over V, F.ctc_loss(blank 0, reduction 'sum',
+ * zero_infinity False) / B.
+ *   logits (B, T, V) device float32, unnormalised;  targets (B, Lmax) device int32 labels in [1, V), row b's first
+ *   target_lengths[b] entries (clamped to [0, Lmax]);  logit_lengths (B) clamped to [0, T]
+ *   loss_rows (B): -log p(labels | logits); +Inf for a row no alignment fits (fewer frames than labels + adjacent repeats;
+ *   no frames but labels); NaN for a row with a label outside [1, V) (torch raises).  loss (1) = sum(loss_rows) / B.
+ *   probs: NULL, or (B, T, V) device float32 receiving the softmax of every frame t < logit_lengths[b] (the rest is left as
+ *   it was): the posteriors that wekws_hip_ctc_kws_search decodes for the accuracy, from the same single read of the logits.
+ *   workspace: wekws_hip_ctc_loss_workspace_bytes(B, T, Lmax) bytes of device scratch (per frame the log-probabilities of
+ *   the blank and of the row's own labels; no (B, T, V) log-softmax is written).  Lmax <= 3000.
+ */
+size_t wekws_hip_ctc_loss_workspace_bytes(int B, int T, int Lmax);
+int wekws_hip_ctc_loss(const float* logits, int B, int T, int V, const int32_t* targets, int Lmax, const int32_t* logit_lengths,
+                       const int32_t* target_lengths, float* loss_rows, float* loss, float* probs, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/*
+ * acc_utterance after the decode (loss.py:119-132): the Levenshtein distance between entry 0 of each utterance's final beam
+ * and its labels.
+ *   beams   (B) records as wekws_hip_ctc_kws_search writes them for a handle of `path_beam` and T = `cap` frames
+ *           (wekws_hip_ctc_kws_beam_bytes(h, cap) bytes each; a record with count 0 is the empty hypothesis)
+ *   dist    (B) int32;  totals: NULL, or (2) int32 = {sum of target_lengths, sum of dist} over the rows with labels:
+ *           the reference's accuracy is (totals[0] - totals[1]) * 100 / totals[0].   Lmax <= 3000.
+ */
+int wekws_hip_ctc_edit_distance(const void* beams, int path_beam, int cap, int B, const int32_t* targets, int Lmax,
+                                const int32_t* target_lengths, int32_t* dist, int32_t* totals, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * Streaming front end  --  the part of the streaming KeyWordSpotter that runs BEFORE the model, for many streams at once:
  *   wekws/bin/stream_kws_ctc.py:335-398 accept_wave: the samples left over from the last chunk (wave_remained), Kaldi fbank
  *   of (leftover + chunk), the last left + right feature frames for the context expansion (feature_remained) and the

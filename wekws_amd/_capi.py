@@ -95,6 +95,15 @@ SIGNATURES = {
     "wekws_hip_ctc_kws_beam_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "wekws_hip_ctc_kws_read_beam": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "wekws_hip_ctc_kws_status": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p]),
+    "wekws_hip_criterion_max_pooling": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "wekws_hip_criterion_ce": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "wekws_hip_ctc_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "wekws_hip_ctc_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wekws_hip_ctc_edit_distance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
     "wekws_hip_stream_frontend_create": (C.c_int, [C.POINTER(StreamFrontendCfg), C.POINTER(C.c_void_p)]),
     "wekws_hip_stream_frontend_destroy": (None, [C.c_void_p]),
     "wekws_hip_stream_frontend_plan": (C.c_int, [C.POINTER(StreamFrontendCfg), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]),
