@@ -6,12 +6,12 @@ import os
 import numpy as np
 import pytest
 
+from tests import forward_streams_matrix as fm
 from tests import route_matrix as rm
 from wekws_amd import _capi, pack
 from wekws_amd.utils import synth
 
 CUS = 256
-KINDS = ["grouped", "ds256_stream", "fsmn_f16"]
 SYMBOLS = ["wekws_hip_stream_cache_create", "wekws_hip_stream_cache_destroy", "wekws_hip_stream_cache_reset",
            "wekws_hip_stream_cache_read", "wekws_hip_stream_cache_write", "wekws_hip_forward_streams"]
 
@@ -30,31 +30,11 @@ def test_the_six_entry_points_are_exported():
 
 @pytest.fixture(scope="module")
 def lib():
-    lib = rm.type_hooks(C.CDLL(rm.hooks_path()))
-    lib.wekws_hip_debug_streams_plan.restype = C.c_int
-    lib.wekws_hip_debug_streams_plan.argtypes = [C.POINTER(_capi.Desc), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p,
-                                                 C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
-    return lib
+    return fm.type_plan(C.CDLL(rm.hooks_path()))
 
 
 def plan(lib, cfg, Tcap, frames, cus=CUS, opts=None):
-    d = rm._desc(cfg, "default")
-    o, n = rm._opts(opts)
-    B = len(frames)
-    fr = np.ascontiguousarray(frames, dtype=np.int32)
-    order, start, gT = np.full(B, -7, np.int32), np.full(B + 1, -7, np.int32), np.full(B, -7, np.int32)
-    out = (C.c_int * 16)()
-    why = C.create_string_buffer(256)
-    assert lib.wekws_hip_debug_streams_plan(C.byref(d), o, n, (C.c_int * 3)(B, Tcap, cus), fr.ctypes.data, out, order.ctypes.data,
-                                            start.ctypes.data, gT.ctypes.data, why, 256) == 0
-    keys = ("kind", "live", "max_T", "ngroups", "slots", "family", "split", "conv_grid", "conv_lds", "nt", "u", "head_slices", "fsmn_grid",
-            "fsmn_lds")
-    p = dict(zip(keys, list(out)))
-    p["kind"] = KINDS[p["kind"]]
-    p["why"] = why.value.decode()
-    p["order"] = order[:p["live"]].tolist()
-    p["groups"] = [(int(gT[g]), order[start[g]:start[g + 1]].tolist()) for g in range(p["ngroups"])]
-    return p
+    return fm.plan(lib, cfg, Tcap, frames, cus, opts)
 
 
 def restated(frames, slots):
@@ -133,3 +113,67 @@ def test_packing_really_packs(lib):
         assert max(sizes) == u and min(sizes) < u and len(p["groups"]) == sum(-(-frames.count(T) // u) for T in (1, 7, 16))
     # the STREAM option off: no table-driven conv kernel
     assert plan(lib, synth.MODEL_CONFIGS["ds_tcn_h256"], 16, [10] * 5, opts={"stream": 0})["kind"] == "grouped"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The case table of the GPU tests (tests/forward_streams_matrix.py) reaches what it claims: a change of select_fsmn_route or
+# plan_streams that quietly stops reaching an instance fails here, without a device.
+def case_plans(lib, case):
+    return [plan(lib, fm.case_config(case), case["Tcap"], frames) for frames in fm.plan_calls(case, CUS)]
+
+
+@pytest.mark.parametrize("case", [c for c in fm.CASES if not c.get("device_only")], ids=lambda c: c["id"])
+def test_matrix_case_has_the_plan_it_claims(lib, case):
+    want = case["expect"]
+    for p in case_plans(lib, case):
+        assert p["kind"] == want["kind"], (case["id"], p["kind"], p["why"])
+        if want["kind"] == "fsmn_f16":
+            assert (p["nt"], p["u"]) == (want["nt"], want["u"]), (case["id"], p["nt"], p["u"], p["live"], p["max_T"])
+        elif want["kind"] == "ds256_stream":
+            assert rm.FAMILIES[p["family"]] == "ds256_stream" and p["split"] == want["split"], (case["id"], p["family"], p["split"])
+        else:
+            assert p["why"] == want["why"], (case["id"], p["why"])
+
+
+def test_matrix_reaches_every_table_driven_instance(lib):
+    """The FSMN cases together: exactly the seven (nt, u) of the switch in fsmn_f16_rows.hip -- parsed from it --; the DS-TCN
+    cases: both splits of ds256_stream; group a alone already holds all seven, so the oracle sees each of them."""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "wekws_amd", "csrc", "fsmn_f16_rows.hip")).read()
+    import re
+    switch = sorted({(int(a), int(b)) for a, b in re.findall(r"case (\d)(\d):", src)})          # case nt * 10 + u
+    assert switch == sorted(fm.FSMN_INSTANCES), switch
+    got = {(p["nt"], p["u"]) for c in fm.FSMN_CASES for p in case_plans(lib, c)}
+    assert sorted(got) == switch, sorted(got)
+    assert {(p["nt"], p["u"]) for c in fm.NONFINITE_CASES for p in case_plans(lib, c)} == {(1, 2), (2, 2)}
+    splits = {p["split"] for c in fm.DS256_CASES for p in case_plans(lib, c) if p["kind"] == "ds256_stream"}
+    assert splits == {0, 1}, splits
+    whys = {c["expect"]["why"] for c in fm.GROUPED_CASES}
+    assert whys == {fm.PADDED, fm.WHY_DS_TILE, fm.WHY_FSMN_TILE, fm.WHY_NO_CONV, fm.WHY_GRU}
+
+
+def test_matrix_frame_counts_are_what_the_cases_need(lib):
+    """Group a: counts from the tile edges, a row at Tcap (but for the 64-frame-stride case), rows with 0 and -1 frames, ids a
+    permutation; packed cases: a count whose rows are no multiple of u, a count held by ONE row (a group with one live slot), and a
+    count whose uniform call over all B rows takes the same instance (what the bit-identity is asserted against)."""
+    for case in fm.FSMN_CASES:
+        ids, fr = fm.frames_of(case, CUS)
+        nt, u = case["expect"]["nt"], case["expect"]["u"]
+        live = [n for n in fr if n > 0]
+        assert len(set(ids)) == len(ids) == len(fr) and max(ids) < len(fr) + 2 and ids != sorted(ids), case["id"]
+        assert 0 in fr and -1 in fr and set(live) <= set(fm.EDGES) | {20}, case["id"]
+        assert case["Tcap"] in fr or case["id"].endswith("stride64"), case["id"]
+        p = plan(lib, fm.case_config(case), case["Tcap"], fr)
+        sizes = [len(rows) for _, rows in p["groups"]]
+        if u > 1:
+            assert any(live.count(T) % u for T in set(live)) and 1 in [live.count(T) for T in set(live)], case["id"]
+            assert min(sizes) == 1 and max(sizes) == u, case["id"]
+        same = [T for T in set(live)
+                if (lambda r: (r["nt"], r["u"]))(rm.fsmn_route(lib, fm.case_config(case), len(fr), T, cus=CUS)) == (nt, u)]
+        assert same, case["id"]
+    # the stride case: Tcap = 64, nothing above 20 frames
+    ids, fr = fm.frames_of(fm.BY_ID["fsmn/nt2_stride64"], CUS)
+    assert max(fr) == 20
+    # group e: every row live, so a poisoned row has a slot-mate
+    for case in fm.NONFINITE_CASES:
+        ids, fr = fm.nonfinite_frames(case, CUS)
+        assert min(fr) > 0 and sorted(ids) == list(range(len(fr)))

@@ -115,7 +115,10 @@ def test_grouped_schedule(records, name, path):
 @pytest.mark.parametrize("name", ["ds_tcn_h256", "fsmn_ctc300"])
 def test_nonfinite_rows_follow_the_table(records, name):
     """A NaN feature in one row, a +Inf in another stream's carried cache: those rows as the float64 oracle has them -- class by
-    class, the finite values within the bar --, every other row of the call bit-identical to the call without the poison."""
+    class, the finite values within the bar --, every other row of the call bit-identical to the call without the poison.
+    That holds because these calls have five rows, so one row per workgroup (u = 1).  With u > 1 a poisoned slot sends every
+    row of its WORKGROUP through the non-finite path: a slot-mate then has the oracle's values within the bar, not the clean call's
+    bits, and only the rows of other workgroups are bit-identical (tests/test_hip_forward_streams_matrix.py, group e)."""
     rec = pick(records, kind="nonfinite", model=name)[0]
     assert sorted(r["row"] for r in rec["rows"] if r["poisoned"]) == [1, 3]
     for row in rec["rows"]:
