@@ -68,7 +68,7 @@ def route(lib, cfg, B, T, has_in=False, has_out=True, precision="default", x16=1
 PLANS = ["as_is", "padded", "generic"]
 PRECISIONS = ["default", "f32", "f16x3", "f16"]                 # enum wekws_hip_precision
 GRU_FAMILIES = ["none", "gru_f32", "gru_f16", "gru_pipe"]
-# the 9 ints of a GRU trace record (wekws_hip_hooks.hip.h: route_record), then what only the CPU entry point reports
+# the 9 ints of a GRU trace record (wekws_hip_hooks.hip: route_record), then what only the CPU entry point reports
 GRU_REC = ("family", "nn", "spw", "tchunk", "nchunks", "slots", "tiles", "grid", "bits")
 GRU_KEYS = ("plan", "C") + GRU_REC + ("stages", "slots_p", "lds", "chunked", "plain", "gran", "res_plain", "res_gran", "eff")
 FSMN_REC = ("tile_frames", "nt", "u", "head_slices", "grid", "lds", "ntiles", "_0", "_1")
@@ -265,7 +265,7 @@ def predict(lib, row, precision=None):
         has_in = row["cache"] or j > 0
         ntiles = math.ceil(T / TILE)
         x16 = int(row["x_off"] % 4 == 0 and (T * idim) % 4 == 0)
-        # (widened models hand the kernels aligned copies of the caller's caches: wekws_hip.hip's cache_remap_kernel)
+        # (widened models hand the kernels aligned copies of the caller's caches: aux_kernels.hip's cache_remap_kernel)
         cache16 = int(plan == "padded" or not (has_in and row["c_off"] % 4))
         tiles = []
         for i in range(ntiles):

@@ -1,7 +1,7 @@
 // WHERE EVERY TENSOR OF THE WEIGHT BLOB LIES -- the executable form of the "Blob layout" comment of include/wekws_hip.h (which stays
 // the document an integrator reads): blob_layout(desc) gives every tensor its offset in floats from the start of the blob and its
 // shape, the size of the blob, and the tensors in blob order.  The one statement of the order on the host: wekws_hip_blob_elems, the
-// packers of wekws_hip.hip, the balancing and zero-padding of weight_image.hip.h and the any-shape path (generic.hip.h) read their
+// packers of create.hip, the balancing and zero-padding of weight_image.hip.h and the any-shape path (generic.hip.h) read their
 // pointers from here and walk nothing themselves.  Usable from device code (ROUTE_HD), but the repair routines of nonfinite.hip.h
 // still walk the blob on their own: they are noinline callees of the hot kernels, and the registers a callee uses decide how its
 // callers are allocated -- see the note there.

@@ -818,60 +818,11 @@ __global__ __launch_bounds__(kThreads, 2) void conv_stack_kernel(const StackPara
   conv_stack_head<KIND, C, NT>(P, A, hbuf, slab, b0);
 }
 
-// Row softmax over the last axis (KWSModel.forward_softmax, kws_model.py:89): one wave per row, two passes over the
-// row -- online (max, rescaled sum) with 16-byte loads through a 4-byte-aligned type (rows of an odd-width matrix are
-// only dword aligned), then normalise in place.  Non-finite logits as torch.softmax has them: a class masked with -Inf
-// adds nothing and gets 0; a NaN or +Inf anywhere, or -Inf everywhere, makes the whole row NaN.
-static __device__ __forceinline__ void softmax_row(float* p, int K, int lane) {
-  struct __attribute__((packed, aligned(4))) V4 { float v[4]; };
-  const int K4 = K & ~3;
-  float mx = -INFINITY, s = 0.f;
-  auto take = [&](float v) __attribute__((always_inline)) {
-    if (v == -INFINITY) return;                              // a masked class adds 0 (mx - v would be Inf - Inf while mx is -Inf)
-    if (v > mx) { s *= __expf(mx - v); mx = v; }
-    s += __expf(v - mx);
-  };
-  for (int k = lane * 4; k < K4; k += 256) {
-    const V4 q = *reinterpret_cast<const V4*>(p + k);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) take(q.v[j]);
-  }
-  if (K4 + lane < K) take(p[K4 + lane]);
-  float gm = mx;
-  for (int off = 32; off > 0; off >>= 1) gm = fmaxf(gm, __shfl_xor(gm, off));
-  // (a lane without a finite class keeps mx = -Inf: its s is 0, or NaN if it saw a NaN, and goes in as it is)
-  float gs = (mx == -INFINITY) ? s : s * __expf(mx - gm);
-  for (int off = 32; off > 0; off >>= 1) gs += __shfl_xor(gs, off);
-  const float inv = 1.0f / gs;
-  for (int k = lane * 4; k < K4; k += 256) {
-    V4 q = *reinterpret_cast<const V4*>(p + k);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) q.v[j] = __expf(q.v[j] - gm) * inv;
-    *reinterpret_cast<V4*>(p + k) = q;
-  }
-  if (K4 + lane < K) p[K4 + lane] = __expf(p[K4 + lane] - gm) * inv;
-}
-static __global__ __attribute__((unused)) void softmax_rows_kernel(float* y, int64_t rows, int K) {
-  const int64_t row = int64_t(blockIdx.x) * (blockDim.x / 64) + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  softmax_row(y + row * K, K, threadIdx.x & 63);
-}
-// The same rows of a table-driven call: workgroup (w, i) takes rows 4 i .. 4 i + 3 of table row w, of its yrows.
-static __global__ __attribute__((unused)) void softmax_stream_rows_kernel(const StreamRow* rows, int K) {
-  const StreamRow r = rows[blockIdx.x];
-  const int t = int(blockIdx.y) * (blockDim.x / 64) + (threadIdx.x >> 6);
-  if (t >= r.yrows) return;
-  softmax_row(r.y + int64_t(t) * K, K, threadIdx.x & 63);
-}
-static inline __attribute__((unused)) bool launch_softmax_stream_rows(const StreamRow* rows, int nrows, int max_yrows, int K, hipStream_t stream) {
-  hipLaunchKernelGGL(softmax_stream_rows_kernel, dim3(unsigned(nrows), unsigned((max_yrows + 3) / 4)), dim3(256), 0, stream, rows, K);
-  return hipGetLastError() == hipSuccess;
-}
-// the one launch statement of softmax_rows_kernel: four rows (waves) per workgroup
-static inline __attribute__((unused)) bool launch_softmax_rows(float* y, int64_t rows, int K, hipStream_t stream) {
-  hipLaunchKernelGGL(softmax_rows_kernel, dim3(unsigned((rows + 3) / 4)), dim3(256), 0, stream, y, rows, K);
-  return hipGetLastError() == hipSuccess;
-}
+// Row softmax over the last axis of y (rows, K) in place (KWSModel.forward_softmax, kws_model.py:89), and the same over the rows of a
+// table-driven call (nrows table rows of at most max_yrows output rows).  Defined in aux_kernels.hip, the one unit that holds the
+// kernels: the forward, forward_streams and the test library's wekws_hip_debug_softmax_rows all reach it.  false: the launch failed.
+__attribute__((visibility("hidden"))) bool launch_softmax_rows(float* y, int64_t rows, int K, hipStream_t stream);
+__attribute__((visibility("hidden"))) bool launch_softmax_stream_rows(const StreamRow* rows, int nrows, int max_yrows, int K, hipStream_t stream);
 
 // Runs the conv_stack route of a KIND backbone with C channels.  Defined below, instantiated once per KIND in
 // conv_stack_{ds,tcn,mdtc}.hip (the units compile in parallel).

@@ -53,26 +53,9 @@ int launch_ctc_edit_distance(const char* beams, size_t beam_stride, int PB, int 
 }  // namespace wekws
 
 // ------------------------------------------------------------------------------------------------ C ABI
-#include "../../include/wekws_hip.h"
-
-#include <cstdarg>
-#include <cstdio>
-
-namespace wekws {
-int set_last_error(int code, const char* msg);   // wekws_hip.hip
-}
+#include "host_util.h"
 
 namespace {
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  return wekws::set_last_error(code, buf);
-}
 
 int launch_fail(const char* what) {
   return fail(WEKWS_HIP_EDEVICE, "%s launch failed: %s", what, hipGetErrorString(hipGetLastError()));

@@ -33,43 +33,14 @@ int launch_ctc_kws_read_beam(const CtcParams& p, int id, char* out, hipStream_t 
 }  // namespace wekws
 
 // ------------------------------------------------------------------------------------------------ C ABI
-#include "../../include/wekws_hip.h"
-
-#include <cstdarg>
 #include <cstddef>
-#include <cstdio>
 #include <mutex>
 #include <new>
 #include <vector>
 
-namespace wekws {
-int set_last_error(int code, const char* msg);   // wekws_hip.hip
-}
+#include "host_util.h"
 
 namespace {
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  return wekws::set_last_error(code, buf);
-}
-
-int hip_fail(hipError_t e, const char* what) {
-  return fail(e == hipErrorOutOfMemory ? WEKWS_HIP_ENOMEM : WEKWS_HIP_EDEVICE, "%s: %s", what, hipGetErrorString(e));
-}
-
-struct Guard {   // the object's device for the scope; the caller's current device is restored
-  int prev = -1;
-  explicit Guard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess || prev == device) prev = -1;
-    else (void)hipSetDevice(device);
-  }
-  ~Guard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 struct CtcKws {
   int device = 0;
@@ -128,7 +99,7 @@ int wekws_hip_ctc_kws_create(const wekws_hip_ctc_kws_desc* d, void** out) {
   CtcKws* o = new (std::nothrow) CtcKws;
   if (!o) return fail(WEKWS_HIP_ENOMEM, "host allocation failed");
   o->device = d->device;
-  Guard g(d->device);
+  DeviceGuard g(d->device);
   wekws::CtcParams& p = o->p;
   p.V = d->vocab; p.K = d->score_beam; p.PB = d->path_beam; p.cap = d->prefix_capacity; p.pool_cap = int(pool_cap);
   p.n_slots = d->max_streams; p.slot_bytes = wekws::ctc_slot_bytes(p.PB, p.cap, p.pool_cap);
@@ -154,7 +125,7 @@ int wekws_hip_ctc_kws_create(const wekws_hip_ctc_kws_desc* d, void** out) {
 void wekws_hip_ctc_kws_destroy(void* h) {
   CtcKws* o = static_cast<CtcKws*>(h);
   if (!o) return;
-  Guard g(o->device);
+  DeviceGuard g(o->device);
   (void)hipDeviceSynchronize();
   if (o->slots) (void)hipFree(o->slots);
   if (o->tokset) (void)hipFree(o->tokset);
@@ -170,7 +141,7 @@ int wekws_hip_ctc_kws_step(void* h, const float* probs, int B, int T, const int3
   if (B < 0 || T < 0) return fail(WEKWS_HIP_EINVAL, "ctc_kws_step: B=%d T=%d", B, T);
   if (B == 0) return WEKWS_HIP_OK;
   if (!stream_ids || !results || (T > 0 && !probs)) return fail(WEKWS_HIP_EINVAL, "NULL argument");
-  Guard g(o->device);
+  DeviceGuard g(o->device);
   if (wekws::launch_ctc_kws(o->p, 0, probs, B, T, stream_ids, frames, reinterpret_cast<wekws::CtcResult*>(results), nullptr,
                             0, static_cast<hipStream_t>(stream)))
     return hip_fail(hipGetLastError(), "ctc_kws_step launch");
@@ -190,7 +161,7 @@ int wekws_hip_ctc_kws_search(void* h, const float* probs, int B, int T, const in
   if (B < 0 || T < 0) return fail(WEKWS_HIP_EINVAL, "ctc_kws_search: B=%d T=%d", B, T);
   if (B == 0) return WEKWS_HIP_OK;
   if (!results || (T > 0 && !probs)) return fail(WEKWS_HIP_EINVAL, "NULL argument");
-  Guard g(o->device);
+  DeviceGuard g(o->device);
   wekws::CtcParams p = o->p;
   p.cap = T > 0 ? T : 1;                 // a prefix grows by at most one token per frame: never overflows
   p.pool_cap = p.PB * p.cap;             // at most PB new cells per frame: never compacts
@@ -218,7 +189,7 @@ int wekws_hip_ctc_kws_reset(void* h, const int32_t* ids, int n, int all, void* s
   if (!o) return fail(WEKWS_HIP_EINVAL, "NULL handle");
   if (n < 0 || (n > 0 && !ids)) return fail(WEKWS_HIP_EINVAL, "ctc_kws_reset: n=%d", n);
   if (n == 0) return WEKWS_HIP_OK;
-  Guard g(o->device);
+  DeviceGuard g(o->device);
   if (wekws::launch_ctc_kws_reset(o->p, ids, n, all, static_cast<hipStream_t>(stream)))
     return hip_fail(hipGetLastError(), "ctc_kws_reset launch");
   return WEKWS_HIP_OK;
@@ -228,7 +199,7 @@ int wekws_hip_ctc_kws_read_beam(void* h, int id, void* out, void* stream) {
   CtcKws* o = static_cast<CtcKws*>(h);
   if (!o || !out) return fail(WEKWS_HIP_EINVAL, "NULL argument");
   if (id < 0 || id >= o->p.n_slots) return fail(WEKWS_HIP_EINVAL, "ctc_kws_read_beam: id %d outside 0..%d", id, o->p.n_slots - 1);
-  Guard g(o->device);
+  DeviceGuard g(o->device);
   if (wekws::launch_ctc_kws_read_beam(o->p, id, static_cast<char*>(out), static_cast<hipStream_t>(stream)))
     return hip_fail(hipGetLastError(), "ctc_kws_read_beam launch");
   return WEKWS_HIP_OK;
@@ -238,7 +209,7 @@ int wekws_hip_ctc_kws_status(void* h, int id, int32_t* status_out, void* stream)
   CtcKws* o = static_cast<CtcKws*>(h);
   if (!o || !status_out) return fail(WEKWS_HIP_EINVAL, "NULL argument");
   if (id < 0 || id >= o->p.n_slots) return fail(WEKWS_HIP_EINVAL, "ctc_kws_status: id %d outside 0..%d", id, o->p.n_slots - 1);
-  Guard g(o->device);
+  DeviceGuard g(o->device);
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const char* src = o->slots + size_t(id) * o->p.slot_bytes + offsetof(wekws::CtcSlotHead, status);
   hipError_t e = hipMemcpyAsync(status_out, src, 4, hipMemcpyDeviceToHost, s);

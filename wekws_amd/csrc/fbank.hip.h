@@ -649,13 +649,9 @@ inline int64_t fbank_grid(int64_t total, int resident) {
   return resident > 0 && grid > resident ? resident : grid;
 }
 
-#ifdef WEKWS_TEST_HOOKS
-// test build only: what the last launch of this thread was given and chose -- rounds, sample size, pair_ok, grid, resident, B, nsamp, nframes
-inline int* fbank_last_launch() {
-  static thread_local int rec[8];
-  return rec;
-}
-#endif
+// what the last launch of this thread was given and chose -- rounds, sample size, pair_ok, grid, resident, B, nsamp, nframes (read by
+// the test library's wekws_hip_debug_fbank_last).  Defined in fbank.hip, the one unit that calls launch_fbank.
+__attribute__((visibility("hidden"))) int* fbank_last_launch();
 
 template <typename S>
 inline int launch_fbank(const FbankParams& P, const S* pcm, int B, int nsamp, int nframes, float* feats, int resident,
@@ -666,12 +662,10 @@ inline int launch_fbank(const FbankParams& P, const S* pcm, int B, int nsamp, in
   const int64_t total = int64_t(B) * nframes;
   const int64_t grid = fbank_grid(total, resident);
   auto kern = rounds == 1 ? fbank_kernel<1, S> : rounds == 2 ? fbank_kernel<2, S> : fbank_kernel<3, S>;
-#ifdef WEKWS_TEST_HOOKS
   {
     const int v[8] = {rounds, int(sizeof(S)), int(fbank_pair_ok(nsamp, P.frame_shift, P.frame_length, pcm)), int(grid), resident, B, nsamp, nframes};
     for (int i = 0; i < 8; ++i) fbank_last_launch()[i] = v[i];
   }
-#endif
   hipLaunchKernelGGL(kern, dim3(unsigned(grid)), dim3(64 * kFbankWaves), lds, stream, P, pcm, B, nsamp, nframes, feats);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }

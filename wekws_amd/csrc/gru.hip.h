@@ -234,24 +234,12 @@ inline int launch_gru_nn(const GruRoute& r, const GruParams& P, const float* x, 
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-// runs a GRU_F32 route of select_gru_route (route.h)
-inline int launch_gru(const GruRoute& r, const GruParams& P, const float* x, int B, int T, const float* h0, float* y, float* hn,
-                      hipStream_t stream) {
-  if (r.family != GRU_F32 || P.kpre > 128) return -4;
-  return r.nn == 4 ? launch_gru_nn<4>(r, P, x, B, T, h0, y, hn, stream)
-         : r.nn == 1 ? launch_gru_nn<1>(r, P, x, B, T, h0, y, hn, stream) : -4;
-}
-
-// GRU: one workgroup per stream, behind the GRU kernels of the call (their loads sanitise, see nf_clean): a stream whose
-// features or incoming states hold a NaN / Inf is re-computed; the others cost one pass over their features.
-__global__ __launch_bounds__(256) void gru_nf_fix_kernel(const NfCtx* R, const float* x, int B, int T, const float* h0, float* hn,
-                                                                float* y) {
-  __shared__ unsigned cell;
-  const int b = blockIdx.x;
-  const int idim = R->d.idim, H = R->d.hdim, L = R->d.num_layers;
-  bool bad = nf_scan(x + int64_t(b) * T * idim, int64_t(T) * idim, &cell);
-  if (!bad && h0) bad = nf_scan_rows(h0 + int64_t(b) * H, L, H, int64_t(B) * H, &cell);
-  if (bad) nf_repair_gru(R, x, int64_t(T) * idim, h0, hn, y, int64_t(T) * R->d.odim, B, T, b);
-}
+// runs a GRU_F32 route of select_gru_route (route.h).  Defined in gru.hip, the one unit that instantiates gru_kernel.
+__attribute__((visibility("hidden")))
+int launch_gru(const GruRoute& r, const GruParams& P, const float* x, int B, int T, const float* h0, float* y, float* hn,
+               hipStream_t stream);
+// the non-finite pass behind the GRU kernels of a call that do not run it themselves (gru.hip: gru_nf_fix_kernel); false: launch failed
+__attribute__((visibility("hidden"))) bool launch_gru_nf_fix(const NfCtx* nf, const float* x, int B, int T, const float* h0, float* hn, float* y, hipStream_t stream);
 
 }  // namespace wekws
+

@@ -644,12 +644,10 @@ inline int launch_gru_f16_nn(const GruRoute& r, const GruF16Params& Q, const Gru
   return launch_gru_f16_mode<NN, 0>(Q, ws, x, B, T, h0, y, hn, 0, T, 1, stream, r.spw);
 }
 
-// runs a GRU_F16 route of select_gru_route (route.h)
-inline int launch_gru_f16(const GruRoute& r, const GruF16Params& Q, const GruF16Workspace& ws, const float* x, int B, int T,
-                          const float* h0, float* y, float* hn, hipStream_t stream) {
-  if (r.family != GRU_F16 || Q.kpre16 > 128 || Q.base.odim > 128) return -4;
-  return r.nn == 2 ? launch_gru_f16_nn<2>(r, Q, ws, x, B, T, h0, y, hn, stream)
-         : r.nn == 1 ? launch_gru_f16_nn<1>(r, Q, ws, x, B, T, h0, y, hn, stream) : -4;
-}
+// runs a GRU_F16 route of select_gru_route (route.h).  Defined in gru.hip, the one unit that instantiates gru_f16_kernel.
+__attribute__((visibility("hidden")))
+int launch_gru_f16(const GruRoute& r, const GruF16Params& Q, const GruF16Workspace& ws, const float* x, int B, int T,
+                   const float* h0, float* y, float* hn, hipStream_t stream);
 
 }  // namespace wekws
+

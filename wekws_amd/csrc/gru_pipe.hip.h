@@ -133,7 +133,7 @@ static __device__ __attribute__((noinline, unused)) void nf_repair_gru_call(cons
 
 // measurement build (tools/probe/gru_stamps.py): 100 MHz wall-clock stamps of slot 0's stages, row k, step t
 #ifdef WEKWS_GRU_PIPE_STAMPS
-__device__ unsigned long long gp_stamps[16 * 1024];
+static __device__ __attribute__((unused)) unsigned long long gp_stamps[16 * 1024];   // (read back by gru.hip, next to the kernels that write it)
 #define GP_STAMP(k, t) do { if (slot == 0 && tid == 0 && (t) < 1024) gp_stamps[(k) * 1024 + (t)] = wall_clock64(); } while (0)
 #else
 #define GP_STAMP(k, t) do {} while (0)
@@ -1268,22 +1268,10 @@ __global__ __launch_bounds__(kThreads) void gru_pipe_kernel(const GruF16Params Q
   }
 }
 
-// runs a GRU_PIPE route of select_gru_route (route.h); ws.nf is set exactly when the route runs the non-finite pass in the kernel
-inline int launch_gru_pipe(const GruRoute& r, const GruF16Params& Q, const GruPipeWorkspace& ws, const float* x, int B, int T, const float* h0,
-                           float* y, float* hn, hipStream_t stream) {
-  if (r.family != GRU_PIPE || r.lds_bytes != kGruPipeLds || (ws.nf != nullptr) != (r.nf_in_kernel != 0) || r.stages != 2 * Q.base.nlayers ||
-      r.slots < 1 || r.slots > kGruPipeMaxSlots)
-    return -4;
-  using G = GruF16Geom<1>;
-  static DynLdsGrant grant[4];
-  // <2>: at most two K steps of features in whole, 16-byte aligned octets; <4>: anything else.  pk: a time-packed first stage
-  const bool k2 = r.k2, pk = r.pk;
-  auto kern = k2 ? (pk ? gru_pipe_kernel<2, true> : gru_pipe_kernel<2, false>) : (pk ? gru_pipe_kernel<4, true> : gru_pipe_kernel<4, false>);
-  static_assert(kGruPipeLds >= int(G::LDS_BYTES), "staging buffers");
-  if (grant_dynamic_lds(kern, kGruPipeLds, grant[(k2 ? 0 : 2) + (pk ? 1 : 0)])) return -3;
-  // (grid: the stage workgroups, + one non-finite workgroup per slot behind them when the route says so: gru_pipe_kernel)
-  hipLaunchKernelGGL(kern, dim3(r.grid), dim3(kThreads), kGruPipeLds, stream, Q, ws, x, B, T, h0, y, hn, r.tiles, r.slots, r.slots_p, r.spw);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
+// runs a GRU_PIPE route of select_gru_route (route.h); ws.nf is set exactly when the route runs the non-finite pass in the kernel.
+// Defined in gru.hip, the one unit that instantiates gru_pipe_kernel.
+int launch_gru_pipe(const GruRoute& r, const GruF16Params& Q, const GruPipeWorkspace& ws, const float* x, int B, int T, const float* h0,
+                    float* y, float* hn, hipStream_t stream);
 
 }  // namespace wekws
+

@@ -36,42 +36,13 @@ int launch_splice_stream(const StreamFeRow* rows, const float* fresh, float* frs
 }  // namespace wekws
 
 // ------------------------------------------------------------------------------------------------ C ABI
-#include "../../include/wekws_hip.h"
-
-#include <cstdarg>
-#include <cstdio>
 #include <mutex>
 #include <new>
 #include <vector>
 
-namespace wekws {
-int set_last_error(int code, const char* msg);   // wekws_hip.hip
-}
+#include "host_util.h"
 
 namespace {
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  return wekws::set_last_error(code, buf);
-}
-
-int hip_fail(hipError_t e, const char* what) {
-  return fail(e == hipErrorOutOfMemory ? WEKWS_HIP_ENOMEM : WEKWS_HIP_EDEVICE, "%s: %s", what, hipGetErrorString(e));
-}
-
-struct Guard {   // the object's device for the scope; the caller's current device is restored
-  int prev = -1;
-  explicit Guard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess || prev == device) prev = -1;
-    else (void)hipSetDevice(device);
-  }
-  ~Guard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 struct StreamFe {
   int device = 0;
@@ -144,7 +115,7 @@ int wekws_hip_stream_frontend_plan(const wekws_hip_stream_frontend_cfg* cfg, con
 void wekws_hip_stream_frontend_destroy(void* h) {
   StreamFe* o = static_cast<StreamFe*>(h);
   if (!o) return;
-  Guard g(o->device);
+  DeviceGuard g(o->device);
   (void)hipDeviceSynchronize();
   for (int i = 0; i < wekws::kStreamFeRing; ++i) {
     if (o->ev[i]) (void)hipEventDestroy(o->ev[i]);
@@ -196,7 +167,7 @@ int wekws_hip_stream_frontend_create(const wekws_hip_stream_frontend_cfg* cfg, v
   o->rem.assign(n, 0); o->fr.assign(n, -1); o->off.assign(n, 0); o->lo_par.assign(n, 0); o->fr_par.assign(n, 0);
   o->seen.assign(n, 0); o->frames_total.assign(n, 0);
   o->plans.reserve(n);
-  Guard g(cfg->device);
+  DeviceGuard g(cfg->device);
   hipError_t e = hipMalloc(&o->d_tables, tables.size() * sizeof(float));
   if (e == hipSuccess) e = hipMemcpy(o->d_tables, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc(&o->lo, n * 2 * size_t(cap) * sizeof(int16_t));
@@ -261,7 +232,7 @@ int wekws_hip_stream_frontend_push(void* h, const int16_t* pcm, int B, int nmax,
   if (need_cap > Tcap) return fail(WEKWS_HIP_EINVAL, "stream_frontend_push: a row yields %d frames, Tcap is %d", need_cap, Tcap);
   if (need_cap > 0 && !feats) return fail(WEKWS_HIP_EINVAL, "NULL argument");
   // ---- the plan table, in stream order
-  Guard g(o->device);
+  DeviceGuard g(o->device);
   const hipStream_t s = static_cast<hipStream_t>(stream_);
   const int slot = o->next;
   o->next = (slot + 1) % wekws::kStreamFeRing;

@@ -1,6 +1,6 @@
 // The host side of a model's weights: the device weight image (sections, MFMA operand packing, block-floating scales and
 // bounds), the exact operand-channel balancing, and the zero-padding of a shape no kernel is built for to the next built one.
-// Part of wekws_hip.hip's translation unit (file-local: everything here is in the unnamed namespace); no device code.
+// Part of create.hip's translation unit (file-local: everything here is in the unnamed namespace); no device code.
 #pragma once
 #include <cmath>
 #include <cstdint>

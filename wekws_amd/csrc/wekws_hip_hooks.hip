@@ -1,8 +1,24 @@
-// The test hooks of libwekws_hip_hooks.so (make hooks: wekws_hip.hip compiled with -DWEKWS_TEST_HOOKS, which includes this file):
-// the route trace of a forward, the routing functions of route.h and the blob layout of blob_layout.h without a device, the GRU epoch, a CU hog, the fbank's plan and
-// table, the row softmax on chosen logits.  Not part of the ABI in include/wekws_hip.h: the product library exports nothing outside the header.
-#pragma once
+// Where a forward reports the route of every launch (model.h: trace_reset, trace) -- the one unit that differs between the two libraries.
+// libwekws_hip.so: the sinks are empty, the unit exports nothing and holds no kernel.  libwekws_hip_hooks.so (make hooks: this unit
+// compiled with -DWEKWS_TEST_HOOKS, every other object shared with the product library): the sinks record, and the unit carries the test
+// hooks: the route trace of a forward, the routing functions of route.h and the blob layout of blob_layout.h without a device, the GRU
+// epoch, a CU hog, the fbank's plan and table, the row softmax on chosen logits.  Not part of the ABI in include/wekws_hip.h.
+#include <algorithm>
+#include <cstring>
+#include <vector>
 
+#include "model.h"
+#include "ds256_stream.hip.h"
+#include "mdtc64_stream.hip.h"
+
+#ifndef WEKWS_TEST_HOOKS
+void trace_reset(int) {}
+void trace(int, const wekws::Route&) {}
+void trace(int, const wekws::GruRoute&) {}
+void trace(int, const wekws::FsmnRoute&) {}
+#else
+static thread_local wekws::Route g_last_route{};             // the route of this thread's last conv launch
+// the route of EVERY tile of this thread's last forward (wekws_hip_debug_route_trace), as records of 9 ints
 struct RouteTrace {
   int path = kTraceOther, ntiles = 0;
   int rec[kTraceMaxTiles][kRecInts];
@@ -25,12 +41,15 @@ static void route_record(const wekws::FsmnRoute& r, int* o) {
   for (int i = 0; i < kRecInts; ++i) o[i] = v[i];
 }
 template <class R>
-static void trace(int path, const R& r) {
+static void trace_record(int path, const R& r) {
   g_route_trace.path = path;
   if (g_route_trace.ntiles < kTraceMaxTiles) route_record(r, g_route_trace.rec[g_route_trace.ntiles]);
   ++g_route_trace.ntiles;
 }
-static void trace_reset(int path) {
+void trace(int path, const wekws::Route& r) { g_last_route = r; trace_record(path, r); }
+void trace(int path, const wekws::GruRoute& r) { trace_record(path, r); }
+void trace(int path, const wekws::FsmnRoute& r) { trace_record(path, r); }
+void trace_reset(int path) {
   g_route_trace.path = path;
   g_route_trace.ntiles = 0;
 }
@@ -328,3 +347,4 @@ extern "C" int wekws_hip_debug_softmax_rows(float* y, int64_t rows, int K, void*
   if (!wekws::launch_softmax_rows(y, rows, K, static_cast<hipStream_t>(stream_))) return fail(WEKWS_HIP_EDEVICE, "softmax launch failed");
   return WEKWS_HIP_OK;
 }
+#endif  // WEKWS_TEST_HOOKS
