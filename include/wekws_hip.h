@@ -635,6 +635,73 @@ int wekws_hip_stream_frontend_reset(void* h, const int32_t* ids, int n);
 /* counts_out = {rem, fr (-1 = none), off, rows delivered since creation / reset} of stream id. */
 int wekws_hip_stream_frontend_counts(void* h, int id, int32_t counts_out[4]);
 
+/* -------------------------------------------------------------------------------------------
+ * Resampling  --  the `resample` step of the data pipeline (wekws/dataset/processor.py:83-103:
+ * torchaudio.transforms.Resample(orig_freq, new_freq) with its defaults, sinc_interp_hann, lowpass_filter_width 6, rolloff
+ * 0.99), for whole utterances and for chunks of many streams, on the device.  Parity is pinned to a float64 restatement of
+ * torchaudio's published algorithm and to scipy.signal.upfirdn with the same taps.
+ * With g = gcd(orig, new), o = orig / g, n = new / g, base = min(o, n) rolloff, width = ceil(lpw o / base), K = 2 width + o:
+ *   t[i][m]    = clamp(((m - width) / o - i / n) base, -lpw, +lpw)          i = 0..n-1, m = 0..K-1   (float64)
+ *   k[i][m]    = float32(sinc(pi t) cos^2(pi t / (2 lpw)) base / o)
+ *   y[j n + i] = sum_m k[i][m] x[j o + m - width]                           x = 0 outside [0, L);  len(y) = ceil(n L / o)
+ * Only the taps where the clamp is inactive are accumulated (the others are exactly 0 in float32), ascending in m, with fmaf
+ * in float32.  Float input holding NaN / +-Inf is convolved over all K taps, as the reference does (0 NaN = NaN).  Equal
+ * rates copy.  A pair whose table of live taps does not fit the kernel's LDS budget (64 KB) is refused at creation with
+ * WEKWS_HIP_EUNSUPPORTED; {8000, 11025, 12000, 22050, 24000, 32000, 44100, 48000, 96000} -> 16000 and 16000 -> 8000 fit.
+ * int16 output is rint (half to even) of the float32 sum, then saturation to [-32768, 32767].
+ *
+ * Streaming: a stream's output q is emitted by the first push after which every live tap of it lies on a received sample;
+ * the concatenation of a stream's outputs, ended by a flush, equals the one-shot result of its whole signal bit for bit.
+ * ------------------------------------------------------------------------------------------*/
+enum wekws_hip_resample_out { WEKWS_HIP_RESAMPLE_OUT_F32 = 0, WEKWS_HIP_RESAMPLE_OUT_I16 = 1 };
+
+typedef struct wekws_hip_resample_cfg {
+  int32_t orig_freq, new_freq;   /* > 0 */
+  int32_t lowpass_filter_width;  /* >= 1 (reference: 6) */
+  int32_t out_dtype;             /* enum wekws_hip_resample_out */
+  double rolloff;                /* 0 < rolloff <= 1 (reference: 0.99) */
+  int32_t max_streams;           /* stream ids 0 .. max_streams - 1; 0 = one-shot only */
+  int32_t max_chunk;             /* largest nmax of a push (>= 1 with streams) */
+  int32_t device;
+  int32_t reserved[3];
+} wekws_hip_resample_cfg;
+
+int wekws_hip_resample_create(const wekws_hip_resample_cfg* cfg, void** out);
+void wekws_hip_resample_destroy(void* h);
+/* ceil(new nsamp / orig) in 64 bits, on the host alone (no device, no handle); -1 for rates <= 0 or nsamp < 0. */
+int64_t wekws_hip_resample_num_samples(int orig_freq, int new_freq, int64_t nsamp);
+/*
+ * One-shot.  pcm (B, nmax) device float32 (_compute) or int16 (_compute_i16); nsamp (B) HOST int32 valid samples per row, or
+ * NULL = nmax;  out (B, mcap) device, float32 or int16 as the handle's out_dtype: row b receives its
+ * wekws_hip_resample_num_samples(orig, new, nsamp[b]) samples and zeros behind them.  A row that yields more than mcap samples
+ * returns WEKWS_HIP_EINVAL and launches nothing.  nmax, mcap <= 2^30 - 1.  Calls may be queued back to back on `stream` without
+ * a synchronise (the row table travels through a ring of pinned tables, grown on demand: a call with more rows than any before
+ * it allocates, so not inside a stream capture).  As for _push, calls on one handle are serialised by a mutex and by the
+ * caller's stream: use one stream per handle, for _compute and _push alike.
+ */
+int wekws_hip_resample_compute(void* h, const float* pcm, int B, int nmax, const int32_t* nsamp, void* out, int mcap, void* stream);
+int wekws_hip_resample_compute_i16(void* h, const int16_t* pcm, int B, int nmax, const int32_t* nsamp, void* out, int mcap,
+                                   void* stream);
+/*
+ * Streaming.  pcm (B, nmax) device int16; row b continues stream stream_ids[b] with its first nsamp[b] samples (0 .. nmax);
+ * stream_ids, nsamp (B) HOST int32, distinct ids, any subset in any order;  out (B, mcap) device as for _compute: row b
+ * receives its counts[b] new samples and zeros behind them;  counts (B) HOST int32 out.  flush != 0 also emits every row's
+ * tail, with zeros beyond the stream's last sample, up to ceil(new N / orig) in total, and ends the stream: a later push to it
+ * is refused until it is reset.  The whole call is planned on the host first: a bad or repeated id, nsamp[b] outside 0 ..
+ * nmax, nmax > max_chunk, a row that yields more than mcap samples or a push after a flush returns WEKWS_HIP_EINVAL, launches
+ * nothing and changes no stream.  Pushes may be queued back to back on `stream` without a synchronise (the per-row plan
+ * travels in stream order through a ring of pinned tables; not inside a stream capture).  Calls on one handle are serialised
+ * by a mutex and by the caller's stream: use one stream per handle.
+ */
+int wekws_hip_resample_push(void* h, const int16_t* pcm, int B, int nmax, const int32_t* stream_ids, const int32_t* nsamp, int flush,
+                            void* out, int mcap, int32_t* counts, void* stream);
+/* A row capacity mcap that always suffices for chunks of up to nmax samples (with flush: the tail included). */
+int wekws_hip_resample_max_out(void* h, int nmax, int flush);
+/* The n streams in ids (HOST int32) start over: nothing received, nothing kept, not flushed. */
+int wekws_hip_resample_reset(void* h, const int32_t* ids, int n);
+/* counts_out = {samples received, samples emitted, samples kept on the device, flushed (0 / 1)} of stream id. */
+int wekws_hip_resample_counts(void* h, int id, int64_t counts_out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,9 +2,13 @@
 // (runtime/core/bin/kws_main.cc:23-61) so that scripts built around it keep working:
 //   kws_main fbank_dim(int) batch_size(int) kws_model_path test_wav_path
 //   -> one line per frame:  "frame <index> prob <p0> <p1> ..."   (6 significant digits, like operator<<(float))
-// The wav file is decoded, its features come from the GPU fbank (wenet::FeaturePipeline here), and the spotter is fed
+// The wav file is decoded, a file whose header rate is not 16000 is resampled to it on the GPU (wekws_hip_resample_*: the
+// `resample` step the reference's recipes put in front of the features), its features come from the GPU fbank
+// (wenet::FeaturePipeline here), and the spotter is fed
 // `batch_size` frames at a time with its streaming cache carried from call to call.  model_path may be the exporter's
 // .onnx, an ORT-format .ort, or a packed model (runtime/kws/model_file.h).
+#include <hip/hip_runtime_api.h>
+
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -51,6 +55,40 @@ void PrintRows(const Frames& rows, size_t first_index) {
   std::fflush(stdout);
 }
 
+constexpr int kModelRate = 16000;
+
+// samples at `rate` -> samples at 16 kHz, float32 in int16 scale as the pipeline takes them (the one-shot float entry point)
+std::vector<float> ResampleTo16k(const std::vector<float>& in, int rate) {
+  wekws_hip_resample_cfg cfg{};
+  cfg.orig_freq = rate;
+  cfg.new_freq = kModelRate;
+  cfg.lowpass_filter_width = 6;
+  cfg.rolloff = 0.99;
+  cfg.out_dtype = WEKWS_HIP_RESAMPLE_OUT_F32;
+  void* rs = nullptr;
+  WEKWS_CHECK(wekws_hip_resample_create(&cfg, &rs) == WEKWS_HIP_OK) << "resampling " << rate << " Hz: " << wekws_hip_last_error();
+  const int64_t n_out = wekws_hip_resample_num_samples(rate, kModelRate, static_cast<int64_t>(in.size()));
+  WEKWS_CHECK(in.size() <= 0x3fffffff && n_out >= 0 && n_out <= 0x3fffffff) << "file too long to resample in one call";
+  std::vector<float> out(static_cast<size_t>(n_out));
+  if (n_out == 0) {
+    wekws_hip_resample_destroy(rs);
+    return out;
+  }
+  float* d_in = nullptr;
+  float* d_out = nullptr;
+  WEKWS_CHECK(hipMalloc(reinterpret_cast<void**>(&d_in), in.size() * sizeof(float)) == hipSuccess);
+  WEKWS_CHECK(hipMalloc(reinterpret_cast<void**>(&d_out), out.size() * sizeof(float)) == hipSuccess);
+  WEKWS_CHECK(hipMemcpy(d_in, in.data(), in.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess);
+  WEKWS_CHECK(wekws_hip_resample_compute(rs, d_in, 1, static_cast<int>(in.size()), nullptr, d_out, static_cast<int>(n_out), nullptr) ==
+              WEKWS_HIP_OK)
+      << wekws_hip_last_error();
+  WEKWS_CHECK(hipMemcpy(out.data(), d_out, out.size() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess);
+  (void)hipFree(d_in);
+  (void)hipFree(d_out);
+  wekws_hip_resample_destroy(rs);
+  return out;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -62,8 +100,9 @@ int main(int argc, char** argv) {
     wenet::WavReader reader(opt.audio);
     WEKWS_CHECK(reader.ok()) << "cannot read " << opt.audio;
     samples.assign(reader.data(), reader.data() + reader.num_samples());
+    if (reader.sample_rate() != kModelRate) samples = ResampleTo16k(samples, reader.sample_rate());
   }
-  wenet::FeaturePipeline features(wenet::FeaturePipelineConfig(opt.feature_dim, 16000));
+  wenet::FeaturePipeline features(wenet::FeaturePipelineConfig(opt.feature_dim, kModelRate));
   features.AcceptWaveform(samples);
   features.set_input_finished();
 

@@ -2,7 +2,7 @@
 """Secondary measurements for the other BASELINE.json configs (one JSON line each, not the bench.py contract):
 batch throughput of every backbone, streaming per-frame latency (B=1, 10-frame chunks, carried cache), fbank
 front-end throughput.  GPU only.   python tools/bench_configs.py > gpurun_out/configs.jsonl"""
-# (also: the streaming front end, filter `stream_frontend`)
+# (also: the streaming front end, filter `stream_frontend`; the streaming resampler in front of it, filter `resample`)
 import json
 import os
 import sys
@@ -229,6 +229,39 @@ def main():
                 dmed, dp10, dp90 = timeit(lambda: kws.forward(chunk), warm=2, reps=5, group=4)
                 row.update(ms_pcm_to_detection=round(dmed, 4), detection_p10=round(dp10, 4), detection_p90=round(dp90, 4),
                            model="fsmn_ctc300")
+            out.append(row)
+            print(json.dumps(out[-1]), flush=True)
+    # streaming resampler: 4096 streams x 14400-sample chunks at 48 kHz (0.3 s) in steady state -- time per push, the same as a
+    # fraction of the time to move the call's input and output bytes at the 8 TB/s of DESIGN.md section 5, and in the same run PCM
+    # -> detection (fsmn_ctc300) from 16 kHz chunks and from the 48 kHz chunks of the same duration
+    if only in "resample":
+        from wekws_amd.frontend import StreamingResampler
+        from wekws_amd.stream import BatchedKeyWordSpotter
+        B, n = 4096, 14400
+        g = torch.Generator(device="cuda").manual_seed(7)
+        chunk = torch.randint(-20000, 20000, (B, n), device="cuda", generator=g, dtype=torch.int32).to(torch.int16)
+        for dt in (torch.int16, torch.float32):
+            rs = StreamingResampler(B, 48000, 16000, max_chunk=n, out_dtype=dt)
+            cap = rs.max_out(n)
+            counts = rs.push(chunk, capacity=cap)[1]
+            counts = rs.push(chunk, capacity=cap)[1]                # steady state: every stream holds its history
+            med, p10, p90 = timeit(lambda: rs.push(chunk, capacity=cap), reps=10, group=10)
+            moved = B * (n * 2 + cap * (2 if dt == torch.int16 else 4))
+            row = dict(kind="resample", config="48000->16000/" + ("int16" if dt == torch.int16 else "float32") + " out", B=B, chunk=n,
+                       samples_per_push=int(counts[0]), ms_push=round(med, 4), p10=round(p10, 4), p90=round(p90, 4),
+                       bytes_moved=moved, ms_at_8TBs=round(moved / 8e12 * 1e3, 4), hbm_fraction=round(moved / 8e12 * 1e3 / med, 3),
+                       chunks_per_s=round(B / med * 1e3, 1))
+            if dt == torch.int16:
+                _, m = build("fsmn_ctc300")
+                fe_kw = dict(num_bins=80, window="povey", left=2, right=2, skip=3)
+                for label, rate, c in (("ms_pcm_to_detection_16k", None, chunk[:, :n // 3].contiguous()), ("ms_pcm_to_detection_48k", 48000, chunk)):
+                    extra = {} if rate is None else dict(input_sample_rate=rate)
+                    kws = BatchedKeyWordSpotter(m, {"k0": (1, 2, 3)}, 0.5, B, max_chunk=int(c.size(1)), **fe_kw, **extra)
+                    kws.forward(c)
+                    dmed, dp10, dp90 = timeit(lambda: kws.forward(c), warm=2, reps=5, group=4)
+                    row.update({label: round(dmed, 4), label + "_p10": round(dp10, 4), label + "_p90": round(dp90, 4)})
+                    del kws
+                row.update(model="fsmn_ctc300")
             out.append(row)
             print(json.dumps(out[-1]), flush=True)
     fb = Fbank(40)

@@ -39,6 +39,11 @@ class StreamFrontendCfg(C.Structure):
                [("reserved", C.c_int32 * 2)]
 
 
+class ResampleCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("orig_freq", "new_freq", "lowpass_filter_width", "out_dtype")] + [("rolloff", C.c_double)] + \
+               [(n, C.c_int32) for n in ("max_streams", "max_chunk", "device")] + [("reserved", C.c_int32 * 3)]
+
+
 class CtcKwsResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("status", "valid", "state", "keyword", "start", "end")] + [("score", C.c_double)]
 
@@ -112,6 +117,16 @@ SIGNATURES = {
                                                  C.c_int, C.c_void_p, C.c_void_p]),
     "wekws_hip_stream_frontend_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "wekws_hip_stream_frontend_counts": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
+    "wekws_hip_resample_create": (C.c_int, [C.POINTER(ResampleCfg), C.POINTER(C.c_void_p)]),
+    "wekws_hip_resample_destroy": (None, [C.c_void_p]),
+    "wekws_hip_resample_num_samples": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
+    "wekws_hip_resample_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "wekws_hip_resample_compute_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "wekws_hip_resample_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_int, C.c_void_p, C.c_void_p]),
+    "wekws_hip_resample_max_out": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "wekws_hip_resample_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "wekws_hip_resample_counts": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
 }
 
 OPTIONS = {"w16": 0, "mdtc16": 1, "stream": 2, "mm": 3, "head_slices": 4, "g16": 5, "envelope": 6, "gru_pipe": 7}   # enum wekws_hip_option

@@ -1,0 +1,223 @@
+// The resampler on the device: torchaudio's Resample (resample_plan.h states the definition) as a polyphase FIR over the live
+// taps of every phase, for whole utterances (one-shot) and for chunks of many streams (streaming), by ONE kernel.  What a row
+// is -- an utterance from its first sample, or a stream's [history | chunk] continued at its next output -- is decided on
+// the host and told through one ResampleRow; the arithmetic of an output sample is resample_sample for both, the live taps of
+// the output's phase in ascending m with fmaf from 0, so a stream's sample equals the one-shot sample bit for bit.
+//
+//   workgroup   256 lanes, one output per lane, 256 consecutive outputs of a row per tile; persistent over the (row, tile)
+//               grid, so the tap table is loaded once per workgroup.
+//   LDS         the live part of the tap table, (n, stride) floats with an odd stride (neighbouring lanes hold neighbouring
+//               phases: rows stride apart fall on different banks), the live range of every phase, and the tile's input in
+//               its source type (int16 / float) -- every sample under the FULL K-tap windows of the tile's outputs, staged
+//               with 16-byte loads wherever 16 source bytes lie inside the row's chunk (the tile's start is moved down to the
+//               source's alignment), sample by sample across the history / chunk seam and the row's ends (zeros outside).
+//   non-finite  (float input) the reference convolves all K taps, the zeros included, and 0 NaN = 0 Inf = NaN.  Staging sees
+//               every sample under the full windows; a tile that holds an all-ones exponent recomputes its outputs over the
+//               K taps of the full table in global memory, in plain IEEE f32.  Finite input never takes that path.
+//               The scan is over the whole staged tile: up to 7 samples of alignment slack in front, and behind the windows of
+//               the tile's outputs whatever the tile's capacity (sized for the most j-blocks 256 outputs can touch) still holds.
+//               A NaN / Inf just outside the windows therefore sends the tile down the K-tap path without need.  Its outputs
+//               are then the same sums with terms of (+-0) x added: within the bar, equal as numbers, but a sum of -0 can come
+//               out as +0 -- that path is not bit-identical to the live-tap path on such a tile.
+//   history     the workgroup of a row's tile 0 writes the samples the stream keeps into the stream's OTHER buffer: the
+//               other tiles still read the old one.
+//   int16 out   rint (half to even), then saturation to [-32768, 32767]; NaN gives 0.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <mutex>
+#include <type_traits>
+#include <vector>
+
+#include "resample_plan.h"
+
+namespace wekws {
+
+constexpr int kResampleTile = 256;            // outputs of a tile = lanes of a workgroup
+constexpr int kResampleRing = 4;              // plan tables in flight (resample.hip)
+constexpr int kResampleLdsBudget = 64 * 1024; // live table + live ranges + input tile
+constexpr int kResampleVec = 8;               // samples of the widest 16-byte group (int16)
+
+struct ResampleRow {        // what the kernel knows about one row (12 x int32); positions are relative to the row's origin:
+                            // sample 0 of an utterance, the first kept sample of a stream
+  int32_t i0;               // phase of the row's first output
+  int32_t base_rel;         // position of tap 0 of that output's block: j0 o - width - origin
+  int32_t cnt;              // outputs to compute
+  int32_t h;                // history samples: positions [0, h) are the stream's buffer, [h, hi_valid) the chunk
+  int32_t hi_valid;         // end of the samples there are (zeros beyond, and before 0)
+  int32_t hist_old, hist_new;   // sample offsets of the stream's history buffers (read / written)
+  int32_t keep_from, keep_cnt;  // positions [keep_from, keep_from + keep_cnt) become the new history
+  int32_t reserved[3];
+};
+
+struct ResampleParams {
+  int32_t o, n, K, width;
+  int32_t stride;           // floats per row of the live table (odd)
+  int32_t tile_cap;         // samples of the input tile (a multiple of kResampleVec)
+  int32_t tile_off;         // its byte offset in LDS (a multiple of 16)
+  int32_t reserved;
+  const float* live;        // (n, stride): taps first_i .. last_i of phase i, then zeros
+  const int32_t* first;     // (n)
+  const int32_t* count;     // (n) live taps of every phase
+  const float* full;        // (n, K)
+};
+
+// j-blocks that 256 consecutive outputs touch at most
+inline int resample_jspan(int n) { return (n + kResampleTile - 2) / n + 1; }
+inline int resample_stride(int max_live) { return max_live | 1; }
+inline int64_t resample_tile_cap(const ResamplePlan& p) {
+  const int64_t c = int64_t(resample_jspan(p.n)) * p.o + 2 * int64_t(p.width) + kResampleVec;
+  return (c + kResampleVec - 1) / kResampleVec * kResampleVec;
+}
+// LDS bytes of a launch with float samples (the larger of the two source types); tile_off if given
+inline int64_t resample_lds_bytes(const ResamplePlan& p, int64_t* tile_off = nullptr) {
+  int64_t table = (int64_t(p.n) * resample_stride(p.max_live) + 2 * int64_t(p.n)) * 4;
+  table = (table + 15) / 16 * 16;
+  if (tile_off) *tile_off = table;
+  return table + resample_tile_cap(p) * 4;
+}
+
+// One output sample: the live taps of its phase, ascending, fmaf from 0.  taps: the phase's row of the live table; x: the sample
+// under the first live tap.
+template <typename In>
+__device__ __forceinline__ float resample_sample(const float* taps, int cnt, const In* x) {
+  float acc = 0.f;
+  for (int m = 0; m < cnt; ++m) acc = fmaf(taps[m], float(x[m]), acc);
+  return acc;
+}
+
+// position rel of the row's virtual signal [history | chunk], zeros outside
+template <typename In>
+__device__ __forceinline__ In resample_fetch(const ResampleRow& R, const In* hist, const In* chunk, int rel) {
+  if (rel < 0 || rel >= R.hi_valid) return In(0);
+  return rel < R.h ? hist[R.hist_old + rel] : chunk[rel - R.h];
+}
+
+template <typename Out>
+__device__ __forceinline__ Out resample_out(float v) {
+  if constexpr (std::is_same<Out, float>::value) {
+    return v;
+  } else {
+    if (v != v) return Out(0);
+    const float r = fminf(fmaxf(rintf(v), -32768.f), 32767.f);
+    return Out(int(r));
+  }
+}
+
+__device__ __forceinline__ int resample_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+template <typename In, typename Out>
+__global__ __launch_bounds__(kResampleTile) void resample_kernel(const ResampleParams P, const ResampleRow* __restrict__ rows,
+                                                                 const In* __restrict__ x, int64_t xstride, In* hist,
+                                                                 Out* __restrict__ y, int mcap, int tiles_per_row,
+                                                                 int64_t total_tiles) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char resample_lds[];
+  constexpr int V = 16 / int(sizeof(In));
+  constexpr bool kFloatIn = std::is_same<In, float>::value;
+  float* const taps = reinterpret_cast<float*>(resample_lds);
+  int* const first = reinterpret_cast<int*>(taps + P.n * P.stride);
+  int* const count = first + P.n;
+  In* const tile = reinterpret_cast<In*>(resample_lds + P.tile_off);
+  const int tid = threadIdx.x;
+  for (int e = tid; e < P.n * P.stride; e += kResampleTile) taps[e] = P.live[e];
+  for (int e = tid; e < P.n; e += kResampleTile) { first[e] = P.first[e]; count[e] = P.count[e]; }
+  __syncthreads();
+
+  for (int64_t t = blockIdx.x; t < total_tiles; t += gridDim.x) {
+    const int b = int(t / tiles_per_row), tl = int(t - int64_t(b) * tiles_per_row);
+    const ResampleRow R = rows[b];
+    const In* const chunk = x + int64_t(b) * xstride;
+    Out* const yrow = y + int64_t(b) * mcap;
+    const int r0 = tl * kResampleTile, r = r0 + tid;
+    if (tl == 0)
+      for (int e = tid; e < R.keep_cnt; e += kResampleTile) hist[R.hist_new + e] = resample_fetch(R, hist, chunk, R.keep_from + e);
+    if (r0 >= R.cnt) {                                           // (the whole workgroup: a tile past the row's count is zeros)
+      if (r < mcap) yrow[r] = Out(0);
+      continue;
+    }
+    // ---- the samples under the full windows of the tile's outputs, from position tile_lo on
+    const int jt0 = (R.i0 + r0) / P.n;
+    int tile_lo = R.base_rel + jt0 * P.o;
+    const int64_t src = int64_t(reinterpret_cast<uintptr_t>(chunk) / sizeof(In)) + (tile_lo - R.h);
+    const int a = int(((src % V) + V) % V);                      // down to a 16-byte boundary of the chunk
+    tile_lo -= a;
+    int bad = 0;
+    for (int g = tid; g < P.tile_cap / V; g += kResampleTile) {
+      const int rel = tile_lo + g * V;
+      if (rel >= 0 && rel >= R.h && rel + V <= R.hi_valid) {
+        const uint4 v = *reinterpret_cast<const uint4*>(chunk + (rel - R.h));
+        *reinterpret_cast<uint4*>(tile + g * V) = v;
+        if constexpr (kFloatIn)
+          bad |= resample_nonfinite(__uint_as_float(v.x)) | resample_nonfinite(__uint_as_float(v.y)) |
+                 resample_nonfinite(__uint_as_float(v.z)) | resample_nonfinite(__uint_as_float(v.w));
+      } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+          const In s = resample_fetch(R, hist, chunk, rel + k);
+          tile[g * V + k] = s;
+          if constexpr (kFloatIn) bad |= resample_nonfinite(s);
+        }
+      }
+    }
+    if constexpr (kFloatIn) bad = __syncthreads_or(bad);
+    else __syncthreads();
+    // ---- one output per lane
+    float acc = 0.f;
+    const bool live = r < R.cnt;
+    if (live) {
+      const int qq = R.i0 + r, jj = qq / P.n, i = qq - jj * P.n;
+      const In* const xs = tile + ((jj - jt0) * P.o + a);        // the sample under tap 0 of the output's block
+      if (kFloatIn && bad) {
+        const float* const k = P.full + int64_t(i) * P.K;
+        for (int m = 0; m < P.K; ++m) acc = fmaf(k[m], float(xs[m]), acc);
+      } else {
+        acc = resample_sample(taps + i * P.stride, count[i], xs + first[i]);
+      }
+    }
+    if (r < mcap) yrow[r] = live ? resample_out<Out>(acc) : Out(0);
+    __syncthreads();                                             // the next tile overwrites the samples
+  }
+}
+
+int launch_resample(const ResampleParams& P, size_t lds, int in_i16, int out_i16, const ResampleRow* rows, const void* x,
+                    int64_t xstride, int16_t* hist, void* y, int B, int mcap, int max_grid, hipStream_t stream);
+
+}  // namespace wekws
+
+// the handle of wekws_hip_resample_* (resample.hip; the hooks unit rounds its tables)
+struct wekws_hip_resample {
+  int device = 0;
+  wekws::ResamplePlan plan;
+  wekws::ResampleParams P{};
+  size_t lds = 0;
+  int out_i16 = 0, max_streams = 0, max_chunk = 0, hist_cap = 0, max_grid = 1;
+  float* d_live = nullptr;
+  float* d_full = nullptr;
+  int32_t* d_meta = nullptr;           // first (n) | count (n)
+  int16_t* hist = nullptr;             // (max_streams, 2, hist_cap) kept samples, ping-ponged per stream
+  // the plan table of a push travels through a ring of pinned host tables, each with its device twin and an event recorded
+  // behind the push that used it (as the streaming front end's)
+  wekws::ResampleRow* h_rows[wekws::kResampleRing] = {};
+  wekws::ResampleRow* d_rows[wekws::kResampleRing] = {};
+  hipEvent_t ev[wekws::kResampleRing] = {};
+  bool ev_used[wekws::kResampleRing] = {};
+  int next = 0;
+  // the row table of a one-shot call: the same kind of ring, every slot grown on demand (B is the caller's)
+  struct OnceSlot {
+    wekws::ResampleRow* h = nullptr;
+    wekws::ResampleRow* d = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+    bool used = false;
+  };
+  OnceSlot once_ring[wekws::kResampleRing];
+  int once_next = 0;
+  std::mutex mu;
+  // per-stream counts live on the host: the outputs of every row are known without a device read-back
+  std::vector<int64_t> received, emitted, origin;   // origin: the first kept sample
+  std::vector<int32_t> par, seen, flushed;
+  int32_t epoch = 0;
+  std::vector<wekws::ResampleStep> steps;           // of the push being planned
+  std::vector<wekws::ResampleRow> once;             // of the one-shot call being planned
+};

@@ -2,7 +2,7 @@
 // libwekws_hip.so: the sinks are empty, the unit exports nothing and holds no kernel.  libwekws_hip_hooks.so (make hooks: this unit
 // compiled with -DWEKWS_TEST_HOOKS, every other object shared with the product library): the sinks record, and the unit carries the test
 // hooks: the route trace of a forward, the routing functions of route.h and the blob layout of blob_layout.h without a device, the GRU
-// epoch, a CU hog, the fbank's plan and table, the row softmax on chosen logits.  Not part of the ABI in include/wekws_hip.h.
+// epoch, a CU hog, the fbank's plan and table, the row softmax on chosen logits, the resampler's taps and plan.  Not part of the ABI in include/wekws_hip.h.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -10,6 +10,7 @@
 #include "model.h"
 #include "ds256_stream.hip.h"
 #include "mdtc64_stream.hip.h"
+#include "resample.hip.h"
 
 #ifndef WEKWS_TEST_HOOKS
 void trace_reset(int) {}
@@ -345,6 +346,72 @@ extern "C" int wekws_hip_debug_softmax_rows(float* y, int64_t rows, int K, void*
   if (!y || rows < 0 || K <= 0 || (rows + 3) / 4 > 0x7fffffffLL) return fail(WEKWS_HIP_EINVAL, "softmax_rows: rows=%lld K=%d", (long long)rows, K);
   if (rows == 0) return WEKWS_HIP_OK;
   if (!wekws::launch_softmax_rows(y, rows, K, static_cast<hipStream_t>(stream_))) return fail(WEKWS_HIP_EDEVICE, "softmax launch failed");
+  return WEKWS_HIP_OK;
+}
+
+// --------------------------------------------- resample ---------------------------------------------
+// The plan of a rate pair, WITHOUT a device (resample_plan.h alone).  dims[10]: o, n, width, K, most live taps of a phase, stride of
+// the live table, LDS bytes of a launch, samples of the input tile, history capacity of a stream, outputs of a tile.  taps: NULL, or
+// (n, K) floats; first / last: NULL, or (n) ints -- filled only if cap_taps >= n K and cap_phases >= n.  Returns 0, WEKWS_HIP_EINVAL
+// for parameters no resampler has.  (A pair the kernels refuse for its size still has a plan; taps are then only computed on request.)
+extern "C" int wekws_hip_debug_resample_plan(int orig, int neu, int lpw, double rolloff, int64_t* dims, float* taps, int64_t cap_taps,
+                                             int32_t* first, int32_t* last, int64_t cap_phases) {
+  if (!dims) return WEKWS_HIP_EINVAL;
+  wekws::ResamplePlan p;
+  if (wekws::resample_plan_ranges(orig, neu, lpw, rolloff, &p)) return WEKWS_HIP_EINVAL;
+  const int64_t v[10] = {p.o, p.n, p.width, p.K, p.max_live, wekws::resample_stride(p.max_live), wekws::resample_lds_bytes(p),
+                         wekws::resample_tile_cap(p), (wekws::resample_hist_cap(p) + 1) & ~1, wekws::kResampleTile};
+  for (int i = 0; i < 10; ++i) dims[i] = v[i];
+  if (first && last && cap_phases >= p.n)
+    for (int i = 0; i < p.n; ++i) { first[i] = p.first[size_t(i)]; last[i] = p.last[size_t(i)]; }
+  if (taps && cap_taps >= int64_t(p.n) * p.K) {
+    wekws::resample_plan_taps(&p);
+    std::memcpy(taps, p.taps.data(), p.taps.size() * sizeof(float));
+  }
+  return WEKWS_HIP_OK;
+}
+// One push onto one stream, WITHOUT a device: the function wekws_hip_resample_push decides every row with.  A stream that has received
+// N samples is given nsamp more (flush: and ended).  out[4]: outputs emitted in total after the push, first sample the stream keeps,
+// outputs emitted in total BEFORE it (resample_emit_count(N)), capacity wekws_hip_resample_max_out gives for nsamp.  Returns 0.
+extern "C" int wekws_hip_debug_resample_step(int orig, int neu, int lpw, double rolloff, int64_t N, int64_t nsamp, int flush, int64_t* out) {
+  if (!out || N < 0 || nsamp < 0) return WEKWS_HIP_EINVAL;
+  wekws::ResamplePlan p;
+  if (wekws::resample_plan_ranges(orig, neu, lpw, rolloff, &p)) return WEKWS_HIP_EINVAL;
+  const wekws::ResampleStep s = wekws::resample_step(p, N, nsamp, flush);
+  out[0] = s.total; out[1] = s.keep_from; out[2] = wekws::resample_emit_count(p, N); out[3] = wekws::resample_max_out(p, nsamp, flush);
+  return WEKWS_HIP_OK;
+}
+// A whole schedule of pushes onto one stream (the last one flushed if flush_last), WITHOUT a device: totals[k] / keeps[k] after push k.
+extern "C" int wekws_hip_debug_resample_schedule(int orig, int neu, int lpw, double rolloff, const int32_t* chunks, int nchunks,
+                                                 int flush_last, int64_t* totals, int64_t* keeps) {
+  if (!chunks || !totals || !keeps || nchunks < 0) return WEKWS_HIP_EINVAL;
+  wekws::ResamplePlan p;
+  if (wekws::resample_plan_ranges(orig, neu, lpw, rolloff, &p)) return WEKWS_HIP_EINVAL;
+  int64_t N = 0;
+  for (int k = 0; k < nchunks; ++k) {
+    if (chunks[k] < 0) return WEKWS_HIP_EINVAL;
+    const wekws::ResampleStep s = wekws::resample_step(p, N, chunks[k], flush_last && k == nchunks - 1);
+    N += chunks[k];
+    totals[k] = s.total; keeps[k] = s.keep_from;
+  }
+  return WEKWS_HIP_OK;
+}
+// Round the handle's taps -- the live table and the full one -- to fp16 values, in place: the negative control of the resampler's bar
+// (a kernel that took its taps at half precision must miss it).  There is no way back: destroy the handle afterwards.
+extern "C" int wekws_hip_debug_resample_round_taps_f16(wekws_hip_resample* r) {
+  if (!r) return fail(WEKWS_HIP_EINVAL, "NULL handle");
+  DeviceGuard guard(r->device);
+  if (!guard.ok) return fail(WEKWS_HIP_EDEVICE, "hipSetDevice(%d)", r->device);
+  std::vector<float> live(size_t(r->P.n) * r->P.stride), full(size_t(r->P.n) * r->P.K);
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(live.data(), r->d_live, live.size() * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(full.data(), r->d_full, full.size() * sizeof(float), hipMemcpyDeviceToHost);
+  for (float& v : live) v = float(_Float16(v));
+  for (float& v : full) v = float(_Float16(v));
+  if (e == hipSuccess) e = hipMemcpy(r->d_live, live.data(), live.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(r->d_full, full.data(), full.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "resample taps: %s", hipGetErrorString(e));
   return WEKWS_HIP_OK;
 }
 #endif  // WEKWS_TEST_HOOKS

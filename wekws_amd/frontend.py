@@ -1,8 +1,8 @@
 """Batched on-device front-end: log-mel filterbank (MI355X replacement for ``wenet::Fbank::Compute``,
 runtime/core/frontend/fbank.h:138-198, behind ``FeaturePipeline::AcceptWaveform``'s framing rule,
 runtime/core/frontend/feature_pipeline.cc:30-47) and the context-expansion / frame-skip step of the data pipeline
-(wekws/dataset/init_dataset.py:24-68).  Thin host wrappers over the C ABI (wekws_hip_fbank_*, wekws_hip_splice);
-no CPU fallback."""
+(wekws/dataset/init_dataset.py:24-68), and in front of both the `resample` step (wekws/dataset/processor.py:83-103).  Thin
+host wrappers over the C ABI (wekws_hip_fbank_*, wekws_hip_splice, wekws_hip_resample_*); no CPU fallback."""
 from __future__ import annotations
 
 import ctypes
@@ -250,4 +250,143 @@ class StreamingFrontEnd:
         """(leftover samples, remembered frames or -1, skip phase, rows delivered) of a stream: host values, no device read."""
         out = (ctypes.c_int32 * 4)()
         _capi.check(self._lib.wekws_hip_stream_frontend_counts(self._ptr, int(stream), out), "wekws_hip_stream_frontend_counts")
+        return tuple(int(v) for v in out)
+
+
+def _resample_handle(orig_freq, new_freq, out_dtype, max_streams, max_chunk, device, lowpass_filter_width=6, rolloff=0.99):
+    if out_dtype not in (torch.float32, torch.int16):
+        raise ValueError("out_dtype must be torch.float32 or torch.int16")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("the resampler runs on the MI355X HIP path only (no CPU fallback)")
+    cfg = _capi.ResampleCfg()
+    cfg.orig_freq, cfg.new_freq = int(orig_freq), int(new_freq)
+    cfg.lowpass_filter_width, cfg.rolloff = int(lowpass_filter_width), float(rolloff)
+    cfg.out_dtype = 1 if out_dtype == torch.int16 else 0
+    cfg.max_streams, cfg.max_chunk = int(max_streams), int(max_chunk)
+    cfg.device = device.index if device.index is not None else torch.cuda.current_device()
+    lib = _capi.load()
+    ptr = ctypes.c_void_p()
+    _capi.check(lib.wekws_hip_resample_create(ctypes.byref(cfg), ctypes.byref(ptr)), "wekws_hip_resample_create")
+    return lib, ptr, torch.device("cuda", cfg.device)
+
+
+class Resample:
+    """``torchaudio.transforms.Resample(orig_freq, new_freq)`` with its defaults (sinc_interp_hann, lowpass_filter_width 6,
+    rolloff 0.99: the `resample` step of wekws/dataset/processor.py:83-103) on the device.
+
+        pcm16k = Resample(44100)(pcm)           # pcm (B, nsamp) float32 or int16 on the device -> (B, ceil(nsamp 16000 / 44100))
+        feats = Mfcc()(pcm16k)
+
+    ``lengths``: the valid samples of each row (host integers); a row's output is zero past its own count, and the counts
+    are returned with it.  ``out_dtype=torch.int16`` rounds (half to even) and saturates."""
+
+    def __init__(self, orig_freq: int, new_freq: int = 16000, device="cuda", out_dtype=torch.float32):
+        self.orig_freq, self.new_freq, self.out_dtype = int(orig_freq), int(new_freq), out_dtype
+        self._ptr = ctypes.c_void_p()
+        self._lib, self._ptr, self.device = _resample_handle(orig_freq, new_freq, out_dtype, 0, 0, device)
+
+    def __del__(self):
+        try:
+            if self._ptr:
+                self._lib.wekws_hip_resample_destroy(self._ptr)
+                self._ptr = ctypes.c_void_p()
+        except Exception:
+            pass
+
+    def num_samples(self, nsamp: int) -> int:
+        return int(self._lib.wekws_hip_resample_num_samples(self.orig_freq, self.new_freq, int(nsamp)))
+
+    def __call__(self, pcm: torch.Tensor, lengths=None):
+        if not torch.is_tensor(pcm) or pcm.dim() != 2 or not pcm.is_cuda or pcm.dtype not in (torch.float32, torch.int16):
+            raise ValueError("pcm must be a (B, nsamp) float32 or int16 tensor on a ROCm device")
+        pcm = pcm.contiguous()
+        B, n = int(pcm.size(0)), int(pcm.size(1))
+        ns = None
+        if lengths is not None:
+            ns = np.ascontiguousarray(np.clip(np.asarray([int(v) for v in lengths], dtype=np.int64), -1, 2 ** 31 - 1), dtype=np.int32)
+            if ns.shape != (B,):
+                raise ValueError("lengths must have one entry per row of pcm")
+        m = self.num_samples(n)
+        out = torch.empty((B, m), dtype=self.out_dtype, device=pcm.device)
+        if B:
+            stream = torch.cuda.current_stream(pcm.device).cuda_stream
+            fn = self._lib.wekws_hip_resample_compute if pcm.dtype == torch.float32 else self._lib.wekws_hip_resample_compute_i16
+            _capi.check(fn(self._ptr, pcm.data_ptr() if n else None, B, n, ns.ctypes.data if ns is not None else None,
+                           out.data_ptr() if m else None, m, ctypes.c_void_p(stream)), "wekws_hip_resample_compute")
+        if lengths is None:
+            return out
+        return out, [self.num_samples(int(v)) for v in ns]
+
+
+class StreamingResampler:
+    """``Resample`` for ``num_streams`` streams at once, chunk by chunk (wekws_hip_resample_push): int16 chunks of any subset
+    of the streams go in, each row's new samples at ``new_freq`` come out.  A stream's outputs, ended by ``flush=True``, are
+    the one-shot result of its whole signal bit for bit; an output is emitted by the first push after which every tap that
+    can contribute to it lies on a received sample.
+
+        rs = StreamingResampler(4096, 48000, max_chunk=14400)
+        out, counts = rs.push(pcm)              # pcm (B, nmax) int16 on the device: row b continues stream b"""
+
+    def __init__(self, num_streams: int, orig_freq: int, new_freq: int = 16000, max_chunk: int = 48000, out_dtype=torch.int16,
+                 device="cuda"):
+        self.num_streams, self.max_chunk = int(num_streams), int(max_chunk)
+        self.orig_freq, self.new_freq, self.out_dtype = int(orig_freq), int(new_freq), out_dtype
+        self._ptr = ctypes.c_void_p()
+        self._lib, self._ptr, self.device = _resample_handle(orig_freq, new_freq, out_dtype, num_streams, max_chunk, device)
+
+    __del__ = Resample.__del__
+
+    def max_out(self, nmax: int, flush: bool = False) -> int:
+        """A row capacity that always suffices for chunks of up to ``nmax`` samples."""
+        return int(self._lib.wekws_hip_resample_max_out(self._ptr, int(nmax), int(bool(flush))))
+
+    def push(self, pcm, samples=None, streams=None, flush: bool = False, capacity: Optional[int] = None):
+        """``pcm``: a (B, nmax) int16 device tensor, or a list of ``bytes`` / int16 arrays (uploaded as ONE padded tensor);
+        ``samples`` / ``streams`` as for StreamingFrontEnd.push.  Returns ``(out, counts)``: out (B, max(counts)) on the
+        device (``capacity`` columns if given), zero past each row's count; counts a host list.  ``flush`` also emits the
+        rows' tails and ends their streams (until ``reset``)."""
+        if not torch.is_tensor(pcm):
+            arrs = [np.frombuffer(c, dtype="<i2") if isinstance(c, (bytes, bytearray, memoryview)) else np.asarray(c) for c in pcm]
+            if any(a.dtype != np.int16 or a.ndim != 1 for a in arrs):
+                raise ValueError("chunks must be bytes or 1-d int16 arrays")
+            if samples is None:
+                samples = [int(a.size) for a in arrs]
+            host = np.zeros((len(arrs), max([int(a.size) for a in arrs] + [0])), dtype=np.int16)
+            for i, a in enumerate(arrs):
+                host[i, :a.size] = a
+            pcm = torch.from_numpy(host).to(self.device)
+        if pcm.dim() != 2 or not pcm.is_cuda or pcm.dtype != torch.int16:
+            raise ValueError("pcm must be a (B, nmax) int16 tensor on a ROCm device")
+        pcm = pcm.contiguous()
+        B, nmax = int(pcm.size(0)), int(pcm.size(1))
+        ids = np.arange(B, dtype=np.int32) if streams is None else np.asarray([int(s) for s in streams], dtype=np.int64)
+        ns = np.full(B, nmax, dtype=np.int32) if samples is None else np.asarray([int(n) for n in samples], dtype=np.int64)
+        if ids.shape != (B,) or ns.shape != (B,):
+            raise ValueError("streams / samples must have one entry per row of pcm")
+        lim = np.iinfo(np.int32)
+        ids = np.ascontiguousarray(np.clip(ids, lim.min, lim.max), dtype=np.int32)     # (out of range stays out of range: EINVAL)
+        ns = np.ascontiguousarray(np.clip(ns, lim.min, lim.max), dtype=np.int32)
+        cap = self.max_out(nmax, flush) if capacity is None else int(capacity)
+        out = torch.empty((B, cap), dtype=self.out_dtype, device=pcm.device)
+        got = np.zeros(max(B, 1), dtype=np.int32)
+        stream = torch.cuda.current_stream(pcm.device).cuda_stream
+        _capi.check(self._lib.wekws_hip_resample_push(
+            self._ptr, pcm.data_ptr() if nmax else None, B, nmax, ids.ctypes.data if B else None, ns.ctypes.data if B else None,
+            int(bool(flush)), out.data_ptr() if cap else None, cap, got.ctypes.data, ctypes.c_void_p(stream)),
+            "wekws_hip_resample_push")
+        counts = got[:B].tolist()
+        if capacity is None:
+            out = out[:, :max(counts + [0])]
+        return out, counts
+
+    def reset(self, streams=None) -> None:
+        ids = list(range(self.num_streams)) if streams is None else [int(s) for s in streams]
+        _capi.check(self._lib.wekws_hip_resample_reset(self._ptr, (ctypes.c_int32 * max(len(ids), 1))(*ids), len(ids)),
+                    "wekws_hip_resample_reset")
+
+    def counts(self, stream: int) -> Tuple[int, int, int, int]:
+        """(samples received, samples emitted, samples kept on the device, flushed) of a stream: host values, no device read."""
+        out = (ctypes.c_int64 * 4)()
+        _capi.check(self._lib.wekws_hip_resample_counts(self._ptr, int(stream), out), "wekws_hip_resample_counts")
         return tuple(int(v) for v in out)

@@ -9,7 +9,7 @@ from typing import Dict, List
 import torch
 
 from wekws_amd.ctc import StreamingKeywordSpotter
-from wekws_amd.frontend import StreamingFrontEnd
+from wekws_amd.frontend import StreamingFrontEnd, StreamingResampler
 from wekws_amd.model.kws_model import StreamCachePool
 
 
@@ -23,15 +23,22 @@ class BatchedKeyWordSpotter:
     ``model``: a ``wekws_amd`` KWSModel with a per-frame CTC head (``forward_softmax``).  The front-end settings are
     StreamingFrontEnd's (``num_bins``, ``window``, ``left``, ``right``, ``skip``, ``max_chunk``, ...), the others
     StreamingKeywordSpotter's (``min_frames``, ``max_frames``, ``interval_frames``, ``score_beam``, ``path_beam``,
-    ``prefix_capacity``); ``downsampling`` is ``skip``."""
+    ``prefix_capacity``); ``downsampling`` is ``skip``.  ``input_sample_rate`` (e.g. 48000): the chunks arrive at that rate and
+    pass a StreamingResampler (int16 out) to the front end's ``sample_rate`` first; ``max_chunk`` then counts INPUT samples."""
 
     _FE = ("num_bins", "window", "left", "right", "skip", "max_chunk", "sample_rate", "frame_length", "frame_shift")
 
     def __init__(self, model, keywords, threshold: float, num_streams: int, **settings):
         fe = {k: settings.pop(k) for k in self._FE if k in settings}
+        input_rate = settings.pop("input_sample_rate", None)
         self.model = model
         self.device = next(model.parameters()).device
         self.num_streams = int(num_streams)
+        self.resampler = None
+        if input_rate is not None:
+            self.resampler = StreamingResampler(self.num_streams, int(input_rate), int(fe.get("sample_rate", 16000)),
+                                                max_chunk=int(fe.get("max_chunk", 16000)), device=self.device)
+            fe["max_chunk"] = self.resampler.max_out(self.resampler.max_chunk)
         self.frontend = StreamingFrontEnd(self.num_streams, device=self.device, **fe)
         shift_ms = 1000.0 * self.frontend.cfg.fbank.frame_shift / self.frontend.cfg.fbank.sample_rate
         self.spotter = StreamingKeywordSpotter(self.num_streams, keywords, threshold, downsampling=self.frontend.skip,
@@ -49,7 +56,10 @@ class BatchedKeyWordSpotter:
         """One chunk per row; row b continues stream ``streams[b]`` (default 0 .. B-1).  Returns, per row,
         ``KeyWordSpotter.forward``'s dict -- ``{}`` for a row that was held or yielded no frame.  With ``return_probs`` also
         a list with each row's (frames, V) posteriors on the device (None for a row without frames) and the features the
-        model was given.  Three device calls: the front end's push, the model step over the pool, the decoder's step."""
+        model was given.  Three device calls: the front end's push, the model step over the pool, the decoder's step (a
+        fourth in front with ``input_sample_rate``: the resampler's push)."""
+        if self.resampler is not None:
+            chunks, samples = self.resampler.push(chunks, samples=samples, streams=streams)
         if torch.is_tensor(chunks):
             nmax = int(chunks.size(1)) if chunks.dim() == 2 else 0
         else:
@@ -76,7 +86,9 @@ class BatchedKeyWordSpotter:
 
     def reset_all(self, streams=None) -> None:
         """KeyWordSpotter.reset_all(): reset() plus the frame offset and last activation, the front end's leftover samples,
-        remembered frames and skip phase, and the streams' cache."""
+        remembered frames and skip phase, the resampler's kept samples, and the streams' cache."""
         self.spotter.reset_all(streams)
+        if self.resampler is not None:
+            self.resampler.reset(streams)
         self.frontend.reset(streams)
         self.pool.reset(streams)
