@@ -516,6 +516,46 @@ int wekws_hip_ctc_kws_read_beam(void* h, int id, void* out, void* stream);
 int wekws_hip_ctc_kws_status(void* h, int id, int32_t* status_out, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * Streaming threshold detector  --  the detection of a max-pooling model (one sigmoid posterior per frame and keyword), for many
+ * streams at once: the alarm scan of wekws/bin/compute_det.py:89-96 carried across chunks.  Per stream and keyword, each keyword
+ * on its own, with a = the frame's index since the stream's reset:
+ *   a frame FIRES iff a >= resume and (double)score >= thresholds[k] (a NaN never fires); then resume = a + window_shift
+ *   best / best_frame: the running maximum since reset and its first frame (NaN ignored); -inf / -1 before any frame
+ * For any split of a score sequence into chunks, empty ones included, the fired frames are those of one scan over the whole.
+ * Scores are compared as float32 widened to double, like wekws_hip_det_false_alarms (not its `_text` variant).
+ * ------------------------------------------------------------------------------------------*/
+typedef struct wekws_hip_threshold_kws_slot {
+  int32_t seen;        /* frames consumed since reset */
+  int32_t resume;      /* first frame the scan looks at again */
+  int32_t best_frame;  /* -1 before any frame */
+  float best;          /* -inf before any frame */
+} wekws_hip_threshold_kws_slot;
+
+/* thresholds: (num_keywords) HOST float64;  window_shift >= 1;  stream ids 0 .. max_streams - 1 */
+int wekws_hip_threshold_kws_create(int num_keywords, const double* thresholds, int window_shift, int max_streams, int device,
+                                   void** out);
+void wekws_hip_threshold_kws_destroy(void* h);
+/* Dcap = ceil(Tcap / window_shift): the hits a chunk of Tcap frames can hold per keyword. */
+int wekws_hip_threshold_kws_max_hits(void* h, int Tcap);
+/*
+ * probs       (B, Tcap, K) device float32; row b continues stream stream_ids[b] with its first frames[b] frames
+ * stream_ids, frames  (B) device int32, as wekws_hip_ctc_kws_step takes them (frames NULL = Tcap); distinct ids, any subset
+ * hit_frames  (B, K, Dcap) device int32: the fired frames of the chunk (indices since reset), ascending, -1 fill
+ * hit_scores  (B, K, Dcap) device float32: their scores, 0 fill
+ * best, best_frame  (B, K) device: the running maximum after the chunk
+ * status      (B) device int32, or NULL: 0, or why the row was SKIPPED with its stream untouched (1: frames[b] outside
+ *             0 .. Tcap; 2: id outside the pool; 3: the frame index would pass int32).  A skipped row's outputs hold the fills.
+ * One launch, no synchronise.  No input value leads to an access outside the buffers as sized above.
+ */
+int wekws_hip_threshold_kws_step(void* h, const float* probs, int B, int Tcap, const int32_t* stream_ids, const int32_t* frames,
+                                 int32_t* hit_frames, float* hit_scores, float* best, int32_t* best_frame, int32_t* status,
+                                 void* stream);
+/* The n streams in ids (device int32) start over: seen = resume = 0, no maximum.  Ids outside the pool are ignored. */
+int wekws_hip_threshold_kws_reset(void* h, const int32_t* ids, int n, void* stream);
+/* The state of (stream id, keyword) into *out (host); synchronises `stream`.  For tests. */
+int wekws_hip_threshold_kws_state(void* h, int id, int keyword, wekws_hip_threshold_kws_slot* out, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * Validation criterion  --  wekws/model/loss.py::criterion, forward only: what Executor.cv / Executor.test
  * (wekws/utils/executor.py:70-115) call after every forward, so that an evaluation loop moves two numbers per run to the
  * host instead of the (B, T, V) logits per batch.  Stateless; every pointer is a device pointer; no call synchronises or
@@ -606,6 +646,12 @@ typedef struct wekws_hip_stream_frontend_cfg {
 } wekws_hip_stream_frontend_cfg;
 
 int wekws_hip_stream_frontend_create(const wekws_hip_stream_frontend_cfg* cfg, void** out);
+/* The same front end delivering MFCC (the reference's MDTC recipes: wekws/dataset/processor.py:134-169): a fresh frame leaves the
+ * fbank kernel as num_ceps cepstra -- DCT-II and cepstral lifter as wekws_hip_dct_lifter applies them, bit for bit, by the wave
+ * that finished the frame; a push stays two launches -- and D below counts num_ceps where it says num_bins.  The handle is of the
+ * kind _create returns: _push, _reset, _counts, _max_frames and _destroy take it; _plan does not depend on the feature width.
+ * 0 < num_ceps <= cfg->fbank.num_bins <= 128 and cepstral_lifter >= 0 (0 disables it), else WEKWS_HIP_EINVAL. */
+int wekws_hip_stream_frontend_create_mfcc(const wekws_hip_stream_frontend_cfg* cfg, int num_ceps, float cepstral_lifter, void** out);
 void wekws_hip_stream_frontend_destroy(void* h);
 /* The plan of one push for one stream, on the host alone (no device, no handle): counts_in = {rem, fr (-1 = none yet), off},
  * plan_out = {status, held, nf, rem_out, pad_first, fr_in, rows_ctx, rows_out, fr_out, off_out}.  Returns EINVAL for a

@@ -48,6 +48,10 @@ class CtcKwsResult(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("status", "valid", "state", "keyword", "start", "end")] + [("score", C.c_double)]
 
 
+class ThresholdKwsSlot(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("seen", "resume", "best_frame")] + [("best", C.c_float)]
+
+
 # name -> (restype, argtypes); the CPU test-suite checks every symbol of the header is exported
 SIGNATURES = {
     "wekws_hip_last_error": (C.c_char_p, []),
@@ -110,6 +114,7 @@ SIGNATURES = {
     "wekws_hip_ctc_edit_distance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
     "wekws_hip_stream_frontend_create": (C.c_int, [C.POINTER(StreamFrontendCfg), C.POINTER(C.c_void_p)]),
+    "wekws_hip_stream_frontend_create_mfcc": (C.c_int, [C.POINTER(StreamFrontendCfg), C.c_int, C.c_float, C.POINTER(C.c_void_p)]),
     "wekws_hip_stream_frontend_destroy": (None, [C.c_void_p]),
     "wekws_hip_stream_frontend_plan": (C.c_int, [C.POINTER(StreamFrontendCfg), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]),
     "wekws_hip_stream_frontend_max_frames": (C.c_int, [C.c_void_p, C.c_int]),
@@ -127,6 +132,13 @@ SIGNATURES = {
     "wekws_hip_resample_max_out": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "wekws_hip_resample_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "wekws_hip_resample_counts": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
+    "wekws_hip_threshold_kws_create": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "wekws_hip_threshold_kws_destroy": (None, [C.c_void_p]),
+    "wekws_hip_threshold_kws_max_hits": (C.c_int, [C.c_void_p, C.c_int]),
+    "wekws_hip_threshold_kws_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "wekws_hip_threshold_kws_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "wekws_hip_threshold_kws_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(ThresholdKwsSlot), C.c_void_p]),
 }
 
 OPTIONS = {"w16": 0, "mdtc16": 1, "stream": 2, "mm": 3, "head_slices": 4, "g16": 5, "envelope": 6, "gru_pipe": 7}   # enum wekws_hip_option

@@ -6,6 +6,13 @@
 #include "topk.hip.h"
 #include "det.hip.h"
 
+namespace wekws {
+// for the streaming front end in MFCC mode (declared in stream_frontend.hip.h): the kernels of mfcc.hip.h live in this unit
+WEKWS_LOCAL int build_dct_lifter_matrix(float* D, int num_bins, int num_ceps, float lifter, hipStream_t stream) {
+  return launch_dct_lifter_matrix(D, num_bins, num_ceps, lifter, stream);
+}
+}  // namespace wekws
+
 extern "C" {
 
 // --------------------------------------------- context expansion + frame skip ---------------------------------------------

@@ -4,7 +4,7 @@
 namespace wekws {
 
 int launch_fbank_stream(const FbankParams& P, const StreamFeRow* rows, const int16_t* pcm, int B, int nmax, int Tv, int16_t* lo,
-                        float* dst, int resident, hipStream_t stream) {
+                        float* dst, int resident, const float* dct, int num_ceps, hipStream_t stream) {
   const int rounds = (P.nslots + 63) / 64;
   if (rounds < 1 || rounds > 3) return -4;
   const int64_t total = int64_t(B) * Tv;
@@ -12,9 +12,8 @@ int launch_fbank_stream(const FbankParams& P, const StreamFeRow* rows, const int
   if (resident > 0 && grid > resident) grid = resident;        // persistent waves: one resident round, like fbank_kernel
   const int pair_static = (P.frame_shift % 2 == 0) && (P.frame_length % 2 == 0) && (nmax % 2 == 0) &&
                           (reinterpret_cast<uintptr_t>(pcm) % 4 == 0) && (reinterpret_cast<uintptr_t>(lo) % 4 == 0);
-  auto kern = rounds == 1 ? fbank_stream_kernel<1> : rounds == 2 ? fbank_stream_kernel<2> : fbank_stream_kernel<3>;
-  hipLaunchKernelGGL(kern, dim3(unsigned(grid)), dim3(64 * kFbankWaves), fbank_stream_lds(), stream, P, rows, pcm, B, nmax, Tv, lo,
-                     dst, pair_static);
+  hipLaunchKernelGGL(fbank_stream_instance(rounds, dct != nullptr), dim3(unsigned(grid)), dim3(64 * kFbankWaves), fbank_stream_lds(),
+                     stream, P, rows, pcm, B, nmax, Tv, lo, dst, pair_static, dct, num_ceps);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -49,7 +48,9 @@ struct StreamFe {
   wekws::StreamFeCfg cfg{};
   wekws::FbankParams fp{};
   int max_streams = 0, max_chunk = 0;
-  int F = 0, W = 1, keep = 0;          // bins, window of the context, frames remembered per stream
+  int F = 0, W = 1, keep = 0;          // floats of a frame (bins, or cepstra in MFCC mode), window of the context, frames remembered per stream
+  int num_ceps = 0;                    // 0: log-mel rows
+  float* d_dct = nullptr;              // MFCC mode: the (num_bins x num_ceps) DCT matrix with the lifter folded in (mfcc.hip.h)
   int rem_cap = 0;                     // samples per leftover buffer (even)
   int Tws = 1;                         // frame slots per row of the fresh-frame workspace
   bool direct = false;                 // no context, no skip: fbank writes the caller's rows
@@ -123,15 +124,15 @@ void wekws_hip_stream_frontend_destroy(void* h) {
     if (o->d_rows[i]) (void)hipFree(o->d_rows[i]);
   }
   if (o->d_tables) (void)hipFree(o->d_tables);
+  if (o->d_dct) (void)hipFree(o->d_dct);
   if (o->lo) (void)hipFree(o->lo);
   if (o->frs) (void)hipFree(o->frs);
   if (o->ws) (void)hipFree(o->ws);
   delete o;
 }
 
-int wekws_hip_stream_frontend_create(const wekws_hip_stream_frontend_cfg* cfg, void** out) {
-  if (!cfg || !out) return fail(WEKWS_HIP_EINVAL, "NULL argument");
-  *out = nullptr;
+// num_ceps 0: log-mel rows (wekws_hip_stream_frontend_create)
+static int stream_frontend_create(const wekws_hip_stream_frontend_cfg* cfg, int num_ceps, float lifter, void** out) {
   wekws::StreamFeCfg c{};
   if (int rc = check_cfg(cfg, &c)) return rc;
   if (cfg->fbank.frame_length <= 64)
@@ -152,7 +153,8 @@ int wekws_hip_stream_frontend_create(const wekws_hip_stream_frontend_cfg* cfg, v
   o->device = cfg->device;
   o->cfg = c;
   o->max_streams = cfg->max_streams; o->max_chunk = cfg->max_chunk;
-  o->F = cfg->fbank.num_bins; o->W = keep + 1; o->keep = keep;
+  o->num_ceps = num_ceps;
+  o->F = num_ceps > 0 ? num_ceps : cfg->fbank.num_bins; o->W = keep + 1; o->keep = keep;
   o->rem_cap = int(cap); o->Tws = int(Tws);
   o->direct = keep == 0 && c.skip == 1;
   std::vector<float> tables;
@@ -170,6 +172,9 @@ int wekws_hip_stream_frontend_create(const wekws_hip_stream_frontend_cfg* cfg, v
   DeviceGuard g(cfg->device);
   hipError_t e = hipMalloc(&o->d_tables, tables.size() * sizeof(float));
   if (e == hipSuccess) e = hipMemcpy(o->d_tables, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess && num_ceps > 0) e = hipMalloc(&o->d_dct, size_t(cfg->fbank.num_bins) * num_ceps * sizeof(float));
+  if (e == hipSuccess && num_ceps > 0 && wekws::build_dct_lifter_matrix(o->d_dct, cfg->fbank.num_bins, num_ceps, lifter, nullptr))
+    e = hipGetLastError();
   if (e == hipSuccess) e = hipMalloc(&o->lo, n * 2 * size_t(cap) * sizeof(int16_t));
   if (e == hipSuccess) e = hipMemset(o->lo, 0, n * 2 * size_t(cap) * sizeof(int16_t));
   if (e == hipSuccess && keep > 0) e = hipMalloc(&o->frs, n * 2 * size_t(keep) * o->F * sizeof(float));
@@ -186,9 +191,24 @@ int wekws_hip_stream_frontend_create(const wekws_hip_stream_frontend_cfg* cfg, v
     return rc;
   }
   o->fp.tables = o->d_tables;
-  o->resident = wekws::fbank_stream_resident_groups(o->fp);
+  o->resident = wekws::fbank_stream_resident_groups(o->fp, num_ceps > 0);
   *out = o;
   return WEKWS_HIP_OK;
+}
+
+int wekws_hip_stream_frontend_create(const wekws_hip_stream_frontend_cfg* cfg, void** out) {
+  if (!cfg || !out) return fail(WEKWS_HIP_EINVAL, "NULL argument");
+  *out = nullptr;
+  return stream_frontend_create(cfg, 0, 0.f, out);
+}
+
+int wekws_hip_stream_frontend_create_mfcc(const wekws_hip_stream_frontend_cfg* cfg, int num_ceps, float cepstral_lifter, void** out) {
+  if (!cfg || !out) return fail(WEKWS_HIP_EINVAL, "NULL argument");
+  *out = nullptr;
+  if (num_ceps <= 0 || num_ceps > cfg->fbank.num_bins || cfg->fbank.num_bins > wekws::kFbankMaxBins || !(cepstral_lifter >= 0.f))
+    return fail(WEKWS_HIP_EINVAL, "stream_frontend: num_ceps=%d num_bins=%d lifter=%g (need 0 < num_ceps <= num_bins <= %d, lifter >= 0)",
+                num_ceps, cfg->fbank.num_bins, double(cepstral_lifter), wekws::kFbankMaxBins);
+  return stream_frontend_create(cfg, num_ceps, cepstral_lifter, out);
 }
 
 int wekws_hip_stream_frontend_max_frames(void* h, int nmax) {
@@ -262,7 +282,8 @@ int wekws_hip_stream_frontend_push(void* h, const int16_t* pcm, int B, int nmax,
   hipError_t e = hipMemcpyAsync(o->d_rows[slot], rows, size_t(B) * sizeof(wekws::StreamFeRow), hipMemcpyHostToDevice, s);
   if (e != hipSuccess) return hip_fail(e, "stream_frontend_push: plan upload");
   // ---- two launches; from here the streams' state moves
-  int rc = wekws::launch_fbank_stream(o->fp, o->d_rows[slot], pcm, B, nmax, Tv, o->lo, o->direct ? feats : o->ws, o->resident, s);
+  int rc = wekws::launch_fbank_stream(o->fp, o->d_rows[slot], pcm, B, nmax, Tv, o->lo, o->direct ? feats : o->ws, o->resident, o->d_dct,
+                                      o->num_ceps, s);
   if (!rc && !o->direct && max_items > 0)
     rc = wekws::launch_splice_stream(o->d_rows[slot], o->ws, o->frs, feats, B, max_items, o->F, o->cfg.left, o->W, o->cfg.skip, s);
   e = hipEventRecord(o->ev[slot], s);

@@ -14,6 +14,12 @@
 //                         OTHER buffer: other waves still read the old one.
 //                         Persistent waves walk the (row, frame slot) grid of B x Tv, Tv the call's largest frame count; a slot
 //                         past its row's count costs a plan read, no transform.
+//                         MFCC mode (template parameter; the log-mel instantiation is the code above and nothing else): the row
+//                         sink is the wave's own LDS strip, and the wave that finished the frame applies DCT-II and lifter before
+//                         the store -- lane c (and c + 64) runs dct_lifter_kernel's chain for cepstrum c, so a streamed row is
+//                         dct_lifter(Fbank(whole))[k] bit for bit.  The (num_bins x num_ceps) matrix is read from GLOBAL memory
+//                         (25.6 KB at 80 x 80, consecutive lanes on consecutive words: cache hits); in LDS it would add up to
+//                         64 KB per workgroup and cost fbank_stream_kernel<2> its four workgroups per CU.
 //   splice_stream_kernel  context and / or skip as a gather over the remembered frames and the fresh ones; writes the caller's
 //                         rows and the frames to remember (the stream's other buffer again).  Pure data movement.
 #pragma once
@@ -39,10 +45,24 @@ struct StreamFeRow {        // what the kernels know about one row of a push (16
 
 constexpr int kStreamFeRing = 4;   // plan tables in flight (stream_frontend.hip)
 
-template <int ROUNDS>
+// U (even) steps of dct_lifter_kernel's chain (mfcc.hip.h), from an even row on: s0 takes the even rows, s1 the odd ones, in order.
+// x: the log-mel values of the rows (LDS), d: the matrix column of this lane's cepstrum from the same row on (global, stride NC).
+template <int U>
+__device__ __forceinline__ void dct_rows(const float* x, const float* __restrict__ d, int NC, float& s0, float& s1) {
+  float dv[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) dv[u] = d[u * NC];
+#pragma unroll
+  for (int u = 0; u < U; u += 2) {
+    s0 = fmaf(x[u], dv[u], s0);
+    s1 = fmaf(x[u + 1], dv[u + 1], s1);
+  }
+}
+
+template <int ROUNDS, bool MFCC>
 __global__ __launch_bounds__(64 * kFbankWaves, ROUNDS == 2 ? 4 : 1) void fbank_stream_kernel(
     const FbankParams P, const StreamFeRow* __restrict__ rows, const int16_t* __restrict__ pcm, int B, int nmax, int Tv,
-    int16_t* __restrict__ lo, float* __restrict__ dst, int pair_static) {
+    int16_t* __restrict__ lo, float* __restrict__ dst, int pair_static, const float* __restrict__ dct, int NC) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)), lane = threadIdx.x & 63;
   float* const strip = lds + wave * kFbankStrip;
@@ -119,9 +139,30 @@ __global__ __launch_bounds__(64 * kFbankWaves, ROUNDS == 2 ? 4 : 1) void fbank_s
       const int64_t slot = int64_t(rows[ub].fb_base) + ufr;
       fbank_frames<ROUNDS, 1>(K, strip, lane, inv_fl, vn, [&]() __attribute__((always_inline)) { fetch(nb, nfr); },
                               [&](int, float*& row) __attribute__((always_inline)) {
-                                row = dst + slot * P.num_bins;
+                                if constexpr (MFCC) row = strip;             // (the power bins are spent: the strip's head is free)
+                                else row = dst + slot * P.num_bins;
                                 return true;
                               });
+      if constexpr (MFCC) {
+        // fbank_frames ends in a wave_sync: the strip holds the frame's num_bins log-mel values.  Cepstrum c is the chain of
+        // dct_lifter_kernel (mfcc.hip.h) on the same matrix: s0 over even n, s1 over odd n, s0 + s1.  One cepstrum per pass -- two
+        // cepstra in one loop would invite the compiler to pair their chains across the broadcast x (pk_safe.hip.h).
+        const int N = P.num_bins;
+        float* const out = dst + slot * NC;
+        for (int c = lane; c < NC; c += 64) {
+          const float* __restrict__ d = dct + c;
+          float s0 = 0.f, s1 = 0.f;
+          int n = 0;
+          // the same chain in blocks of 8 rows whose matrix loads are all issued before the first is used: one load per step,
+          // waited for at once, left the wave idle for a cache round trip per pair of rows (16 at a time cost registers: spills
+          // in the 128-register instance, a wave per SIMD less in the others)
+          for (; n + 8 <= N; n += 8) dct_rows<8>(strip + n, d + n * NC, NC, s0, s1);
+          for (; n + 1 < N; n += 2) dct_rows<2>(strip + n, d + n * NC, NC, s0, s1);
+          if (n < N) s0 = fmaf(strip[n], d[n * NC], s0);
+          out[c] = s0 + s1;
+        }
+        wave_sync();                                            // every lane has read the row: the strip is free for the next frame
+      }
     } else {
       fetch(nb, nfr);
     }
@@ -155,10 +196,17 @@ __global__ __launch_bounds__(256) void splice_stream_kernel(const StreamFeRow* _
 
 inline size_t fbank_stream_lds() { return size_t(kFbankWaves * kFbankStrip) * sizeof(float); }
 
-inline int fbank_stream_resident_groups(const FbankParams& P) {
+using FbankStreamKernel = void (*)(const FbankParams, const StreamFeRow*, const int16_t*, int, int, int, int16_t*, float*, int,
+                                   const float*, int);
+inline FbankStreamKernel fbank_stream_instance(int rounds, bool mfcc) {
+  if (mfcc) return rounds == 1 ? fbank_stream_kernel<1, true> : rounds == 2 ? fbank_stream_kernel<2, true> : fbank_stream_kernel<3, true>;
+  return rounds == 1 ? fbank_stream_kernel<1, false> : rounds == 2 ? fbank_stream_kernel<2, false> : fbank_stream_kernel<3, false>;
+}
+
+inline int fbank_stream_resident_groups(const FbankParams& P, bool mfcc) {
   const int rounds = (P.nslots + 63) / 64;
   if (rounds < 1 || rounds > 3) return 0;
-  auto kern = rounds == 1 ? fbank_stream_kernel<1> : rounds == 2 ? fbank_stream_kernel<2> : fbank_stream_kernel<3>;
+  auto kern = fbank_stream_instance(rounds, mfcc);
   int per_cu = 0, dev = 0;
   hipDeviceProp_t prop;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * kFbankWaves, fbank_stream_lds()) == hipSuccess &&
@@ -167,8 +215,11 @@ inline int fbank_stream_resident_groups(const FbankParams& P) {
   return 256 * 4;
 }
 
+// dct: NULL for log-mel rows of P.num_bins floats, else the (num_bins x num_ceps) matrix of launch_dct_lifter_matrix: rows of num_ceps
 int launch_fbank_stream(const FbankParams& P, const StreamFeRow* rows, const int16_t* pcm, int B, int nmax, int Tv, int16_t* lo,
-                        float* dst, int resident, hipStream_t stream);
+                        float* dst, int resident, const float* dct, int num_ceps, hipStream_t stream);
+// the matrix of mfcc.hip.h into D (num_bins x num_ceps floats on the device); defined in frame_ops.hip, the unit that emits that header
+__attribute__((visibility("hidden"))) int build_dct_lifter_matrix(float* D, int num_bins, int num_ceps, float lifter, hipStream_t stream);
 int launch_splice_stream(const StreamFeRow* rows, const float* fresh, float* frs, float* out, int B, int max_items_f, int F,
                          int left, int W, int skip, hipStream_t stream);
 

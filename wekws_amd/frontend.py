@@ -153,11 +153,16 @@ class StreamingFrontEnd:
         feats, frames = fe.push(pcm)            # pcm (B, nmax) int16 on the device: row b continues stream b
 
     Context is off (left = right = 0) or ``left == right >= 1``; anything else is refused (the streaming reference is
-    coherent only there).  int16 input only, as the reference receives it."""
+    coherent only there).  int16 input only, as the reference receives it.
+
+    ``num_ceps``: None for log-mel rows; else every frame leaves the fbank kernel as ``num_ceps`` cepstra (``Mfcc``'s DCT and
+    ``cepstral_lifter``, applied by the wave that finished the frame: still two launches), bit for bit
+    ``dct_lifter(Fbank(...)(whole signal), num_ceps, cepstral_lifter)``; ``feat_dim = num_ceps * (left + right + 1)``.  The
+    reference's MDTC recipes: ``num_bins=80, window="povey", num_ceps=80``."""
 
     def __init__(self, num_streams: int, num_bins: int = 40, window: str = "hamming", left: int = 0, right: int = 0,
                  skip: int = 1, max_chunk: int = 16000, sample_rate: int = 16000, frame_length: Optional[int] = None,
-                 frame_shift: Optional[int] = None, device="cuda"):
+                 frame_shift: Optional[int] = None, device="cuda", num_ceps: Optional[int] = None, cepstral_lifter: float = 22.0):
         if window not in WINDOWS:
             raise ValueError(f"window must be one of {sorted(WINDOWS)}")
         self.device = torch.device(device)
@@ -165,7 +170,10 @@ class StreamingFrontEnd:
             raise RuntimeError("wekws_amd.frontend.StreamingFrontEnd runs on the MI355X HIP path only (no CPU fallback)")
         self.num_streams, self.num_bins, self.max_chunk = int(num_streams), int(num_bins), int(max_chunk)
         self.left, self.right, self.skip = int(left), int(right), int(skip)
-        self.feat_dim = self.num_bins * (self.left + self.right + 1)
+        self.num_ceps = None if num_ceps is None else int(num_ceps)
+        self.cepstral_lifter = float(cepstral_lifter)
+        self.frame_dim = self.num_bins if self.num_ceps is None else self.num_ceps     # floats of one frame
+        self.feat_dim = self.frame_dim * (self.left + self.right + 1)
         cfg = _capi.StreamFrontendCfg()
         cfg.fbank.num_bins, cfg.fbank.sample_rate = self.num_bins, int(sample_rate)
         cfg.fbank.frame_length = int(frame_length) if frame_length is not None else sample_rate // 1000 * 25
@@ -178,8 +186,13 @@ class StreamingFrontEnd:
         self.cfg = cfg
         self._lib = _capi.load()
         self._ptr = ctypes.c_void_p()
-        _capi.check(self._lib.wekws_hip_stream_frontend_create(ctypes.byref(cfg), ctypes.byref(self._ptr)),
-                    "wekws_hip_stream_frontend_create")
+        if self.num_ceps is None:
+            _capi.check(self._lib.wekws_hip_stream_frontend_create(ctypes.byref(cfg), ctypes.byref(self._ptr)),
+                        "wekws_hip_stream_frontend_create")
+        else:
+            _capi.check(self._lib.wekws_hip_stream_frontend_create_mfcc(ctypes.byref(cfg), self.num_ceps, self.cepstral_lifter,
+                                                                        ctypes.byref(self._ptr)),
+                        "wekws_hip_stream_frontend_create_mfcc")
 
     def __del__(self):
         try:
