@@ -514,6 +514,28 @@ size_t wekws_hip_ctc_kws_beam_bytes(void* h, int cap);
 int wekws_hip_ctc_kws_read_beam(void* h, int id, void* out, void* stream);
 /* The stream's sticky status (0 or WEKWS_HIP_E*) into *status_out; synchronises `stream`. */
 int wekws_hip_ctc_kws_status(void* h, int id, int32_t* status_out, void* stream);
+/*
+ * Keyword sets  --  KeyWordSpotter.set_keywords (wekws/bin/stream_kws_ctc.py:304-333) per STREAM instead of per object.  A set
+ * is a keyword list, a first-beam token set (or none) and a threshold; the beams, min / max / interval frames, downsampling
+ * and prefix capacity stay the handle's.  Set 0 is the descriptor's own and every stream starts in it: a program that never
+ * registers a set sees no difference.  A result record's `keyword` is the index inside the stream's own set.
+ * The calls are ordered against steps by `stream`, as reset is; a refused call (WEKWS_HIP_EINVAL: an unknown set, a bad or
+ * repeated stream id, an empty keyword, a token outside the vocabulary, dropping a set in use) changes nothing and does no
+ * device work.  Registering or dropping a set leaves every other stream's state and results alone.
+ */
+/* Register a keyword set on the handle; *set_out receives its id (>= 1; 0 is the descriptor's own set).
+   Arguments as the descriptor's: token_set NULL = no first-beam set.  All arrays on the host. */
+int wekws_hip_ctc_kws_add_set(void* h, const int32_t* keyword_tokens, const int32_t* keyword_offsets, int num_keywords,
+                              const int32_t* token_set, int token_set_len, double threshold, int32_t* set_out, void* stream);
+/* Drop a set no stream is assigned to (EINVAL otherwise, and for set 0); its id is reused, lowest first. */
+int wekws_hip_ctc_kws_drop_set(void* h, int32_t set, void* stream);
+/* Streams ids[i] (host, distinct) now use sets[i] (host) and are reset as by reset_all. */
+int wekws_hip_ctc_kws_assign(void* h, const int32_t* ids, const int32_t* sets, int n, void* stream);
+/* The set of stream `id` (host mirror, no device work); -1 for a bad id. */
+int wekws_hip_ctc_kws_stream_set(void* h, int id);
+/* wekws_hip_ctc_kws_search with a set per row (sets: host, B entries; NULL = set 0 for every row). */
+int wekws_hip_ctc_kws_search_sets(void* h, const float* probs, int B, int T, const int32_t* lengths, const int32_t* sets,
+                                  wekws_hip_ctc_kws_result* results, void* beams, void* stream);
 
 /* -------------------------------------------------------------------------------------------
  * Streaming threshold detector  --  the detection of a max-pooling model (one sigmoid posterior per frame and keyword), for many

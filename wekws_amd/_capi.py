@@ -104,6 +104,13 @@ SIGNATURES = {
     "wekws_hip_ctc_kws_beam_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "wekws_hip_ctc_kws_read_beam": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "wekws_hip_ctc_kws_status": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p]),
+    "wekws_hip_ctc_kws_add_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double,
+                                            C.POINTER(C.c_int32), C.c_void_p]),
+    "wekws_hip_ctc_kws_drop_set": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "wekws_hip_ctc_kws_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "wekws_hip_ctc_kws_stream_set": (C.c_int, [C.c_void_p, C.c_int]),
+    "wekws_hip_ctc_kws_search_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
     "wekws_hip_criterion_max_pooling": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "wekws_hip_criterion_ce": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -18,9 +18,16 @@
 // synchronisation, no spin loops.  A stream's state is only ever touched by its own one-wave workgroup, so the
 // workgroup-scope fences of __syncthreads() order the lanes' global writes and reads (the CU's L1 serves the whole
 // workgroup); no agent-scope fence (an L2 write-back) is needed per frame.
+//
+// Keyword sets (ctc_kws_sets.h).  The keywords, the first-beam token set and the threshold belong to a SET; every slot has a
+// set id.  The wave reads its slot's id once -- it is wave-uniform --, takes the set's record and from it the mask pointer,
+// the keyword block and the threshold.  The tables are written by copies and by the assign kernel only, both ordered
+// against the steps by the stream; a table that grew is a new allocation, so a launch keeps reading the one it was given.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "ctc_kws_sets.h"
 
 #pragma clang fp contract(off)   // the reference evaluates `n_pb + pb * ps + pnb * ps` with one rounding per operation
 
@@ -49,13 +56,32 @@ struct CtcParams {
   int V, K, PB, cap, pool_cap, n_slots;
   size_t slot_bytes;
   char* slots;
-  const uint32_t* tokset;   // bitmask over the vocabulary, nullptr = no token set
-  const int32_t* kw_tok;
-  const int32_t* kw_off;
-  int n_kw;
-  double threshold;
+  const CtcSetRec* sets;        // one record per set id
+  const int32_t* kw_arena;      // the sets' keyword blocks
+  const uint32_t* mask_arena;   // the sets' token masks
+  const int32_t* slot_set;      // the set id of every slot (offline: of every row); nullptr = set 0 for all
+  int n_sets;                   // ids below this have a record
   int min_frames, max_frames, interval_frames, ds;
 };
+
+// what a wave takes from its set's record
+struct CtcSet {
+  const uint32_t* tokset;   // bitmask over the vocabulary, nullptr = no token set
+  const int32_t* kw_off;    // n_kw + 1 offsets into kw_tok
+  const int32_t* kw_tok;
+  int n_kw;
+  double threshold;
+};
+__device__ inline CtcSet ctc_set(const CtcParams& p, int set) {
+  const CtcSetRec r = p.sets[set];
+  CtcSet o;
+  o.tokset = r.mask_word >= 0 ? p.mask_arena + r.mask_word : nullptr;
+  o.kw_off = p.kw_arena + r.kw_base;
+  o.kw_tok = o.kw_off + r.n_kw + 1;
+  o.n_kw = r.n_kw;
+  o.threshold = r.threshold;
+  return o;
+}
 
 struct CtcSlot {
   CtcSlotHead* h;
@@ -120,23 +146,24 @@ struct CtcLds {
 };
 
 // The keyword detection of execute_detection / score_ctc over the beam of parity `par`: hypotheses in beam order,
-// keywords in insertion order, first hit wins; is_sublist's range(len(main) - len(check)) quirk included.
-// Every lane returns the keyword index (-1: none); lane 0 also updates *hit_score, *start and *end.
-__device__ inline int ctc_detect(const CtcParams& p, const CtcSlot& S, int par, int nb, double* hit_score, int* start, int* end) {
+// the set's keywords in insertion order, first hit wins; is_sublist's range(len(main) - len(check)) quirk included.
+// Every lane returns the keyword's index inside the set (-1: none); lane 0 also updates *hit_score, *start and *end.
+__device__ inline int ctc_detect(const CtcParams& p, const CtcSet& ks, const CtcSlot& S, int par, int nb, double* hit_score, int* start,
+                                 int* end) {
   const int lane = threadIdx.x;
   for (int hy = 0; hy < nb; ++hy) {
     const int L = S.h->len[par][hy];
     const int32_t* tk = S.tok + (size_t(par) * p.PB + hy) * p.cap;
     const int32_t* nd = S.node + (size_t(par) * p.PB + hy) * p.cap;
-    for (int k = 0; k < p.n_kw; ++k) {
-      const int o0 = p.kw_off[k], kl = p.kw_off[k + 1] - o0;
+    for (int k = 0; k < ks.n_kw; ++k) {
+      const int o0 = ks.kw_off[k], kl = ks.kw_off[k + 1] - o0;
       if (L < kl) continue;
       const int n_off = (L == kl) ? 1 : L - kl;
       int off = -1;
       for (int b0 = 0; b0 < n_off && off < 0; b0 += 64) {
         const int i = b0 + lane;
         bool ok = i < n_off;
-        for (int m = 0; ok && m < kl; ++m) ok = tk[i + m] == p.kw_tok[o0 + m];
+        for (int m = 0; ok && m < kl; ++m) ok = tk[i + m] == ks.kw_tok[o0 + m];
         const uint64_t bal = __ballot(ok);
         if (bal) off = b0 + __ffsll((unsigned long long)bal) - 1;
       }
@@ -190,9 +217,10 @@ __device__ inline void ctc_compact(const CtcParams& p, const CtcSlot& S, int par
   __syncthreads();
 }
 
-// One frame of the search on the slot's current beam.  Returns 0, or a status (the beam is then left as it was).
+// One frame of the search on the slot's current beam; `tokset`: the first-beam token set of the slot's keyword set, or
+// nullptr.  Returns 0, or a status (the beam is then left as it was).
 template <int KMAX, int PBMAX>
-__device__ int ctc_frame(const CtcParams& p, const CtcSlot& S, CtcLds<KMAX, PBMAX>& L, const float* row, int t) {
+__device__ int ctc_frame(const CtcParams& p, const uint32_t* tokset, const CtcSlot& S, CtcLds<KMAX, PBMAX>& L, const float* row, int t) {
   const int lane = threadIdx.x;
   const int K = p.K, PB = p.PB;
   // ---- first beam: the lane's k best over a strided slice, then k rounds of a wave-wide arg-max
@@ -240,7 +268,7 @@ __device__ int ctc_frame(const CtcParams& p, const CtcSlot& S, CtcLds<KMAX, PBMA
     if (i != 0x7fffffff) {
       const float f = row[i];
       const double ps = double(f);
-      const bool in_set = !p.tokset || ((p.tokset[i >> 5] >> (i & 31)) & 1u);
+      const bool in_set = !tokset || ((tokset[i >> 5] >> (i & 31)) & 1u);
       if (ps > 0.05 && in_set) {     // NaN fails the comparison: dropped after taking its place
         if (lane == 0) { L.ftok[nf] = i; L.fps[nf] = ps; }
         ++nf;
@@ -434,7 +462,8 @@ __global__ __launch_bounds__(64) void ctc_kws_read_beam_kernel(CtcParams p, int 
 }
 
 // mode 0 (streaming step): row b continues stream ids[b] with counts[b] frames.  mode 1 (offline search): row b is a
-// fresh utterance of counts[b] frames in slot b; `beams` (optional) receives its final beam.
+// fresh utterance of counts[b] frames in slot b; `beams` (optional) receives its final beam.  Either way the slot's
+// keyword set is p.slot_set[slot].
 template <int KMAX, int PBMAX>
 __global__ __launch_bounds__(64) void ctc_kws_kernel(CtcParams p, int mode, const float* __restrict__ probs, int T,
                                                      const int32_t* __restrict__ ids, const int32_t* __restrict__ counts,
@@ -448,6 +477,12 @@ __global__ __launch_bounds__(64) void ctc_kws_kernel(CtcParams p, int mode, cons
     if (lane == 0) { res.status = kCtcEInval; results[b] = res; }
     return;
   }
+  const int set = p.slot_set ? __builtin_amdgcn_readfirstlane(p.slot_set[sid]) : 0;
+  if (set < 0 || set >= p.n_sets) {
+    if (lane == 0) { res.status = kCtcEInval; results[b] = res; }
+    return;
+  }
+  const CtcSet ks = ctc_set(p, set);
   const CtcSlot S = ctc_slot(p, sid);
   CtcSlotHead* H = S.h;
   if (mode == 1) {
@@ -465,13 +500,13 @@ __global__ __launch_bounds__(64) void ctc_kws_kernel(CtcParams p, int mode, cons
   const float* x = probs + size_t(b) * T * p.V;
   if (mode == 1) {
     for (int t = 0; t < n; ++t) {
-      const int st = ctc_frame<KMAX, PBMAX>(p, S, L, x + size_t(t) * p.V, t);
+      const int st = ctc_frame<KMAX, PBMAX>(p, ks.tokset, S, L, x + size_t(t) * p.V, t);
       if (st) { if (lane == 0) H->status = st; break; }
     }
     __syncthreads();
     double hs = 1.0;
     int start = 0, end = 0;
-    const int kw = H->status ? -1 : ctc_detect(p, S, H->parity, H->nb, &hs, &start, &end);
+    const int kw = H->status ? -1 : ctc_detect(p, ks, S, H->parity, H->nb, &hs, &start, &end);
     if (lane == 0) {
       res.status = H->status; res.state = kw >= 0; res.keyword = kw; res.start = start; res.end = end; res.score = hs;
       results[b] = res;
@@ -483,17 +518,17 @@ __global__ __launch_bounds__(64) void ctc_kws_kernel(CtcParams p, int mode, cons
   int st = 0;
   for (int t = 0; t < n; ++t) {
     const int at = t * p.ds + H->total_frames;
-    st = ctc_frame<KMAX, PBMAX>(p, S, L, x + size_t(t) * p.V, at);
+    st = ctc_frame<KMAX, PBMAX>(p, ks.tokset, S, L, x + size_t(t) * p.V, at);
     if (st) break;
     double hs = H->hit_score;
     int start = 0, end = 0;
-    const int kw = ctc_detect(p, S, H->parity, H->nb, &hs, &start, &end);
+    const int kw = ctc_detect(p, ks, S, H->parity, H->nb, &hs, &start, &end);
     int act = 0;
     if (lane == 0) {
       if (kw >= 0) {
         H->hit_score = hs;
         const int dur = end - start;
-        if (hs >= p.threshold && p.min_frames <= dur && dur <= p.max_frames &&
+        if (hs >= ks.threshold && p.min_frames <= dur && dur <= p.max_frames &&
             (H->last_active_pos == -1 || end - H->last_active_pos >= p.interval_frames)) {
           act = 1;
           H->last_active_pos = end;
@@ -533,6 +568,18 @@ __global__ void ctc_kws_reset_kernel(CtcParams p, const int32_t* ids, int n, int
   if (all) { h->total_frames = 0; h->last_active_pos = -1; }
 }
 
+// streams ids[i] take the keyword sets sets[i] and start over as by reset_all; the host has checked ids and sets
+__global__ void ctc_kws_assign_kernel(CtcParams p, int32_t* slot_set, const int32_t* ids, const int32_t* sets, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int s = ids[i];
+  if (s < 0 || s >= p.n_slots) return;
+  slot_set[s] = sets[i];
+  CtcSlotHead* h = ctc_slot(p, s).h;
+  ctc_reset_head(h);
+  h->total_frames = 0; h->last_active_pos = -1;
+}
+
 __global__ void ctc_kws_init_kernel(CtcParams p) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= p.n_slots) return;
@@ -545,6 +592,7 @@ __global__ void ctc_kws_init_kernel(CtcParams p) {
 int launch_ctc_kws(const CtcParams& p, int mode, const float* probs, int B, int T, const int32_t* ids,
                    const int32_t* counts, CtcResult* results, char* beams, size_t beam_stride, hipStream_t stream);
 int launch_ctc_kws_reset(const CtcParams& p, const int32_t* ids, int n, int all, hipStream_t stream);
+int launch_ctc_kws_assign(const CtcParams& p, int32_t* slot_set, const int32_t* ids, const int32_t* sets, int n, hipStream_t stream);
 int launch_ctc_kws_init(const CtcParams& p, hipStream_t stream);
 int launch_ctc_kws_read_beam(const CtcParams& p, int id, char* out, hipStream_t stream);
 

@@ -2,7 +2,7 @@
 // libwekws_hip.so: the sinks are empty, the unit exports nothing and holds no kernel.  libwekws_hip_hooks.so (make hooks: this unit
 // compiled with -DWEKWS_TEST_HOOKS, every other object shared with the product library): the sinks record, and the unit carries the test
 // hooks: the route trace of a forward, the routing functions of route.h and the blob layout of blob_layout.h without a device, the GRU
-// epoch, a CU hog, the fbank's plan and table, the row softmax on chosen logits, the resampler's taps and plan.  Not part of the ABI in include/wekws_hip.h.
+// epoch, a CU hog, the fbank's plan and table, the row softmax on chosen logits, the resampler's taps and plan, the CTC decoder's keyword-set table.  Not part of the ABI in include/wekws_hip.h.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -10,6 +10,7 @@
 #include "model.h"
 #include "ds256_stream.hip.h"
 #include "mdtc64_stream.hip.h"
+#include "ctc_kws_sets.h"
 #include "resample.hip.h"
 
 #ifndef WEKWS_TEST_HOOKS
@@ -413,5 +414,67 @@ extern "C" int wekws_hip_debug_resample_round_taps_f16(wekws_hip_resample* r) {
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "resample taps: %s", hipGetErrorString(e));
   return WEKWS_HIP_OK;
+}
+
+// --------------------------------------------- CTC keyword sets ---------------------------------------------
+// A script of set operations on the table of ctc_kws_sets.h, WITHOUT a device: the table wekws_hip_ctc_kws_add_set / _drop_set /
+// _assign decide every refusal and every id with.  vocab, n_streams: the handle's.  ops: n_ints int32, one operation after the other:
+//   0, n_kw, n_tok, offsets[n_kw + 1], tokens[n_tok], ts_len (-1 - L: a NULL token set with token_set_len = L, so -1: none),
+//      token_set[max(ts_len, 0)], threshold (two halves of the double, low first)
+//                                                                  add: outcome = the set's id (the first add makes set 0), or -1
+//   1, set                                                         drop: outcome 0, or -1
+//   2, n, ids[n], sets[n]                                          assign: outcome 0, or -1
+// outcomes: one per operation, at most max_ops.  image: the table afterwards (CtcSetTable::image), *image_len its length in ints; it is
+// written only if it fits image_cap.  Returns the number of operations run, or WEKWS_HIP_EINVAL for a script that does not parse.
+extern "C" int wekws_hip_debug_ctc_kws_sets(int vocab, int n_streams, const int32_t* ops, int64_t n_ints, int32_t* outcomes, int max_ops,
+                                            int32_t* image, int64_t image_cap, int64_t* image_len) {
+  if (vocab < 1 || n_streams < 0 || n_ints < 0 || (n_ints > 0 && !ops) || max_ops < 0 || (max_ops > 0 && !outcomes) || !image_len)
+    return WEKWS_HIP_EINVAL;
+  wekws::CtcSetTable tab;
+  tab.init(vocab, n_streams);
+  char why[256];
+  int n = 0;
+  int64_t i = 0;
+  auto room = [&](int64_t k) { return k >= 0 && k <= n_ints - i; };
+  while (i < n_ints) {
+    if (n >= max_ops) return WEKWS_HIP_EINVAL;
+    const int kind = ops[i++];
+    if (kind == 0) {
+      if (!room(2)) return WEKWS_HIP_EINVAL;
+      const int n_kw = ops[i], n_tok = ops[i + 1];
+      i += 2;
+      if (n_kw < 0 || n_tok < 0 || !room(int64_t(n_kw) + 1 + n_tok + 1)) return WEKWS_HIP_EINVAL;
+      const int32_t* offs = ops + i;
+      const int32_t* toks = offs + n_kw + 1;
+      // the table reads tokens up to the last offset: a script whose offsets run past its tokens is refused here, not there
+      for (int k = 0; k <= n_kw; ++k)
+        if (offs[k] > n_tok) return WEKWS_HIP_EINVAL;
+      i += int64_t(n_kw) + 1 + n_tok;
+      const int ts_len = ops[i++];
+      if (!room(int64_t(ts_len < 0 ? 0 : ts_len) + 2)) return WEKWS_HIP_EINVAL;
+      static const int32_t none = 0;
+      const int32_t* ts = ts_len < 0 ? nullptr : (ts_len > 0 ? ops + i : &none);
+      i += ts_len < 0 ? 0 : ts_len;
+      double thr;
+      std::memcpy(&thr, ops + i, 8);
+      i += 2;
+      outcomes[n++] = tab.add(wekws::CtcSetSpec{toks, offs, n_kw, ts, ts_len < 0 ? -1 - ts_len : ts_len, thr}, why, sizeof why);
+    } else if (kind == 1) {
+      if (!room(1)) return WEKWS_HIP_EINVAL;
+      outcomes[n++] = tab.drop(ops[i++], why, sizeof why);
+    } else if (kind == 2) {
+      if (!room(1)) return WEKWS_HIP_EINVAL;
+      const int cnt = ops[i++];
+      if (cnt < 0 || !room(2 * int64_t(cnt))) return WEKWS_HIP_EINVAL;
+      outcomes[n++] = tab.assign(ops + i, ops + i + cnt, cnt, why, sizeof why);
+      i += 2 * int64_t(cnt);
+    } else {
+      return WEKWS_HIP_EINVAL;
+    }
+  }
+  const std::vector<int32_t> img = tab.image();
+  *image_len = int64_t(img.size());
+  if (image && image_cap >= int64_t(img.size()) && !img.empty()) std::memcpy(image, img.data(), img.size() * 4);
+  return n;
 }
 #endif  // WEKWS_TEST_HOOKS

@@ -6,7 +6,10 @@
   of loss.py:206-312, score_ctc's detection loop and the streaming ``KeyWordSpotter`` of wekws/bin/stream_kws_ctc.py --
   on the device for a batch of utterances or thousands of streams (``wekws_hip_ctc_kws_*``, csrc/ctc_kws.hip.h), bit-identical
   to the reference given the same float32 posteriors.  The host receives one small result record per stream and call.
-  Intended use: ``probs, cache = model.forward_softmax(chunk, cache); res = spotter.step(probs)``."""
+  Intended use: ``probs, cache = model.forward_softmax(chunk, cache); res = spotter.step(probs)``.
+- keyword sets: every stream of a ``StreamingKeywordSpotter`` (``add_keywords`` / ``assign`` / ``drop_keywords``) and every
+  row of ``keyword_search_sets`` may have its own keywords, token set and threshold (``wekws_hip_ctc_kws_add_set`` / ``_assign``
+  / ``_drop_set`` / ``_search_sets``, csrc/ctc_kws_sets.h) -- ``KeyWordSpotter.set_keywords`` per stream instead of per object."""
 from __future__ import annotations
 
 import ctypes
@@ -96,6 +99,28 @@ class _Handle:
     def beam_bytes(self, cap: int) -> int:
         return int(self.lib.wekws_hip_ctc_kws_beam_bytes(self.h, int(cap)))
 
+    def add_set(self, keywords: Sequence[Tuple[int, ...]], tokenset, threshold: float, stream: int) -> int:
+        """Register a keyword set (wekws_hip_ctc_kws_add_set); tokenset None = no first-beam set.  Returns its id."""
+        flat = np.array([t for k in keywords for t in k] or [0], np.int32)
+        offs = np.array([0] + list(np.cumsum([len(k) for k in keywords])), np.int32)
+        ts = None if tokenset is None else np.array(sorted(int(x) for x in tokenset) or [0], np.int32)
+        out = ctypes.c_int32(-1)
+        _capi.check(self.lib.wekws_hip_ctc_kws_add_set(self.h, flat.ctypes.data, offs.ctypes.data, len(keywords),
+                                                       None if ts is None else ts.ctypes.data,
+                                                       0 if tokenset is None else len(tokenset), float(threshold),
+                                                       ctypes.byref(out), ctypes.c_void_p(stream)),
+                    "wekws_hip_ctc_kws_add_set")
+        return int(out.value)
+
+    def drop_set(self, set_id: int, stream: int) -> None:
+        _capi.check(self.lib.wekws_hip_ctc_kws_drop_set(self.h, int(set_id), ctypes.c_void_p(stream)),
+                    "wekws_hip_ctc_kws_drop_set")
+
+    def assign(self, ids: Sequence[int], sets: Sequence[int], stream: int) -> None:
+        a, b = np.array(list(ids), np.int32), np.array(list(sets), np.int32)
+        _capi.check(self.lib.wekws_hip_ctc_kws_assign(self.h, a.ctypes.data, b.ctypes.data, len(a), ctypes.c_void_p(stream)),
+                    "wekws_hip_ctc_kws_assign")
+
     def decode_beam(self, raw: np.ndarray, cap: int):
         """One beam record -> [(prefix, pb, pnb, [(token, frame, prob), ...]), ...] in beam order."""
         PB = self.path_beam
@@ -125,7 +150,10 @@ def _results(res: torch.Tensor) -> np.ndarray:
                                                                        ("end", "<i4"), ("score", "<f8")]))
 
 
-def _search(probs, lengths, keywords, tokenset, score_beam_size, path_beam_size, want_beams: bool):
+def _search(probs, lengths, keywords, tokenset, score_beam_size, path_beam_size, want_beams: bool, more_sets=(),
+            set_of_row=None):
+    """One offline search.  ``more_sets``: (keywords, tokenset) pairs registered as sets 1, 2, ... beside the handle's own;
+    ``set_of_row``: the set of every row (None: set 0)."""
     x = _cuda_f32(probs, "ctc decode")
     B, T, V = x.shape
     if V < 1:
@@ -138,15 +166,27 @@ def _search(probs, lengths, keywords, tokenset, score_beam_size, path_beam_size,
         if lens.numel() != B:
             raise ValueError(f"ctc decode: {lens.numel()} lengths for {B} utterances")
     hd = _Handle(dev.index or 0, V, keywords, tokenset, score_beam_size, path_beam_size)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    for i, (kws, ts) in enumerate(more_sets):
+        if hd.add_set(kws, ts, 0.0, stream) != i + 1:
+            raise RuntimeError("ctc decode: keyword set ids out of order")
+    rows = None
+    if set_of_row is not None:
+        rows = np.array([int(s) for s in set_of_row], np.int32)
+        if rows.size != B or (B and (rows.min() < 0 or rows.max() > len(more_sets))):
+            raise ValueError(f"ctc decode: set_of_row must hold {B} indices in 0..{len(more_sets)}")
     res = torch.empty((B, 32), dtype=torch.uint8, device=dev)
     cap = max(T, 1)
     bb = hd.beam_bytes(cap)
     beams = torch.empty((B, bb), dtype=torch.uint8, device=dev) if (want_beams and B) else None
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    if B:
+    if B and rows is None:
         _capi.check(hd.lib.wekws_hip_ctc_kws_search(hd.h, x.data_ptr(), B, T, lens.data_ptr(), res.data_ptr(),
                                                      beams.data_ptr() if beams is not None else None,
                                                      ctypes.c_void_p(stream)), "wekws_hip_ctc_kws_search")
+    elif B:
+        _capi.check(hd.lib.wekws_hip_ctc_kws_search_sets(hd.h, x.data_ptr(), B, T, lens.data_ptr(), rows.ctypes.data,
+                                                          res.data_ptr(), beams.data_ptr() if beams is not None else None,
+                                                          ctypes.c_void_p(stream)), "wekws_hip_ctc_kws_search_sets")
     r = _results(res)
     for b in range(B):
         if r["status"][b] != 0:
@@ -178,13 +218,34 @@ def keyword_search(probs: torch.Tensor, lengths, keywords, score_beam_size: int 
             for x in r]
 
 
+def keyword_search_sets(probs: torch.Tensor, lengths, keyword_sets, set_of_row, score_beam_size: int = 3,
+                        path_beam_size: int = 20):
+    """``keyword_search`` with a keyword list per row, in one launch: ``keyword_sets`` is a sequence of keyword collections
+    (each a dict or a sequence, as ``keyword_search`` takes one), ``set_of_row[b]`` the index of row b's.  Every set decodes
+    with its own token set (blank included).  Returns per utterance ``(keyword or None, hit_score, start frame, end frame)``,
+    the keyword named from the row's own set."""
+    lists = [_keyword_lists(k) for k in keyword_sets]
+    if not lists:
+        raise ValueError("keyword_search_sets: no keyword set")
+    sets = [(toks, {0} | {t for k in toks for t in k}) for _, toks in lists]
+    which = [int(s) for s in set_of_row]
+    _, r, _, _ = _search(probs, lengths, sets[0][0], sets[0][1], score_beam_size, path_beam_size, False, sets[1:], which)
+    return [(lists[s][0][int(x["keyword"])] if x["state"] else None, float(x["score"]), int(x["start"]), int(x["end"]))
+            for x, s in zip(r, which)]
+
+
 class StreamingKeywordSpotter:
     """``KeyWordSpotter`` (wekws/bin/stream_kws_ctc.py) after the model, for ``num_streams`` streams on one device.
 
     ``step(probs, frames=None, streams=None)``: probs (B, T, V) posteriors on the device (``forward_softmax``'s output),
     row b continuing stream ``streams[b]`` (default: 0 .. B-1) with its first ``frames[b]`` frames (default T).  Returns,
     per row, ``KeyWordSpotter.forward``'s result dict (``{}`` for a row without frames); a stream that failed (an infinite
-    posterior, a prefix beyond ``prefix_capacity``) returns ``{"status": code}`` until ``reset`` / ``reset_all``."""
+    posterior, a prefix beyond ``prefix_capacity``) returns ``{"status": code}`` until ``reset`` / ``reset_all``.
+
+    Every stream may have its own keywords (``KeyWordSpotter.set_keywords``, one object per user, in the reference):
+    ``add_keywords`` registers a keyword set beside the constructor's (set 0, where every stream starts), ``assign`` gives it
+    to streams -- from its next frame an assigned stream is a fresh ``KeyWordSpotter`` built with that set --, ``drop_keywords``
+    frees a set no stream uses.  The beams and ``min_frames`` / ``max_frames`` / ``interval_frames`` stay the spotter's."""
 
     def __init__(self, num_streams: int, keywords, threshold: float, min_frames: int = 5, max_frames: int = 250,
                  interval_frames: int = 50, score_beam: int = 3, path_beam: int = 20, downsampling: int = 1,
@@ -200,6 +261,9 @@ class StreamingKeywordSpotter:
                          interval_frames=interval_frames, downsampling=downsampling, max_streams=num_streams,
                          prefix_capacity=prefix_capacity or max(256, 2 * max_frames + 64))
         self._hd = None
+        # host mirror of the keyword sets: id -> names, and the set of every stream
+        self._set_names = {0: self.names}
+        self._set_of = [0] * self.num_streams
         if vocab is not None:
             self._create(vocab)
 
@@ -210,30 +274,88 @@ class StreamingKeywordSpotter:
                            c["max_streams"], c["prefix_capacity"])
         self.vocab = vocab
 
-    def _ids(self, streams, n: int) -> torch.Tensor:
+    def _id_list(self, streams, n: int) -> List[int]:
         ids = list(range(n)) if streams is None else [int(s) for s in (streams.tolist() if hasattr(streams, "tolist") else streams)]
         if len(ids) != n:
             raise ValueError(f"{len(ids)} stream ids for {n} rows")
         if len(set(ids)) != len(ids) or any(s < 0 or s >= self.num_streams for s in ids):
             raise ValueError(f"stream ids must be distinct and in 0..{self.num_streams - 1}")
-        return torch.tensor(ids, dtype=torch.int32, device=self.device)
+        return ids
+
+    def _ids(self, streams, n: int) -> torch.Tensor:
+        return torch.tensor(self._id_list(streams, n), dtype=torch.int32, device=self.device)
+
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def add_keywords(self, keywords, threshold: Optional[float] = None, tokenset=None) -> int:
+        """Register a keyword set: ``keywords`` a dict or a sequence as the constructor takes, ``threshold`` None = the
+        spotter's own, ``tokenset`` None = the reference's ``{0} | tokens``.  Returns the set's id (>= 1)."""
+        if self._hd is None:
+            if self.vocab is None:
+                raise ValueError("StreamingKeywordSpotter.add_keywords: the vocabulary is not known yet: pass vocab= to the "
+                                 "constructor")
+            self._create(self.vocab)
+        names, toks = _keyword_lists(keywords)
+        ts = {0} | {t for k in toks for t in k} if tokenset is None else {int(t) for t in tokenset}
+        thr = self._cfg["threshold"] if threshold is None else threshold
+        sid = self._hd.add_set(toks, ts, thr, self._stream())
+        self._set_names[sid] = names
+        return sid
+
+    def assign(self, streams, set_id: int) -> None:
+        """The streams (None: all) now use keyword set ``set_id`` and start over as by ``reset_all``."""
+        set_id = int(set_id)
+        if set_id not in self._set_names:
+            raise ValueError(f"keyword set {set_id} is not registered")
+        ids = self._id_list(streams, len(streams) if streams is not None else self.num_streams)
+        if not ids:
+            return
+        if self._hd is None:
+            if self.vocab is None:
+                raise ValueError("StreamingKeywordSpotter.assign: the vocabulary is not known yet: pass vocab= to the constructor")
+            self._create(self.vocab)
+        self._hd.assign(ids, [set_id] * len(ids), self._stream())
+        for s in ids:
+            self._set_of[s] = set_id
+
+    def drop_keywords(self, set_id: int) -> None:
+        """Forget a keyword set no stream is assigned to; its id is handed out again."""
+        set_id = int(set_id)
+        if set_id == 0 or set_id not in self._set_names:
+            raise ValueError(f"keyword set {set_id} is not registered" if set_id else "set 0 is the spotter's own")
+        self._hd.drop_set(set_id, self._stream())
+        del self._set_names[set_id]
+
+    def keywords_of(self, stream: int) -> int:
+        """The id of the stream's keyword set."""
+        if not 0 <= int(stream) < self.num_streams:
+            raise ValueError(f"stream id {stream} outside 0..{self.num_streams - 1}")
+        return self._set_of[int(stream)]
 
     def step(self, probs: torch.Tensor, frames=None, streams=None) -> List[Dict]:
-        return [self._dict(r) for r in self.step_records(probs, frames, streams)]
+        recs, ids = self._step(probs, frames, streams)
+        return [self._dict(r, s) for r, s in zip(recs, ids)]
 
-    def _dict(self, r) -> Dict:
+    def _dict(self, r, stream: Optional[int] = None) -> Dict:
+        """A result record as ``KeyWordSpotter.forward``'s dict; the keyword is named from the stream's own set."""
         if r["status"] != 0:
             return {"status": int(r["status"])}
         if not r["valid"]:
             return {}
         on = bool(r["state"])
-        return {"state": 1 if on else 0, "keyword": self.names[int(r["keyword"])] if on else None,
+        names = self.names if stream is None else self._set_names[self._set_of[stream]]
+        return {"state": 1 if on else 0, "keyword": names[int(r["keyword"])] if on else None,
                 "start": int(r["start"]) * self.resolution if on else None,
                 "end": int(r["end"]) * self.resolution if on else None, "score": float(r["score"]) if on else None}
 
     def step_records(self, probs: torch.Tensor, frames=None, streams=None) -> np.ndarray:
         """``step`` returning the raw result records (status, valid, state, keyword, start, end, score) -- hit_score and
         the last detection included when the stream did not activate."""
+        return self._step(probs, frames, streams)[0]
+
+    def _step(self, probs: torch.Tensor, frames, streams) -> Tuple[np.ndarray, List[int]]:
+        """The records of one step and the stream id of every row."""
         x = _cuda_f32(probs, "StreamingKeywordSpotter.step")
         B, T, V = x.shape
         if self._hd is None:
@@ -242,7 +364,8 @@ class StreamingKeywordSpotter:
             self._create(V)
         if V != self.vocab:
             raise ValueError(f"StreamingKeywordSpotter.step: vocabulary {V}, the spotter has {self.vocab}")
-        ids = self._ids(streams, B)
+        id_list = self._id_list(streams, B)
+        ids = torch.tensor(id_list, dtype=torch.int32, device=self.device)
         if frames is None:
             fr = torch.full((B,), T, dtype=torch.int32, device=self.device)
         else:
@@ -255,7 +378,7 @@ class StreamingKeywordSpotter:
             _capi.check(self._hd.lib.wekws_hip_ctc_kws_step(self._hd.h, x.data_ptr(), B, T, ids.data_ptr(), fr.data_ptr(),
                                                             res.data_ptr(), ctypes.c_void_p(stream)),
                         "wekws_hip_ctc_kws_step")
-        return _results(res)
+        return _results(res), id_list
 
     def _reset(self, streams, all_: int):
         if self._hd is None:

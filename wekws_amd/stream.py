@@ -29,7 +29,11 @@ class BatchedKeyWordSpotter:
     StreamingFrontEnd's (``num_bins``, ``window``, ``left``, ``right``, ``skip``, ``max_chunk``, ...), the others
     StreamingKeywordSpotter's (``min_frames``, ``max_frames``, ``interval_frames``, ``score_beam``, ``path_beam``,
     ``prefix_capacity``); ``downsampling`` is ``skip``.  ``input_sample_rate`` (e.g. 48000): the chunks arrive at that rate and
-    pass a StreamingResampler (int16 out) to the front end's ``sample_rate`` first; ``max_chunk`` then counts INPUT samples."""
+    pass a StreamingResampler (int16 out) to the front end's ``sample_rate`` first; ``max_chunk`` then counts INPUT samples.
+
+    Streams of different users may have different wake words: ``sid = kws.add_keywords({...}, threshold)`` registers a keyword
+    set beside the constructor's, ``kws.set_keywords(sid, streams)`` gives it to streams (a new session for them),
+    ``kws.drop_keywords(sid)`` frees it once no stream uses it.  A step is still the same three device calls."""
 
     _FE = ("num_bins", "window", "left", "right", "skip", "max_chunk", "sample_rate", "frame_length", "frame_shift", "num_ceps",
            "cepstral_lifter")
@@ -98,6 +102,25 @@ class BatchedKeyWordSpotter:
             self.resampler.reset(streams)
         self.frontend.reset(streams)
         self.pool.reset(streams)
+
+    def add_keywords(self, keywords, threshold=None) -> int:
+        """Register a keyword set beside the constructor's (StreamingKeywordSpotter.add_keywords); returns its id."""
+        if self.spotter._hd is None:
+            self.spotter._create(int(self.model.odim))
+        return self.spotter.add_keywords(keywords, threshold)
+
+    def set_keywords(self, set_id: int, streams=None) -> None:
+        """``KeyWordSpotter.set_keywords`` for the given streams (default all): they use keyword set ``set_id`` from now on.  A stream that
+        gets new keywords is a new session: the decoder's assign, and reset_all of the front end, the resampler and the cache."""
+        self.spotter.assign(streams, set_id)
+        if self.resampler is not None:
+            self.resampler.reset(streams)
+        self.frontend.reset(streams)
+        self.pool.reset(streams)
+
+    def drop_keywords(self, set_id: int) -> None:
+        """Forget a keyword set no stream uses."""
+        self.spotter.drop_keywords(set_id)
 
 
 class BatchedThresholdSpotter:
