@@ -770,6 +770,63 @@ int wekws_hip_resample_reset(void* h, const int32_t* ids, int n);
 /* counts_out = {samples received, samples emitted, samples kept on the device, flushed (0 / 1)} of stream id. */
 int wekws_hip_resample_counts(void* h, int id, int64_t counts_out[4]);
 
+/* -------------------------------------------------------------------------------------------
+ * Augmentation  --  add_reverb, add_noise and spec_aug of the data pipeline (wekws/dataset/processor.py:374-392, 395-430,
+ * 206-240) on the device, between the resampler and the front end.  What is drawn at random (whether a row is augmented, which
+ * RIR or noise, where the noise starts, the SNR, the masks) is drawn by the caller and passed in HOST tables; every call checks
+ * its tables on the host before anything is launched, and the tables reach the device in stream order without a
+ * synchronisation, as wekws_hip_resample_compute's do (a ring of pinned tables grown on demand: not inside a stream capture
+ * when a call is larger than any before it).  Calls on one handle are serialised by a mutex and by the caller's stream.
+ *
+ * Reverberation: y[n] = sum_{k=0..min(n, L-1)} h[k] x[n-k], h = rir / sqrt(sum rir^2) (the sum in double), n < the row's
+ * length: signal.convolve(audio, h, 'full')[:len(audio)].  Computed as overlap-save convolution in float32 with the RIR in
+ * uniform partitions: hop H = wekws_hip_reverb_hop() = 2048, transforms of 2H points, P = ceil(L / H) partitions, output block b
+ * = the last H samples of the inverse transform of sum_{p=0..min(P-1, b)} X[b-p] Hf[p].  The partition spectra, transformed in
+ * double on the host, stay on the device: sum over the RIRs of P (H + 1) complex float32 (8 bytes each).
+ * ------------------------------------------------------------------------------------------*/
+int wekws_hip_reverb_hop(void);
+/* Without a device: out = {partitions of a rir_len-tap RIR, blocks of a row of nmax samples, bytes of scratch a call with B rows
+ * of up to nmax samples needs, bytes of the RIR's spectra}.  WEKWS_HIP_EINVAL for rir_len < 1, B < 0, nmax < 0 or > 2^30 - 1. */
+int wekws_hip_reverb_plan(int rir_len, int B, int nmax, int64_t out[4]);
+/* Without a device: the check wekws_hip_reverb_apply makes of a call, against RIRs of these lengths. */
+int wekws_hip_reverb_check(const int32_t* rir_lengths, int R, int B, int nmax, const int32_t* nsamp, const int32_t* rir_of_row);
+/* rirs (R, max_len) HOST float32, lengths (R) HOST int32: RIR r is rirs[r][0 .. lengths[r]).  A length outside 1..max_len, a
+ * NaN or an Inf among the taps, and an all-zero RIR (the reference divides by zero) are WEKWS_HIP_EINVAL. */
+int wekws_hip_reverb_create(const float* rirs, const int32_t* lengths, int R, int max_len, int device, void** out);
+void wekws_hip_reverb_destroy(void* h);
+/* Bytes of scratch (the rows' input spectra) a call needs.  The handle owns the scratch and grows it on demand (a call larger
+ * than any before it allocates: not inside a stream capture). */
+size_t wekws_hip_reverb_workspace_bytes(void* h, int B, int nmax);
+/* pcm, out (B, nmax) device float32 in any scale (the operation is linear);  nsamp (B) HOST int32 valid samples per row, NULL =
+ * nmax;  rir_of_row (B) HOST int32: the row's RIR, -1 = the row is copied bit for bit.  Samples of out at or past nsamp[b] are
+ * left as they were.  out == pcm, a length outside 0..nmax and an RIR index outside -1..R-1 are WEKWS_HIP_EINVAL and launch
+ * nothing.  A row's result does not depend on the other rows, and two identical calls give identical bits.  A row with a NaN
+ * or an Inf among its valid samples is NaN over its whole valid length (what the reference's FFT convolution gives); the
+ * other rows are unaffected. */
+int wekws_hip_reverb_apply(void* h, const float* pcm, int B, int nmax, const int32_t* nsamp, const int32_t* rir_of_row, float* out,
+                           void* stream);
+/* Noise at a drawn SNR.  noises (Rn, max_len) HOST float32 in int16 scale with a length each, as for the RIRs.  With
+ *   v[n] = noise[(start + n) mod nlen]          (start + nsamp <= nlen where the noise is longer than the row: cut, not wrapped)
+ *   audio_db = 10 log10(mean((pcm / pcm_scale)^2) + 1e-4),  noise_db = 10 log10(mean(v^2) + 1e-4)   (both sums in double)
+ *   g = sqrt(10^((audio_db - noise_db - snr_db) / 10))      (in double on the device, rounded to float32)
+ * out = pcm + pcm_scale g v, one fmaf a sample.  pcm_scale (> 0; rounded to float32) is 1 for samples in [-1, 1] and 32768 for
+ * the int16-scale floats the front end takes.  noise_of_row -1 copies the row; start, snr_db (B) HOST; out may be pcm;
+ * non-finite samples propagate as IEEE arithmetic has them.  start < 0, a start that runs a longer noise past its end, a
+ * non-finite snr_db and the refusals of wekws_hip_reverb_apply are WEKWS_HIP_EINVAL and launch nothing. */
+int wekws_hip_noise_create(const float* noises, const int32_t* lengths, int Rn, int max_len, int device, void** out);
+void wekws_hip_noise_destroy(void* h);
+/* Without a device: the check wekws_hip_noise_mix makes of a call, against noises of these lengths. */
+int wekws_hip_noise_check(const int32_t* noise_lengths, int Rn, int B, int nmax, const int32_t* nsamp, const int32_t* noise_of_row,
+                          const int32_t* start, const double* snr_db, double pcm_scale);
+int wekws_hip_noise_mix(void* h, const float* pcm, int B, int nmax, const int32_t* nsamp, const int32_t* noise_of_row, const int32_t* start,
+                        const double* snr_db, double pcm_scale, float* out, void* stream);
+/* SpecAugment masks.  feats, out (B, T, F) device float32;  lengths (B) HOST int32 frames per row, NULL = T;  t_masks (B, nt, 2)
+ * and f_masks (B, nf, 2) HOST int32 [start, end) pairs, already clipped as the reference clips them: 0 <= start <= end <= the
+ * row's frames / F, else WEKWS_HIP_EINVAL.  Within a row's frames the frames of its time masks and the bins of its frequency
+ * masks become 0; everything else, the frames past the row's length included, is copied.  out may be feats. */
+int wekws_hip_spec_mask(const float* feats, int B, int T, int F, const int32_t* lengths, const int32_t* t_masks, int nt,
+                        const int32_t* f_masks, int nf, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
