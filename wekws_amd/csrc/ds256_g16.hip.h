@@ -131,7 +131,8 @@ __global__ __launch_bounds__(kW16Threads) void ds256_g16_kernel(const StackParam
   // 104 k cycles where the kernel takes 114 k per utterance and CU: a tenth of the time went into workgroup turnover
   // (16 waves and 160 KB of LDS to release, allocate and start four times per CU).
   // FAST: the NEXT utterance's features are copied from HBM straight into LDS (global_load_lds: no registers) behind the
-  // classifier of the current one, into the 32 KB of the dynamic allocation above the planes (where the general
+  // classifier of the current one (the context variant; WARM, below: at the top of the current one's block 0, a whole utterance
+  // ahead), into the 32 KB of the dynamic allocation above the planes (where the general
   // instantiation keeps the classifier's f32 tile) -- a linear copy of T * idim floats in 16-byte pieces, 1 KiB per wave
   // and instruction.  The trip to HBM that used to open every utterance (features -> registers -> maximum) now ends
   // before the utterance starts.
@@ -148,7 +149,40 @@ __global__ __launch_bounds__(kW16Threads) void ds256_g16_kernel(const StackParam
                                          (__attribute__((address_space(3))) void*)(xbuf + wbase * 4), 16, 0, 0);
     }
   };
+  // The same copy, requested a whole utterance ahead (WARM, below).  Spelled as inline assembly because of what the compiler does
+  // with the builtin: it cannot tell which LDS bytes the copy writes, so it drains the memory counter in front of the NEXT LDS
+  // instruction of any kind -- fine where the features are wanted at once (the cold path), an exposed trip to HBM where they are
+  // wanted 100 k cycles later.  The compiler does not count these loads; its own counted waits can only come out longer for
+  // that, never shorter (loads return in order: a wait for a younger load covers them, a wait for an older one leaves them out).
+  auto prefetch_x_ahead = [&](int bn) __attribute__((always_inline)) {
+    // (thread index opaque: the 64-bit piece offsets are to be computed here, not once in front of the utterance loop and kept
+    // in scratch)
+    int t0 = threadIdx.x;
+    asm volatile("" : "+v"(t0));
+    const int nitems = (A.T * P.idim) >> 2;
+    const float* src = A.x + int64_t(bn) * A.xs_b;
+    for (int e0 = 0; e0 < nitems; e0 += kW16Threads) {
+      const int wbase = __builtin_amdgcn_readfirstlane(e0 + (t0 & ~63));
+      const unsigned at = static_cast<unsigned>(reinterpret_cast<uintptr_t>(xbuf + wbase * 4));   // LDS offset = low half of the flat address
+      if (e0 + t0 < nitems)
+        asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, off"   // (M0 = LDS address, written by the compiler; one wait state)
+                     :: "v"(src + (e0 + t0) * 4), "{m0}"(at) : "memory");
+    }
+  };
   if constexpr (FAST) prefetch_x(blockIdx.x);
+  // WARM (FAST without incoming cache): an utterance that follows another one in the walk is staged UNDER that one's classifier (the
+  // fused boundary behind the block loop) -- its items taken from xbuf, its maximum published, its operand planes written, its input
+  // layer multiplied -- and enters the loop body at the residual blocks.  `warm` says so; workgroup-uniform.  The prologue below is
+  // the cold path: the first utterance of a walk, the one after an utterance that left for non-finite input, every one-pass launch.
+  // (-DWEKWS_G16_COLD_BOUNDARY builds the kernel with the cold sequence for every utterance: the A/B aid of
+  // profiles/r07_boundary_ab.txt, tools/abvar.sh)
+#ifdef WEKWS_G16_COLD_BOUNDARY
+  constexpr bool WARM = false;
+#else
+  constexpr bool WARM = FAST && !CTX;
+#endif
+  bool warm = false;
+  F16Frag a0;                                                // weight fragment of the even K steps; K step 0: carried over (WARM: over the boundary)
   for (int b = blockIdx.x; b < A.B; b += gridDim.x) {          // (not FAST: the grid is B, one pass)
   // (the weight pointer is re-made opaque for every utterance: with a loop-invariant __restrict__ pointer the compiler
   // hoists the preprocessing fragments, biases and classifier rows out of the loop and keeps them in registers for the
@@ -211,7 +245,44 @@ __global__ __launch_bounds__(kW16Threads) void ds256_g16_kernel(const StackParam
     if constexpr (FAST) {
       if (b + int(gridDim.x) < A.B) prefetch_x(b + gridDim.x);
     }
+    // (WARM: the cold prologue that follows drains the memory counter at once anyway.  Done here, the compiler sees no load of
+    // the abandoned utterance in flight on ANY way into the block loop, and puts no wait of its own behind the ahead-copy there.)
+    if constexpr (WARM) { warm = false; __builtin_amdgcn_s_waitcnt(0x0F70); }
   };
+  // WARM: another utterance of this walk follows -- this one's classifier stages it (workgroup-uniform)
+  const bool more = WARM && b + int(gridDim.x) < A.B;
+  // the input layer's pieces, shared by the cold prologue and the fused boundary
+  auto pre_frags = [&](F16Frag (&a)[2]) __attribute__((always_inline)) {
+    const uint4* ap = reinterpret_cast<const uint4*>(W + P.pre_a16) + size_t(wave) * nk * 128 + lane;
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {                         // in flight over the barriers (nk = 1: the same step twice)
+      const uint4* q = ap + min(st, nk - 1) * 128;
+      a[st].h = __builtin_bit_cast(f16x8, q[0]);
+      a[st].l = __builtin_bit_cast(f16x8, q[64]);
+    }
+  };
+  auto pre_mfma = [&](const F16Frag (&a)[2]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int st = 0; st < 2; ++st)                           // (compile-time indices: a runtime-indexed fragment array spills)
+      if (st < nk)
+        g16_mfma_step<NT, SPLIT>(acc, a[st], planes + st * 2 * PB + frag_off, planes + st * 2 * PB + PB + frag_off);
+  };
+  auto pre_epilogue = [&](float cpre, const float4& bias) __attribute__((always_inline)) {
+    cpre *= P.pre_inv_s;                                     // 1 / (feature scale * weight scale)
+    float hmax = 0.f;
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = fmaf(acc[tt][r], cpre, f4c(bias, r));
+        if (P.pre_relu) v = fmaxf(v, 0.f);
+        hv[tt][r] = v;
+        hmax = fmaxf(hmax, fabsf(v));
+      }
+    }
+    amax_publish(amax_cells + 2, hmax);
+  };
+  if (!(WARM && warm)) {                                     // ---- the cold path, down to barrier (A) (not indented)
   amax_zero<kW16Threads>(amax_cells, kAmaxCells);
   // The features are requested before the barrier: the table's trip to L2 (first utterance), the barrier and the request
   // for block 0's taps (whose address is in the table) all happen while the features are on their way from HBM.
@@ -241,21 +312,13 @@ __global__ __launch_bounds__(kW16Threads) void ds256_g16_kernel(const StackParam
     float sx = 1.f, cpre = 1.f;
     if (one_trip) {
       F16Frag a[2];
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {                       // in flight over the barriers (nk = 1: the same step twice)
-        const uint4* q = ap + min(st, nk - 1) * 128;
-        a[st].h = __builtin_bit_cast(f16x8, q[0]);
-        a[st].l = __builtin_bit_cast(f16x8, q[64]);
-      }
+      pre_frags(a);
       __syncthreads();
       if (amax_inputs_bad(amax_cells)) { skip_bad(); continue; }
       sx = pow2_scale(amax_read(amax_cells), &cpre);
       w16_store_x<PB, SPLIT>(xi, sx, planes);
       __syncthreads();
-#pragma unroll
-      for (int st = 0; st < 2; ++st)                         // (compile-time indices: a runtime-indexed fragment array spills)
-        if (st < nk)
-          g16_mfma_step<NT, SPLIT>(acc, a[st], planes + st * 2 * PB + frag_off, planes + st * 2 * PB + PB + frag_off);
+      pre_mfma(a);
     } else {
     __syncthreads();
     if (amax_inputs_bad(amax_cells)) { skip_bad(); continue; }
@@ -291,31 +354,38 @@ __global__ __launch_bounds__(kW16Threads) void ds256_g16_kernel(const StackParam
       }
     }
     }
-    cpre *= P.pre_inv_s;                                     // 1 / (feature scale * weight scale)
-    float hmax = 0.f;
-#pragma unroll
-    for (int tt = 0; tt < NT; ++tt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = fmaf(acc[tt][r], cpre, f4c(bias, r));
-        if (P.pre_relu) v = fmaxf(v, 0.f);
-        hv[tt][r] = v;
-        hmax = fmaxf(hmax, fabsf(v));
-      }
-    }
-    amax_publish(amax_cells + 2, hmax);
+    pre_epilogue(cpre, bias);
     __syncthreads();                                         // (A) maximum published, planes free, taps staged
   }
   G16_PH(0);                                                 // [0] preprocessing
+  }                                                          // ---- (cold path)
   // ======================================= residual blocks =======================================
-  F16Frag a0;                                                // weight fragment of the even K steps; K step 0: carried over
   auto frag_base = [&](int i) __attribute__((always_inline)) {
     return reinterpret_cast<const uint4*>(W + __builtin_amdgcn_readfirstlane(blk[i].a1_16)) + size_t(wave) * OTS;
   };
-  {
+  if (!(WARM && warm)) {                                     // (warm: requested by the last pass of the utterance before)
     const uint4* ap0 = frag_base(0);
     F16Frag t[1];
     load_a16<1>(t, ap0 + lane, 0); a0 = t[0];
+    // (cold path only: the fragment is waited for HERE, as the compiler always did in front of the block loop; merged with the
+    // warm path's carried registers first, its wait would come behind the feature copy below and expose that trip)
+    if constexpr (WARM) asm volatile("" :: "v"(a0.h), "v"(a0.l));
+  }
+  if constexpr (WARM) {
+    // The features of the NEXT utterance of the walk, a whole utterance ahead of their use.  xbuf is dead here: this utterance's
+    // items were taken from it at least two barriers ago (cold: in front of the input layer; warm: in phase 1 of the boundary).
+    // Nobody waits for the copy by name.  Every wave issues its pieces here, in front of block 0's depthwise phase, and then
+    // drains its memory counter in each of the four matrix phases below (loads return in order: the waits for the weight
+    // fragments requested behind the copy cover it); the barriers between here and phase 1 of the boundary, where the
+    // items are taken, make every wave's pieces visible to all.  The depthwise phase of block 0 (~6 k cycles) covers the trip.
+    // The hand-over stores come later and are not waited for on the copy's account.
+    // (The explicit vmcnt(0) in front: nothing is in flight here on either path -- cold: a0 was just waited for; warm: the boundary
+    // consumed everything it requested -- but the compiler cannot see that across the utterance loop and otherwise drains the
+    // counter in the block loop's preheader, BEHIND the copy.)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    if (more) prefetch_x_ahead(b + gridDim.x);
+    // cell [0] (features) was last read in front of barrier (A) / (A'); its next publish is phase 1 of the boundary
+    if (tid == 0) amax_cells[0].v = 0u;
   }
   for (int bi = 0; bi < P.nblocks; ++bi) {
     const BlockDesc bd = blk[bi];
@@ -323,7 +393,9 @@ __global__ __launch_bounds__(kW16Threads) void ds256_g16_kernel(const StackParam
     // (wave-uniform bases in scalar registers: the fragment addresses are base + lane, one shared vector offset)
     const uint4* ap1 = frag_base(bi);
     // the fragment of the NEXT block's first K step is requested by this block's last pass (below)
-    const uint4* apn = frag_base(min(bi + 1, P.nblocks - 1));
+    // (last block: block 0's again when another utterance of the walk follows -- it arrives during the boundary)
+    const int bnext = bi + 1 < P.nblocks ? bi + 1 : (more ? 0 : bi);
+    const uint4* apn = frag_base(bnext);
     // ---- operand scale of this block: the depthwise rows are bounded through the maximum of the input tile (published
     //      by the epilogue that produced it)
     float c1;
@@ -397,7 +469,7 @@ __global__ __launch_bounds__(kW16Threads) void ds256_g16_kernel(const StackParam
     }
     const float4 ebias = *reinterpret_cast<const float4*>(W + bd.b1 + o0);
     // next block's taps: on their way into LDS during the matrix phase
-    if (bi + 1 < P.nblocks) stage_taps(blk[bi + 1]);         // (this block's taps were last read before barrier (B))
+    if (bi + 1 < P.nblocks || more) stage_taps(blk[bnext]);  // (this block's taps were last read before barrier (B))
 
     // ---- pointwise conv: all eight K steps back to back
     auto kpass = [&](int ks, auto first_c) __attribute__((always_inline)) {
@@ -458,15 +530,17 @@ __global__ __launch_bounds__(kW16Threads) void ds256_g16_kernel(const StackParam
     // channel groups -- meet in LDS where the planes were, four lanes add 16 of them each, a quad reduction and the
     // sigmoid finish the frame: one barrier, ~60 vector and ~25 LDS instructions per wave instead of writing the tile to
     // LDS for conv_stack_head (two more barriers, 80 LDS reads per output part; 8 k of the kernel's 110 k cycles).
+    // The partial sums live behind the first two K steps' planes (4 PB + 64 PS 4 = 12,288 NT + 4,096 bytes <= 16 PB for every
+    // NT): in the fused boundary the next utterance's operand planes are written to 0 .. 4 PB while the sums are added up.
     const int K = P.odim;
     constexpr int PS = 32 * NT + 16;                          // floats per partial row: 16 lanes x (NT frames x 2 outputs), padded
-    float* const part = w16_lds;
-    {
-      const float4 w0 = *reinterpret_cast<const float4*>(W + P.head_w + o0);
-      const float4 w1 = *reinterpret_cast<const float4*>(W + P.head_w + (K > 1 ? C : 0) + o0);
-      if constexpr (FAST) {                                  // (behind the classifier rows: loads return in order)
-        if (b + int(gridDim.x) < A.B) prefetch_x(b + gridDim.x);
-      }
+    static_assert(4 * PB + 64 * PS * 4 <= 2 * NKS * PB, "the partial sums end inside the planes");
+    float* const part = w16_lds + PB;                         // (4 PB bytes in)
+    // (the classifier's addresses are derived from an opaque copy of the thread index: the 64-bit channel offset the block tops
+    // use would otherwise be kept for these loads across the block loop, in scratch)
+    int th = threadIdx.x;
+    if constexpr (WARM) asm volatile("" : "+v"(th));
+    auto head_partials = [&](const float4& w0, const float4& w1) __attribute__((always_inline)) {
       float* dst = part + (wave * 4 + lq) * PS + 2 * NT * l15;
       const HeadPairs hw(w0, w1);                            // (packed, operand selects spelled out: pk_safe.hip.h)
 #pragma unroll
@@ -475,9 +549,13 @@ __global__ __launch_bounds__(kW16Threads) void ds256_g16_kernel(const StackParam
         head_fma4(pp, hw.x, hw.y, hw.z, hw.w, hv[tt]);
         *reinterpret_cast<float2*>(dst + 2 * tt) = float2{pp.x, pp.y};   // frame NT l15 + tt: outputs (0, 1)
       }
-    }
-    __syncthreads();
-    {
+    };
+    // (the head's bias is requested with the classifier rows, in front of the barrier: read where it is added, its trip to L2 sat
+    // between the partial sums and the store of y with nothing to cover it)
+    // (WARM only: in the other instantiations one more register across the barrier costs scratch)
+    float hbias = 0.f;
+    if constexpr (WARM) hbias = W[P.head_b + (((th >> 2) & 1) < K ? (th >> 2) & 1 : 0)];
+    auto head_reduce = [&]() __attribute__((always_inline)) {
       const int e = tid >> 2, qd = tid & 3;                  // e = 2 frame + output; four lanes per e
       const int t = e >> 1, k = e & 1;
       const float* src = part + qd * 16 * PS + e;
@@ -487,11 +565,72 @@ __global__ __launch_bounds__(kW16Threads) void ds256_g16_kernel(const StackParam
       v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
       v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
       if (qd == 0 && t < T && k < K) {
-        v += W[P.head_b + k];
+        v += WARM ? hbias : W[P.head_b + k];
         if (P.sigmoid) v = sigmoidf_(v);
         A.y[int64_t(b) * A.ys_b + int64_t(t) * K + k] = v;
       }
+    };
+    const int o0h = (th >> 6) * 16 + ((th >> 4) & 3) * 4;     // = o0
+    const float4 w0 = *reinterpret_cast<const float4*>(W + P.head_w + o0h);
+    const float4 w1 = *reinterpret_cast<const float4*>(W + P.head_w + (K > 1 ? C : 0) + o0h);
+    if (more) {
+      // ---- WARM: the fused boundary -- this utterance's classifier and the next one's preprocessing in three steps.
+      // Order of events on the maximum cells (no cell is cleared between its publish and its read):
+      //   [0] features   zeroed at the top of block 0 (behind (A) / (A'), its last read in front of it); published in phase 1; read in phase 2
+      //   [2 ..]         last read at a block top, in front of the last block's barrier (A); zeroed in phase 1; [2] published
+      //                  by the input layer behind (B2), [3 + i] by the block epilogues behind (A')
+      //   [1] cache      never published without an incoming cache: zero since the cold path's amax_zero
+      const int bn = b + int(gridDim.x);
+      // phase 1, (A) .. (B1): head partial sums; the next utterance's items out of xbuf, its maximum; the input layer's fragments
+      // (the fragments and the bias are requested right behind the classifier rows, all in one trip that taking the items and
+      // publishing their maximum cover: the weights travel as FLAT loads, which the compiler waits for all at once, so a request
+      // placed behind the first use of the classifier rows would be waited for on the spot)
+      F16Frag a[2];
+      pre_frags(a);
+      const float4 bias = *reinterpret_cast<const float4*>(W + P.pre_b + o0h);
+      if (tid >= 2 && tid < kAmaxCells) amax_cells[tid].v = 0u;
+      const W16XItem xn = g16_take_x<NT, PB>(xbuf, T, P.idim, nk, tid);
+      amax_publish(amax_cells, w16_x_amax_bits(xn));
+      head_partials(w0, w1);
+      __syncthreads();                                       // (B1) partial sums written, maximum published, xbuf free
+      // phase 2, (B1) .. (B2): y of this utterance; the next one's operand planes
+      // (the input layer's fragments and bias, requested in phase 1, are in the registers HERE, in front of the stores of y.
+      // Loads and stores share one in-order counter: waited for behind the stores, at the first MFMA, they would wait for
+      // the stores' trip to memory as well.)
+      asm volatile("" :: "v"(a[0].h), "v"(a[0].l), "v"(a[1].h), "v"(a[1].l), "v"(bias.x), "v"(bias.y), "v"(bias.z), "v"(bias.w));
+      head_reduce();
+      if (amax_inputs_bad(amax_cells)) {
+        // the next utterance holds a NaN / Inf: noted for the tail (the barrier inside keeps the cells until every wave has
+        // read them), ITS successor's features requested, and the walk goes on cold behind it
+        nf_list_note(nfl, bn);
+        if (bn + int(gridDim.x) < A.B) prefetch_x(bn + gridDim.x);
+        __builtin_amdgcn_s_waitcnt(0x0F70);                  // (as in skip_bad: nothing in flight on the way back into the loop)
+        G16_PH(7);
+        b = bn; warm = false;
+        continue;
+      }
+      float cpre;
+      const float sx = pow2_scale(amax_read(amax_cells), &cpre);
+      w16_store_x<PB, SPLIT>(xn, sx, planes);
+      G16_PH(7);                                             // [7] classifier = phases 1 and 2 of the boundary
+      __syncthreads();                                       // (B2) the next utterance's planes are written
+      // input layer, (B2) .. (A')
+#pragma unroll
+      for (int tt = 0; tt < NT; ++tt) acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      pre_mfma(a);
+      pre_epilogue(cpre, bias);
+      __syncthreads();                                       // (A') maximum published, planes free, taps staged
+      G16_PH(0);                                             // [0] preprocessing = the input layer of the boundary
+      warm = true;
+      continue;
     }
+    warm = false;
+    if constexpr (FAST && !WARM) {                           // (behind the classifier rows: loads return in order)
+      if (b + int(gridDim.x) < A.B) prefetch_x(b + gridDim.x);
+    }
+    head_partials(w0, w1);
+    __syncthreads();
+    head_reduce();
   } else if constexpr (!FAST) {
     // every other head reads the tile from LDS (conv_stack_head): written once, where the planes were
 #pragma unroll
