@@ -827,6 +827,37 @@ int wekws_hip_noise_mix(void* h, const float* pcm, int B, int nmax, const int32_
 int wekws_hip_spec_mask(const float* feats, int B, int T, int F, const int32_t* lengths, const int32_t* t_masks, int nt,
                         const int32_t* f_masks, int nf, float* out, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * Global CMVN statistics  --  the accumulation of tools/compute_cmvn_stats.py (:26-72 per batch, :128-151 over the batches):
+ * per bin the sum of the features ("mean_stat") and of their squares ("var_stat") over every valid frame, and the frame
+ * count ("frame_num"), for features that are already on the device.  A handle keeps the running totals of its `dim` bins on
+ * its device; calls on one handle are serialised by a mutex and by the caller's stream.
+ *
+ * Accumulation is in double from the first add ((double)x and its square are exact), where the reference adds in float32:
+ * each statistic is within N 2^-53 sum|term| of the exact sum over the N frames added since the last reset.  The one
+ * deviation from the reference: a sum that overflows float32 stays finite here.  Non-finite features propagate as IEEE
+ * addition has them, per bin: a NaN gives NaN, +Inf alone +Inf, +Inf and -Inf together NaN in mean_stat and +Inf in var_stat.
+ * The bits a call adds are a function of (feats, lengths, B, T, dim) alone: tiles of a fixed number of frames, their partial
+ * sums folded in one fixed order, no floating-point atomics.
+ * ------------------------------------------------------------------------------------------*/
+/* dim outside 1..4096 is WEKWS_HIP_EINVAL (before any device work); no such device is WEKWS_HIP_EDEVICE. */
+int wekws_hip_cmvn_stats_create(int dim, int device, void** out);
+void wekws_hip_cmvn_stats_destroy(void* h);
+/* Without a device: out = {frames a tile holds (from D alone), tiles of a call over (B, T, D), bytes of scratch the call needs:
+ * 2 D doubles a tile, and for more than 64 tiles as much per 64 tiles}.
+ * WEKWS_HIP_EINVAL for D outside 1..4096, a negative B or T, or more than 2^31 - 1 frames. */
+int wekws_hip_cmvn_stats_plan(int B, int T, int D, int64_t out[3]);
+/* feats (B, T, dim) device float32;  lengths (B) DEVICE int32 frames per row, NULL = T.  Frames at or past a row's length are
+ * never read (a NaN in the padding does not reach the sums); a row whose length is outside 0..T adds nothing and is counted
+ * as a bad row.  Asynchronous: two launches (three for more than 64 tiles), no synchronisation; the handle's scratch grows on
+ * demand (a call larger than any before it allocates: not inside a stream capture).  A negative B or T, or more than 2^31 - 1
+ * frames, is WEKWS_HIP_EINVAL. */
+int wekws_hip_cmvn_stats_update(void* h, const float* feats, int B, int T, const int32_t* lengths, void* stream);
+/* The totals and both counters start over (asynchronous). */
+int wekws_hip_cmvn_stats_reset(void* h, void* stream);
+/* mean_stat, var_stat (dim) HOST doubles; counts = {frame_num, bad_rows}.  The one call that synchronises (with `stream`). */
+int wekws_hip_cmvn_stats_read(void* h, double* mean_stat, double* var_stat, int64_t counts[2], void* stream);
+
 #ifdef __cplusplus
 }
 #endif
