@@ -365,6 +365,29 @@ int wekws_hip_fbank_compute_i16(wekws_hip_fbank* f, const int16_t* pcm, int B, i
                                 void* stream);
 
 /*
+ * The same extractor with DITHER  --  `dither` of kaldi.fbank / kaldi.mfcc as every training recipe of the reference sets it
+ * (fbank_conf / mfcc_conf `dither: 1.0`, wekws/dataset/processor.py:134-203; the C++ stage: fbank.h:105,150-153): after the signal
+ * is cut into frames and before the DC removal,  frame[i] += dither * N(0, 1),  an independent draw for every (frame, sample) of
+ * the frame's frame_length samples, the signal in int16 scale.  The draws are made inside the kernel by a counter-based generator
+ * (Philox4x32-10 + Box-Muller): the draw at (seed, row id, frame, sample) is a pure function of those four numbers, where row b of
+ * the call has row id first_row + b  --  a data set cut into batches in any way gets the same noise per utterance, a repeated call
+ * the same bits, and float32 PCM holding int16 values the bits of the int16 call.  One deviation from the reference: it draws
+ * from torch's global CPU generator; that stream is not reproduced, the distribution and the place of the addition are.
+ *   dither == 0            the plain call above, bit for bit (it IS that call)
+ *   dither < 0, NaN, Inf   WEKWS_HIP_EINVAL, nothing is launched
+ */
+int wekws_hip_fbank_compute_dither(wekws_hip_fbank* f, const float* pcm, int B, int nsamp, float* feats, float dither,
+                                   uint64_t seed, int64_t first_row, void* stream);
+int wekws_hip_fbank_compute_dither_i16(wekws_hip_fbank* f, const int16_t* pcm, int B, int nsamp, float* feats, float dither,
+                                       uint64_t seed, int64_t first_row, void* stream);
+/*
+ * The unit-variance normal field the two calls above scale by `dither` and add: out (B, nframes, frame_length) device float32,
+ * out[b][t][i] the draw of (seed, first_row + b, frame t, sample i).  1 <= frame_length <= 512.  Runs on the current device.
+ * The definition (generator, key, counter, sample mapping, uniforms, transform): csrc/philox.hip.h.
+ */
+int wekws_hip_dither_noise(uint64_t seed, int64_t first_row, int B, int nframes, int frame_length, float* out, void* stream);
+
+/*
  * Context expansion + frame skip  --  replaces context_expansion / frame_skip of the data pipeline
  * (wekws/dataset/init_dataset.py:24-68, wekws/dataset/processor.py:267-311; fsmn_ctc.yaml:21-25 uses left 2,
  * right 2, skip 3: 80-d fbank -> the 400-d FSMN input at a third of the frame rate), fused into one gather:

@@ -1,4 +1,5 @@
-// The fbank extractor: instantiations of fbank_kernel (fbank.hip.h), the handle and its C entry points.
+// The fbank extractor: instantiations of fbank_kernel (fbank.hip.h), the handle and its C entry points.  (The dithered instantiations
+// and their entry points: fbank_dither.hip.)
 #include <new>
 #include <vector>
 
@@ -64,6 +65,8 @@ int wekws_hip_fbank_create(const wekws_hip_fbank_cfg* cfg, int device, wekws_hip
   f->fp.tables = f->d_tables;
   f->resident_f32 = wekws::fbank_resident_groups<float>(f->fp);
   f->resident_i16 = wekws::fbank_resident_groups<int16_t>(f->fp);
+  f->resident_dither_f32 = wekws::fbank_dither_resident(f->fp, 4);
+  f->resident_dither_i16 = wekws::fbank_dither_resident(f->fp, 2);
   *out = f;
   return WEKWS_HIP_OK;
 }

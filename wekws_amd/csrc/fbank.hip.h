@@ -33,6 +33,8 @@
 #include <cmath>
 #include <vector>
 
+#include "philox.hip.h"
+
 namespace wekws {
 
 constexpr int kFbankMaxBins = 128;
@@ -547,10 +549,20 @@ __device__ __forceinline__ void fbank_frames(const FbankLane<ROUNDS>& K, float* 
 // (the usual audio rates, not every integer rate), every bin count 1 .. 128 and the three transform lengths that frames of 65 .. 512
 // samples select, no bank without an empty filter has more than 128 slots (tests/test_fbank_matrix.py sweeps fbank_build_tables and
 // asserts it for those rates).  The instantiations stay for a rate outside that sample; no test runs them.
-template <int ROUNDS, typename S>
-__global__ __launch_bounds__(64 * kFbankWaves, ROUNDS == 2 ? 4 : 1) void fbank_kernel(const FbankParams P, const S* __restrict__ pcm,
-                                                                 int B, int nsamp, int nframes,
-                                                                 float* __restrict__ feats) {
+//
+// DITHER (compile time; the instantiations live in fbank_dither.hip): the fetch adds dither * N(0, 1) to every sample INSIDE the frame,
+// where the reference adds it (after framing, before the DC removal: fbank.h:150-153) -- the draw of (seed, row id, frame, sample) as
+// philox.hip.h defines it, made in registers while the frame's loads fly.  Samples past frame_length stay zero: fbank_frames relies
+// on it.  Without DITHER the body is the kernel it was, operation for operation (DESIGN.md 3.17 says what its disassembly differs in).
+struct FbankDither {
+  float dither;        // standard deviation, int16 scale
+  uint64_t seed;
+  int64_t first_row;   // row b of the call is row id first_row + b
+};
+
+template <int ROUNDS, typename S, bool DITHER>
+__device__ __forceinline__ void fbank_kernel_body(const FbankParams P, const S* __restrict__ pcm, int B, int nsamp, int nframes,
+                                                  float* __restrict__ feats, const FbankDither D) {
   constexpr int FW = kFbankFW;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -608,6 +620,26 @@ __global__ __launch_bounds__(64 * kFbankWaves, ROUNDS == 2 ? 4 : 1) void fbank_k
           vn[w][m] = v;
         }
       }
+      if constexpr (DITHER) {
+        PhiloxDither G;
+        G.init(D.seed);
+        const int64_t row = D.first_row + b;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          if (256 * j < FL) {                                 // (uniform: frames of up to 256 samples draw one block per lane)
+            float2 z[2];
+            G.block(lane + 128 * j, fr, row, z[0], z[1]);     // the pairs m = 2 j and 2 j + 1 of this lane
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              const int m = 2 * j + h, i = 2 * (lane + 64 * m);
+              const float x = fmaf(D.dither, z[h].x, vn[w][m].x);
+              const float y = fmaf(D.dither, z[h].y, vn[w][m].y);
+              vn[w][m].x = (live && i < FL) ? x : vn[w][m].x;
+              vn[w][m].y = (live && i + 1 < FL) ? y : vn[w][m].y;
+            }
+          }
+        }
+      }
     }
   };
   fetch(ub, ufr);
@@ -625,6 +657,25 @@ __global__ __launch_bounds__(64 * kFbankWaves, ROUNDS == 2 ? 4 : 1) void fbank_k
                              });
     ub = nb; ufr = nfr;
   }
+}
+
+template <int ROUNDS, typename S>
+__global__ __launch_bounds__(64 * kFbankWaves, ROUNDS == 2 ? 4 : 1) void fbank_kernel(const FbankParams P, const S* __restrict__ pcm,
+                                                                 int B, int nsamp, int nframes,
+                                                                 float* __restrict__ feats) {
+  fbank_kernel_body<ROUNDS, S, false>(P, pcm, B, nsamp, nframes, feats, FbankDither{});
+}
+
+// ROUNDS == 2 with DITHER: capped at 128 registers like the plain kernel, at 76 / 100 bytes of scratch (float / int16); 3 lifts the
+// cap (146 / 149 registers, three waves per SIMD, no scratch).  Measured both ways, neither wins on both sample types: DESIGN.md 3.17.
+#ifndef WEKWS_FBANK_DITHER_R2_GROUPS
+#define WEKWS_FBANK_DITHER_R2_GROUPS 4
+#endif
+template <int ROUNDS, typename S>
+__global__ __launch_bounds__(64 * kFbankWaves, ROUNDS == 2 ? WEKWS_FBANK_DITHER_R2_GROUPS : 1) void fbank_dither_kernel(const FbankParams P, const S* __restrict__ pcm,
+                                                                 int B, int nsamp, int nframes,
+                                                                 float* __restrict__ feats, const FbankDither D) {
+  fbank_kernel_body<ROUNDS, S, true>(P, pcm, B, nsamp, nframes, feats, D);
 }
 
 // persistent waves: exactly one resident round (a second, partly filled round costs a whole wave lifetime).  The number
@@ -652,6 +703,8 @@ inline int64_t fbank_grid(int64_t total, int resident) {
 // what the last launch of this thread was given and chose -- rounds, sample size, pair_ok, grid, resident, B, nsamp, nframes (read by
 // the test library's wekws_hip_debug_fbank_last).  Defined in fbank.hip, the one unit that calls launch_fbank.
 __attribute__((visibility("hidden"))) int* fbank_last_launch();
+// workgroups of one resident round of the dithered kernel for samples of sample_bytes (fbank_dither.hip, the unit that instantiates it)
+__attribute__((visibility("hidden"))) int fbank_dither_resident(const FbankParams& P, int sample_bytes);
 
 template <typename S>
 inline int launch_fbank(const FbankParams& P, const S* pcm, int B, int nsamp, int nframes, float* feats, int resident,

@@ -87,6 +87,7 @@ struct wekws_hip_fbank {
   int device = 0;
   float* d_tables = nullptr;
   int resident_f32 = 0, resident_i16 = 0;   // workgroups of one resident round, per sample type (fbank.hip.h)
+  int resident_dither_f32 = 0, resident_dither_i16 = 0;   // ... of the dithered kernels (fbank_dither.hip)
 };
 
 // ---- model.hip

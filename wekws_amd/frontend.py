@@ -18,10 +18,18 @@ WINDOWS = dict(hamming=0, povey=1)
 
 class Fbank:
     """feats = Fbank(num_bins=40)(pcm)  with pcm (B, nsamp) float32 in int16 scale on a ROCm device
-    (the runtime never divides by 32768: runtime/core/frontend/wav.h:98-102) -> (B, frames, num_bins)."""
+    (the runtime never divides by 32768: runtime/core/frontend/wav.h:98-102) -> (B, frames, num_bins).
+
+    ``dither`` > 0: the training recipes' ``dither: 1.0`` (wekws/dataset/processor.py:134-203) -- ``frame[i] += dither * N(0, 1)``
+    after framing, before DC removal, drawn inside the kernel.  The draw at (``seed``, row id, frame, sample) is a pure function
+    of those four numbers; row b of a call has row id ``first_row + b``, by default the object's own row counter, which advances
+    by B per call (``reset_rows`` sets it): a data set cut into batches in any way gets the same noise per utterance.
+
+        fb = Fbank(80, window="povey", dither=1.0, seed=777)
+        feats = fb(pcm)                         # rows 0 .. B-1; the next call continues at B"""
 
     def __init__(self, num_bins: int = 40, sample_rate: int = 16000, frame_length: Optional[int] = None,
-                 frame_shift: Optional[int] = None, window: str = "hamming", device="cuda"):
+                 frame_shift: Optional[int] = None, window: str = "hamming", device="cuda", dither: float = 0.0, seed: int = 0):
         # FeaturePipelineConfig: 25 ms window, 10 ms shift (feature_pipeline.h:34-39)
         self.num_bins = num_bins
         self.sample_rate = sample_rate
@@ -29,6 +37,9 @@ class Fbank:
         self.frame_shift = frame_shift if frame_shift is not None else sample_rate // 1000 * 10
         if window not in WINDOWS:
             raise ValueError(f"window must be one of {sorted(WINDOWS)}")
+        self.dither, self.seed, self.next_row = float(dither), int(seed), 0
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must be an unsigned 64-bit integer")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("wekws_amd.frontend.Fbank runs on the MI355X HIP path only (no CPU fallback)")
@@ -52,20 +63,34 @@ class Fbank:
     def num_frames(self, nsamp: int) -> int:
         return int(self._lib.wekws_hip_fbank_num_frames(self._ptr, int(nsamp)))
 
-    def __call__(self, pcm: torch.Tensor) -> torch.Tensor:
+    def reset_rows(self, n: int = 0) -> None:
+        """The row id the next call without ``first_row`` starts at."""
+        self.next_row = int(n)
+
+    def __call__(self, pcm: torch.Tensor, first_row: Optional[int] = None) -> torch.Tensor:
         """(B, nsamp) PCM on a ROCm device -> (B, frames, num_bins) log-mel.  float32 in int16 scale (wav.h:98-102), or
         int16 as FeaturePipeline::AcceptWaveform(std::vector<int16_t>) receives it (feature_pipeline.cc:49-55): widened
-        in the kernel's registers -- 2 bytes per sample over PCIe and HBM, the same features bit for bit."""
+        in the kernel's registers -- 2 bytes per sample over PCIe and HBM, the same features bit for bit.
+        ``first_row``: the row id of row 0 for the dither's draws (default: the object's counter, advanced by B)."""
         if pcm.dim() != 2 or not pcm.is_cuda or pcm.dtype not in (torch.float32, torch.int16):
             raise ValueError("pcm must be a (B, nsamp) float32 or int16 tensor on a ROCm device")
         pcm = pcm.contiguous()
         B, n = int(pcm.size(0)), int(pcm.size(1))
         nf = self.num_frames(n)
         feats = torch.empty((B, nf, self.num_bins), dtype=torch.float32, device=pcm.device)
+        row0 = self.next_row if first_row is None else int(first_row)
         if B and nf:
             stream = torch.cuda.current_stream(pcm.device).cuda_stream
-            fn = self._lib.wekws_hip_fbank_compute if pcm.dtype == torch.float32 else self._lib.wekws_hip_fbank_compute_i16
-            _capi.check(fn(self._ptr, pcm.data_ptr(), B, n, feats.data_ptr(), ctypes.c_void_p(stream)), "wekws_hip_fbank_compute")
+            if self.dither == 0.0:
+                fn = self._lib.wekws_hip_fbank_compute if pcm.dtype == torch.float32 else self._lib.wekws_hip_fbank_compute_i16
+                _capi.check(fn(self._ptr, pcm.data_ptr(), B, n, feats.data_ptr(), ctypes.c_void_p(stream)), "wekws_hip_fbank_compute")
+            else:
+                fn = self._lib.wekws_hip_fbank_compute_dither if pcm.dtype == torch.float32 else \
+                    self._lib.wekws_hip_fbank_compute_dither_i16
+                _capi.check(fn(self._ptr, pcm.data_ptr(), B, n, feats.data_ptr(), self.dither, self.seed, row0,
+                               ctypes.c_void_p(stream)), "wekws_hip_fbank_compute_dither")
+        if first_row is None:
+            self.next_row = row0 + B
         return feats
 
     def leftover(self, nsamp: int) -> Tuple[int, int]:
@@ -111,6 +136,21 @@ def frame_skip(feats: torch.Tensor, skip_rate: int = 1) -> torch.Tensor:
     return splice_skip(feats, 0, 0, skip_rate)
 
 
+def dither_noise(seed: int, first_row: int, B: int, nframes: int, frame_length: int, device="cuda") -> torch.Tensor:
+    """The (B, nframes, frame_length) unit-variance normal field that ``Fbank(dither=d, seed=seed)`` scales by d and adds to the
+    frames of rows ``first_row .. first_row + B - 1`` (wekws_hip_dither_noise; the definition: csrc/philox.hip.h)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("wekws_amd.frontend.dither_noise runs on the MI355X HIP path only (no CPU fallback)")
+    lib = _capi.load()
+    with torch.cuda.device(device):
+        out = torch.empty((int(B), int(nframes), int(frame_length)), dtype=torch.float32, device=device)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        _capi.check(lib.wekws_hip_dither_noise(int(seed), int(first_row), int(B), int(nframes), int(frame_length),
+                                               out.data_ptr() if out.numel() else None, ctypes.c_void_p(stream)), "wekws_hip_dither_noise")
+    return out
+
+
 def dct_lifter(logmel: torch.Tensor, num_ceps: int, cepstral_lifter: float = 22.0) -> torch.Tensor:
     """The MFCC tail of torchaudio.compliance.kaldi.mfcc (DCT-II 'ortho' with Kaldi's first column, first ``num_ceps``
     cepstra, cepstral lifter) on (..., num_mel_bins) log-mel rows -> (..., num_ceps); wekws_hip_dct_lifter."""
@@ -131,17 +171,21 @@ class Mfcc:
     """``kaldi.mfcc(waveform * (1 << 15), num_ceps, num_mel_bins, frame_length, frame_shift, energy_floor=0.0,
     sample_frequency)`` of the reference's MDTC recipes (wekws/dataset/processor.py:134-169) on the device: Povey-window
     fbank (wekws_hip_fbank_*) followed by the DCT / lifter kernel.  ``pcm`` is (B, nsamp) float32 already in int16 scale.
+    ``dither`` / ``seed`` / ``first_row`` / ``reset_rows``: as for ``Fbank`` (the recipes' ``mfcc_conf`` sets ``dither: 1.0``).
     Parity with torchaudio is unpinned (see oracle/kaldi_feats_oracle.py)."""
 
     def __init__(self, num_ceps: int = 80, num_mel_bins: int = 80, sample_rate: int = 16000, cepstral_lifter: float = 22.0,
-                 device="cuda"):
+                 device="cuda", dither: float = 0.0, seed: int = 0):
         if not 0 < num_ceps <= num_mel_bins:
             raise ValueError("need 0 < num_ceps <= num_mel_bins")
         self.num_ceps, self.cepstral_lifter = int(num_ceps), float(cepstral_lifter)
-        self.fbank = Fbank(num_mel_bins, sample_rate, window="povey", device=device)
+        self.fbank = Fbank(num_mel_bins, sample_rate, window="povey", device=device, dither=dither, seed=seed)
 
-    def __call__(self, pcm: torch.Tensor) -> torch.Tensor:
-        return dct_lifter(self.fbank(pcm), self.num_ceps, self.cepstral_lifter)
+    def reset_rows(self, n: int = 0) -> None:
+        self.fbank.reset_rows(n)
+
+    def __call__(self, pcm: torch.Tensor, first_row: Optional[int] = None) -> torch.Tensor:
+        return dct_lifter(self.fbank(pcm, first_row), self.num_ceps, self.cepstral_lifter)
 
 
 class StreamingFrontEnd:
