@@ -794,6 +794,53 @@ int wekws_hip_resample_reset(void* h, const int32_t* ids, int n);
 int wekws_hip_resample_counts(void* h, int id, int64_t counts_out[4]);
 
 /* -------------------------------------------------------------------------------------------
+ * Rate bank  --  the resampler for rows and streams of DIFFERENT source rates in one launch.  The reference's `resample` step is
+ * per utterance (wekws/dataset/processor.py:94-103: every sample carries its own sample_rate), so a batch may mix 8 kHz
+ * telephony, 16 kHz devices and 44.1 / 48 kHz browser audio.  A bank holds up to WEKWS_HIP_RESAMPLE_BANK_MAX source rates
+ * ("members", indexed in the order given) and one target rate; each row of a one-shot call names its member, each stream of a
+ * streaming handle is assigned one.  A member is the resampler of its pair as defined above, with the bank's
+ * lowpass_filter_width and rolloff; a member equal to the target copies.  A row's output equals the single-rate handle's for that
+ * rate bit for bit.  One launch serves all rows: the (row, tile) list the workgroups walk is ordered by member and every
+ * workgroup walks one contiguous span of it, reloading its tap table only where the member changes.
+ * ------------------------------------------------------------------------------------------*/
+#define WEKWS_HIP_RESAMPLE_BANK_MAX 16
+/*
+ * cfg as for wekws_hip_resample_create (max_streams == 0: one-shot only); orig_freqs (num_rates) HOST int32, the members;
+ * cfg->orig_freq must equal orig_freqs[0].  WEKWS_HIP_EINVAL for an empty bank, more than WEKWS_HIP_RESAMPLE_BANK_MAX members, a
+ * repeated rate or a rate <= 0; WEKWS_HIP_EUNSUPPORTED, with a message that names the member, for a member whose table does
+ * not fit the LDS budget.  The LDS of a launch, the history capacity of a stream and max_out are the largest member's.
+ */
+int wekws_hip_resample_bank_create(const wekws_hip_resample_cfg* cfg, const int32_t* orig_freqs, int num_rates, void** out);
+void wekws_hip_resample_bank_destroy(void* h);
+/*
+ * One-shot, as wekws_hip_resample_compute;  member_of_row (B) HOST int32 indices into the bank: row b receives its
+ * wekws_hip_resample_num_samples(orig_freqs[member_of_row[b]], new, nsamp[b]) samples and zeros behind them.  Refusals as for
+ * the single-rate call, plus a member index out of range: WEKWS_HIP_EINVAL, nothing launched.  The row table travels through
+ * the same kind of ring of pinned tables.
+ */
+int wekws_hip_resample_bank_compute(void* h, const float* pcm, int B, int nmax, const int32_t* nsamp, const int32_t* member_of_row,
+                                    void* out, int mcap, void* stream);
+int wekws_hip_resample_bank_compute_i16(void* h, const int16_t* pcm, int B, int nmax, const int32_t* nsamp,
+                                        const int32_t* member_of_row, void* out, int mcap, void* stream);
+/*
+ * The n streams in ids (HOST int32) use member `member` from now on and start over: nothing received, nothing kept, not
+ * flushed.  A bad id or member is refused and changes no stream.  Streams start on member 0.
+ */
+int wekws_hip_resample_bank_set_rate(void* h, const int32_t* ids, int n, int member);
+/* The source rate in Hz of stream id's member; WEKWS_HIP_EINVAL for a bad id. */
+int wekws_hip_resample_bank_rate_of(void* h, int id);
+/*
+ * Streaming: the contracts of wekws_hip_resample_push, _max_out, _reset and _counts, every row planned with its stream's
+ * member.  The whole call is planned on the host first, a refused call launches nothing and changes no stream, and a push is one
+ * launch whatever the members of its rows.  nmax counts input samples at whatever rate; _max_out is the largest member's.
+ */
+int wekws_hip_resample_bank_push(void* h, const int16_t* pcm, int B, int nmax, const int32_t* stream_ids, const int32_t* nsamp,
+                                 int flush, void* out, int mcap, int32_t* counts, void* stream);
+int wekws_hip_resample_bank_max_out(void* h, int nmax, int flush);
+int wekws_hip_resample_bank_reset(void* h, const int32_t* ids, int n);
+int wekws_hip_resample_bank_counts(void* h, int id, int64_t counts_out[4]);
+
+/* -------------------------------------------------------------------------------------------
  * Augmentation  --  add_reverb, add_noise and spec_aug of the data pipeline (wekws/dataset/processor.py:374-392, 395-430,
  * 206-240) on the device, between the resampler and the front end.  What is drawn at random (whether a row is augmented, which
  * RIR or noise, where the noise starts, the SNR, the masks) is drawn by the caller and passed in HOST tables; every call checks

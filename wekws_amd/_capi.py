@@ -144,6 +144,19 @@ SIGNATURES = {
     "wekws_hip_resample_max_out": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "wekws_hip_resample_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "wekws_hip_resample_counts": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
+    "wekws_hip_resample_bank_create": (C.c_int, [C.POINTER(ResampleCfg), C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "wekws_hip_resample_bank_destroy": (None, [C.c_void_p]),
+    "wekws_hip_resample_bank_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                  C.c_void_p]),
+    "wekws_hip_resample_bank_compute_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_int, C.c_void_p]),
+    "wekws_hip_resample_bank_set_rate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "wekws_hip_resample_bank_rate_of": (C.c_int, [C.c_void_p, C.c_int]),
+    "wekws_hip_resample_bank_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_int, C.c_void_p, C.c_void_p]),
+    "wekws_hip_resample_bank_max_out": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "wekws_hip_resample_bank_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "wekws_hip_resample_bank_counts": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
     "wekws_hip_threshold_kws_create": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "wekws_hip_threshold_kws_destroy": (None, [C.c_void_p]),
     "wekws_hip_threshold_kws_max_hits": (C.c_int, [C.c_void_p, C.c_int]),

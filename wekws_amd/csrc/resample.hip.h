@@ -34,10 +34,7 @@
 
 namespace wekws {
 
-constexpr int kResampleTile = 256;            // outputs of a tile = lanes of a workgroup
 constexpr int kResampleRing = 4;              // plan tables in flight (resample.hip)
-constexpr int kResampleLdsBudget = 64 * 1024; // live table + live ranges + input tile
-constexpr int kResampleVec = 8;               // samples of the widest 16-byte group (int16)
 
 struct ResampleRow {        // what the kernel knows about one row (12 x int32); positions are relative to the row's origin:
                             // sample 0 of an utterance, the first kept sample of a stream
@@ -48,7 +45,8 @@ struct ResampleRow {        // what the kernel knows about one row (12 x int32);
   int32_t hi_valid;         // end of the samples there are (zeros beyond, and before 0)
   int32_t hist_old, hist_new;   // sample offsets of the stream's history buffers (read / written)
   int32_t keep_from, keep_cnt;  // positions [keep_from, keep_from + keep_cnt) become the new history
-  int32_t reserved[3];
+  int32_t member, row;          // rate bank alone (resample_bank.hip.h): the row's plan, and its place in x and y
+  int32_t reserved;
 };
 
 struct ResampleParams {
@@ -62,21 +60,6 @@ struct ResampleParams {
   const int32_t* count;     // (n) live taps of every phase
   const float* full;        // (n, K)
 };
-
-// j-blocks that 256 consecutive outputs touch at most
-inline int resample_jspan(int n) { return (n + kResampleTile - 2) / n + 1; }
-inline int resample_stride(int max_live) { return max_live | 1; }
-inline int64_t resample_tile_cap(const ResamplePlan& p) {
-  const int64_t c = int64_t(resample_jspan(p.n)) * p.o + 2 * int64_t(p.width) + kResampleVec;
-  return (c + kResampleVec - 1) / kResampleVec * kResampleVec;
-}
-// LDS bytes of a launch with float samples (the larger of the two source types); tile_off if given
-inline int64_t resample_lds_bytes(const ResamplePlan& p, int64_t* tile_off = nullptr) {
-  int64_t table = (int64_t(p.n) * resample_stride(p.max_live) + 2 * int64_t(p.n)) * 4;
-  table = (table + 15) / 16 * 16;
-  if (tile_off) *tile_off = table;
-  return table + resample_tile_cap(p) * 4;
-}
 
 // One output sample: the live taps of its phase, ascending, fmaf from 0.  taps: the phase's row of the live table; x: the sample
 // under the first live tap.
@@ -107,76 +90,102 @@ __device__ __forceinline__ Out resample_out(float v) {
 
 __device__ __forceinline__ int resample_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
+// The LDS of a workgroup under the plan P: the live table, the live ranges, the input tile.
+template <typename In>
+struct ResampleLds {
+  float* taps;
+  int* first;
+  int* count;
+  In* tile;
+  __device__ __forceinline__ ResampleLds(unsigned char* lds, const ResampleParams& P)
+      : taps(reinterpret_cast<float*>(lds)), first(reinterpret_cast<int*>(taps + P.n * P.stride)), count(first + P.n),
+        tile(reinterpret_cast<In*>(lds + P.tile_off)) {}
+};
+
+// the live table and the live ranges of P into LDS (the caller's barrier follows)
+template <typename In>
+__device__ __forceinline__ void resample_load_table(const ResampleParams& P, const ResampleLds<In>& S) {
+  const int tid = threadIdx.x;
+  for (int e = tid; e < P.n * P.stride; e += kResampleTile) S.taps[e] = P.live[e];
+  for (int e = tid; e < P.n; e += kResampleTile) { S.first[e] = P.first[e]; S.count[e] = P.count[e]; }
+}
+
+// Tile tl of row R, by the whole workgroup: the history write-back (tile 0), the staging, one output per lane.  chunk / yrow: the
+// row's input and output.  Ends behind a barrier, so the next tile may overwrite the samples (and the table).
+template <typename In, typename Out>
+__device__ __forceinline__ void resample_tile(const ResampleParams& P, const ResampleLds<In>& S, const ResampleRow& R,
+                                              const In* __restrict__ chunk, In* hist, Out* __restrict__ yrow, int mcap, int tl) {
+  constexpr int V = 16 / int(sizeof(In));
+  constexpr bool kFloatIn = std::is_same<In, float>::value;
+  const float* const taps = S.taps;
+  const int* const first = S.first;
+  const int* const count = S.count;
+  In* const tile = S.tile;
+  const int tid = threadIdx.x;
+  const int r0 = tl * kResampleTile, r = r0 + tid;
+  if (tl == 0)
+    for (int e = tid; e < R.keep_cnt; e += kResampleTile) hist[R.hist_new + e] = resample_fetch(R, hist, chunk, R.keep_from + e);
+  if (r0 >= R.cnt) {                                           // (the whole workgroup: a tile past the row's count is zeros)
+    if (r < mcap) yrow[r] = Out(0);
+    return;
+  }
+  // ---- the samples under the full windows of the tile's outputs, from position tile_lo on
+  const int jt0 = (R.i0 + r0) / P.n;
+  int tile_lo = R.base_rel + jt0 * P.o;
+  const int64_t src = int64_t(reinterpret_cast<uintptr_t>(chunk) / sizeof(In)) + (tile_lo - R.h);
+  const int a = int(((src % V) + V) % V);                      // down to a 16-byte boundary of the chunk
+  tile_lo -= a;
+  int bad = 0;
+  for (int g = tid; g < P.tile_cap / V; g += kResampleTile) {
+    const int rel = tile_lo + g * V;
+    if (rel >= 0 && rel >= R.h && rel + V <= R.hi_valid) {
+      const uint4 v = *reinterpret_cast<const uint4*>(chunk + (rel - R.h));
+      *reinterpret_cast<uint4*>(tile + g * V) = v;
+      if constexpr (kFloatIn)
+        bad |= resample_nonfinite(__uint_as_float(v.x)) | resample_nonfinite(__uint_as_float(v.y)) |
+               resample_nonfinite(__uint_as_float(v.z)) | resample_nonfinite(__uint_as_float(v.w));
+    } else {
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        const In s = resample_fetch(R, hist, chunk, rel + k);
+        tile[g * V + k] = s;
+        if constexpr (kFloatIn) bad |= resample_nonfinite(s);
+      }
+    }
+  }
+  if constexpr (kFloatIn) bad = __syncthreads_or(bad);
+  else __syncthreads();
+  // ---- one output per lane
+  float acc = 0.f;
+  const bool live = r < R.cnt;
+  if (live) {
+    const int qq = R.i0 + r, jj = qq / P.n, i = qq - jj * P.n;
+    const In* const xs = tile + ((jj - jt0) * P.o + a);        // the sample under tap 0 of the output's block
+    if (kFloatIn && bad) {
+      const float* const k = P.full + int64_t(i) * P.K;
+      for (int m = 0; m < P.K; ++m) acc = fmaf(k[m], float(xs[m]), acc);
+    } else {
+      acc = resample_sample(taps + i * P.stride, count[i], xs + first[i]);
+    }
+  }
+  if (r < mcap) yrow[r] = live ? resample_out<Out>(acc) : Out(0);
+  __syncthreads();                                             // the next tile overwrites the samples
+}
+
 template <typename In, typename Out>
 __global__ __launch_bounds__(kResampleTile) void resample_kernel(const ResampleParams P, const ResampleRow* __restrict__ rows,
                                                                  const In* __restrict__ x, int64_t xstride, In* hist,
                                                                  Out* __restrict__ y, int mcap, int tiles_per_row,
                                                                  int64_t total_tiles) {
   extern __shared__ __attribute__((aligned(16))) unsigned char resample_lds[];
-  constexpr int V = 16 / int(sizeof(In));
-  constexpr bool kFloatIn = std::is_same<In, float>::value;
-  float* const taps = reinterpret_cast<float*>(resample_lds);
-  int* const first = reinterpret_cast<int*>(taps + P.n * P.stride);
-  int* const count = first + P.n;
-  In* const tile = reinterpret_cast<In*>(resample_lds + P.tile_off);
-  const int tid = threadIdx.x;
-  for (int e = tid; e < P.n * P.stride; e += kResampleTile) taps[e] = P.live[e];
-  for (int e = tid; e < P.n; e += kResampleTile) { first[e] = P.first[e]; count[e] = P.count[e]; }
+  const ResampleLds<In> S(resample_lds, P);
+  resample_load_table(P, S);
   __syncthreads();
 
   for (int64_t t = blockIdx.x; t < total_tiles; t += gridDim.x) {
     const int b = int(t / tiles_per_row), tl = int(t - int64_t(b) * tiles_per_row);
     const ResampleRow R = rows[b];
-    const In* const chunk = x + int64_t(b) * xstride;
-    Out* const yrow = y + int64_t(b) * mcap;
-    const int r0 = tl * kResampleTile, r = r0 + tid;
-    if (tl == 0)
-      for (int e = tid; e < R.keep_cnt; e += kResampleTile) hist[R.hist_new + e] = resample_fetch(R, hist, chunk, R.keep_from + e);
-    if (r0 >= R.cnt) {                                           // (the whole workgroup: a tile past the row's count is zeros)
-      if (r < mcap) yrow[r] = Out(0);
-      continue;
-    }
-    // ---- the samples under the full windows of the tile's outputs, from position tile_lo on
-    const int jt0 = (R.i0 + r0) / P.n;
-    int tile_lo = R.base_rel + jt0 * P.o;
-    const int64_t src = int64_t(reinterpret_cast<uintptr_t>(chunk) / sizeof(In)) + (tile_lo - R.h);
-    const int a = int(((src % V) + V) % V);                      // down to a 16-byte boundary of the chunk
-    tile_lo -= a;
-    int bad = 0;
-    for (int g = tid; g < P.tile_cap / V; g += kResampleTile) {
-      const int rel = tile_lo + g * V;
-      if (rel >= 0 && rel >= R.h && rel + V <= R.hi_valid) {
-        const uint4 v = *reinterpret_cast<const uint4*>(chunk + (rel - R.h));
-        *reinterpret_cast<uint4*>(tile + g * V) = v;
-        if constexpr (kFloatIn)
-          bad |= resample_nonfinite(__uint_as_float(v.x)) | resample_nonfinite(__uint_as_float(v.y)) |
-                 resample_nonfinite(__uint_as_float(v.z)) | resample_nonfinite(__uint_as_float(v.w));
-      } else {
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-          const In s = resample_fetch(R, hist, chunk, rel + k);
-          tile[g * V + k] = s;
-          if constexpr (kFloatIn) bad |= resample_nonfinite(s);
-        }
-      }
-    }
-    if constexpr (kFloatIn) bad = __syncthreads_or(bad);
-    else __syncthreads();
-    // ---- one output per lane
-    float acc = 0.f;
-    const bool live = r < R.cnt;
-    if (live) {
-      const int qq = R.i0 + r, jj = qq / P.n, i = qq - jj * P.n;
-      const In* const xs = tile + ((jj - jt0) * P.o + a);        // the sample under tap 0 of the output's block
-      if (kFloatIn && bad) {
-        const float* const k = P.full + int64_t(i) * P.K;
-        for (int m = 0; m < P.K; ++m) acc = fmaf(k[m], float(xs[m]), acc);
-      } else {
-        acc = resample_sample(taps + i * P.stride, count[i], xs + first[i]);
-      }
-    }
-    if (r < mcap) yrow[r] = live ? resample_out<Out>(acc) : Out(0);
-    __syncthreads();                                             // the next tile overwrites the samples
+    resample_tile<In, Out>(P, S, R, x + int64_t(b) * xstride, hist, y + int64_t(b) * mcap, mcap, tl);
   }
 }
 

@@ -1,0 +1,82 @@
+// The resampler for rows of DIFFERENT source rates in one launch: a rate bank (resample_bank_plan.h) of up to 16 members, each the
+// plan of one (orig, new) pair.  The arithmetic, the staging, the non-finite path and the history write-back are the single-rate
+// kernel's own device functions (resample.hip.h: resample_tile and what it calls), given the parameters of the row's member: a
+// row's output equals the single-rate kernel's for that rate bit for bit.
+//
+//   workgroup   256 lanes, one output per lane; persistent over ONE CONTIGUOUS SPAN of the (row, tile) list, which is ordered by
+//               member (resample_bank_plan.h states the order and the spans).
+//   table       the parameters of every member (ResampleParams: sizes, LDS offsets, table pointers) are a small device table.  The
+//               workgroup remembers which member's live table and live ranges its LDS holds; when its next tile is of another
+//               member it passes a barrier (other waves may still read the old table), reloads, and passes a second one.  A span
+//               changes member at most members - 1 times, and usually never.
+//   LDS         the layout of the loaded member, exactly as the single-rate kernel lays it out; the launch asks for the largest
+//               member's bytes.
+//   rows        the row table is uploaded in slot order (sorted by member); a row carries its member and its place in x and y.
+#pragma once
+#include "resample.hip.h"
+#include "resample_bank_plan.h"
+
+namespace wekws {
+
+template <typename In, typename Out>
+__global__ __launch_bounds__(kResampleTile) void resample_bank_kernel(const ResampleParams* __restrict__ members,
+                                                                      const ResampleRow* __restrict__ rows,
+                                                                      const In* __restrict__ x, int64_t xstride, In* hist,
+                                                                      Out* __restrict__ y, int mcap, int tiles_per_row,
+                                                                      int64_t total_tiles) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char resample_bank_lds[];
+  const int64_t t0 = resample_bank_span_begin(total_tiles, gridDim.x, blockIdx.x);
+  const int64_t t1 = resample_bank_span_begin(total_tiles, gridDim.x, int64_t(blockIdx.x) + 1);
+  int loaded = -1;
+  ResampleParams P{};
+  for (int64_t t = t0; t < t1; ++t) {
+    const ResampleRow R = rows[resample_bank_slot(t, tiles_per_row)];
+    if (R.member != loaded) {
+      __syncthreads();                                           // other waves may still read the old table
+      P = members[R.member];
+      resample_load_table(P, ResampleLds<In>(resample_bank_lds, P));
+      loaded = R.member;
+      __syncthreads();
+    }
+    resample_tile<In, Out>(P, ResampleLds<In>(resample_bank_lds, P), R, x + int64_t(R.row) * xstride, hist,
+                           y + int64_t(R.row) * mcap, mcap, resample_bank_tile(t, tiles_per_row));
+  }
+}
+
+int launch_resample_bank(const ResampleParams* members, size_t lds, int in_i16, int out_i16, const ResampleRow* rows, const void* x,
+                         int64_t xstride, int16_t* hist, void* y, int B, int mcap, int max_grid, hipStream_t stream);
+
+}  // namespace wekws
+
+// the handle of wekws_hip_resample_bank_* (resample_bank.hip; the hooks unit caps its grid and rounds a member's tables)
+struct wekws_hip_resample_bank {
+  int device = 0;
+  wekws::ResampleBankPlan bank;
+  std::vector<int32_t> rates;                      // orig_freq of every member
+  std::vector<wekws::ResampleParams> P;            // of every member, as the device table holds them
+  wekws::ResampleParams* d_params = nullptr;
+  size_t lds = 0;
+  int out_i16 = 0, max_streams = 0, max_chunk = 0, hist_cap = 0, max_grid = 1, default_grid = 1;
+  std::vector<float*> d_live, d_full;              // per member
+  std::vector<int32_t*> d_meta;                    // per member: first (n) | count (n)
+  int16_t* hist = nullptr;                         // (max_streams, 2, hist_cap), ping-ponged per stream
+  // the row table of a call travels through a ring of pinned host tables with device twins, as the single-rate handle's does;
+  // a slot too small for a one-shot call is replaced (a push never has more rows than streams)
+  struct Slot {
+    wekws::ResampleRow* h = nullptr;
+    wekws::ResampleRow* d = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+    bool used = false;
+  };
+  Slot ring[wekws::kResampleRing];
+  int next = 0;
+  std::mutex mu;
+  // per-stream state lives on the host: the outputs of every row are known without a device read-back
+  std::vector<int64_t> received, emitted, origin;
+  std::vector<int32_t> par, seen, flushed, member;
+  int32_t epoch = 0;
+  std::vector<wekws::ResampleStep> steps;          // of the push being planned
+  std::vector<wekws::ResampleRow> table;           // of the call being planned, in row order
+  std::vector<int32_t> members_of, order;          // of the call being planned: member of every row, rows sorted by member
+};

@@ -160,4 +160,25 @@ inline int64_t resample_max_out(const ResamplePlan& p, int64_t nmax, int flush) 
   return (in * p.n + p.o - 1) / p.o + 2;
 }
 
+// ---- what the kernel's launch is sized with (resample.hip.h); host arithmetic, stated here so that a plan of several rates
+// (resample_bank_plan.h) can take its maxima without a device header
+constexpr int kResampleTile = 256;            // outputs of a tile = lanes of a workgroup
+constexpr int kResampleLdsBudget = 64 * 1024; // live table + live ranges + input tile
+constexpr int kResampleVec = 8;               // samples of the widest 16-byte group (int16)
+
+// j-blocks that 256 consecutive outputs touch at most
+inline int resample_jspan(int n) { return (n + kResampleTile - 2) / n + 1; }
+inline int resample_stride(int max_live) { return max_live | 1; }
+inline int64_t resample_tile_cap(const ResamplePlan& p) {
+  const int64_t c = int64_t(resample_jspan(p.n)) * p.o + 2 * int64_t(p.width) + kResampleVec;
+  return (c + kResampleVec - 1) / kResampleVec * kResampleVec;
+}
+// LDS bytes of a launch with float samples (the larger of the two source types); tile_off if given
+inline int64_t resample_lds_bytes(const ResamplePlan& p, int64_t* tile_off = nullptr) {
+  int64_t table = (int64_t(p.n) * resample_stride(p.max_live) + 2 * int64_t(p.n)) * 4;
+  table = (table + 15) / 16 * 16;
+  if (tile_off) *tile_off = table;
+  return table + resample_tile_cap(p) * 4;
+}
+
 }  // namespace wekws

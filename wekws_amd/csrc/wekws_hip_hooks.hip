@@ -2,7 +2,7 @@
 // libwekws_hip.so: the sinks are empty, the unit exports nothing and holds no kernel.  libwekws_hip_hooks.so (make hooks: this unit
 // compiled with -DWEKWS_TEST_HOOKS, every other object shared with the product library): the sinks record, and the unit carries the test
 // hooks: the route trace of a forward, the routing functions of route.h and the blob layout of blob_layout.h without a device, the GRU
-// epoch, a CU hog, the fbank's plan and table, the row softmax on chosen logits, the resampler's taps and plan, the CTC decoder's keyword-set table.  Not part of the ABI in include/wekws_hip.h.
+// epoch, a CU hog, the fbank's plan and table, the row softmax on chosen logits, the resampler's taps and plan (a rate bank's too), the CTC decoder's keyword-set table.  Not part of the ABI in include/wekws_hip.h.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -12,6 +12,7 @@
 #include "mdtc64_stream.hip.h"
 #include "ctc_kws_sets.h"
 #include "resample.hip.h"
+#include "resample_bank.hip.h"
 
 #ifndef WEKWS_TEST_HOOKS
 void trace_reset(int) {}
@@ -413,6 +414,68 @@ extern "C" int wekws_hip_debug_resample_round_taps_f16(wekws_hip_resample* r) {
   if (e == hipSuccess) e = hipMemcpy(r->d_full, full.data(), full.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "resample taps: %s", hipGetErrorString(e));
+  return WEKWS_HIP_OK;
+}
+
+// --------------------------------------------- resample bank ---------------------------------------------
+// The plan of a rate bank, WITHOUT a device (resample_bank_plan.h alone).  dims[4]: LDS bytes of a launch, history capacity of a stream,
+// max_out(nmax, flush), members.  With member_of_row (B) also the tile order of a launch over B rows of tiles_per_row tiles by `grid`
+// workgroups: list_row / list_tile (B tiles_per_row) the (row, tile) of every list entry, span_begin (grid + 1) the first entry of every
+// workgroup and the end of the list.  Returns 0, WEKWS_HIP_EINVAL for a bank no resampler has or a member index outside it,
+// WEKWS_HIP_EUNSUPPORTED for a member that does not fit (*bad_member says which).
+extern "C" int wekws_hip_debug_resample_bank_plan(const int32_t* rates, int num, int neu, int lpw, double rolloff, int nmax, int flush,
+                                                  int64_t* dims, int* bad_member, const int32_t* member_of_row, int B, int tiles_per_row,
+                                                  int grid, int32_t* list_row, int32_t* list_tile, int64_t* span_begin) {
+  if (!dims || nmax < 0) return WEKWS_HIP_EINVAL;
+  wekws::ResampleBankPlan bp;
+  int bad = -1;
+  const wekws::ResampleBankRefusal r = wekws::resample_bank_plan(rates, num, neu, lpw, rolloff, &bp, &bad);
+  if (bad_member) *bad_member = bad;
+  if (r == wekws::kResampleBankLds) return WEKWS_HIP_EUNSUPPORTED;
+  if (r != wekws::kResampleBankOk) return WEKWS_HIP_EINVAL;
+  dims[0] = wekws::resample_bank_lds_bytes(bp); dims[1] = wekws::resample_bank_hist_cap(bp);
+  dims[2] = wekws::resample_bank_max_out(bp, nmax, flush); dims[3] = int64_t(bp.members.size());
+  if (!member_of_row) return WEKWS_HIP_OK;
+  if (B < 0 || tiles_per_row < 1 || grid < 1 || !list_row || !list_tile || !span_begin) return WEKWS_HIP_EINVAL;
+  for (int b = 0; b < B; ++b)
+    if (member_of_row[b] < 0 || member_of_row[b] >= num) return WEKWS_HIP_EINVAL;
+  std::vector<int32_t> order(size_t(B) + 1);
+  wekws::resample_bank_order(member_of_row, B, num, order.data());
+  const int64_t total = wekws::resample_bank_total(B, tiles_per_row);
+  for (int64_t t = 0; t < total; ++t) {
+    list_row[t] = order[size_t(wekws::resample_bank_slot(t, tiles_per_row))];
+    list_tile[t] = wekws::resample_bank_tile(t, tiles_per_row);
+  }
+  for (int w = 0; w <= grid; ++w) span_begin[w] = wekws::resample_bank_span_begin(total, grid, w);
+  return WEKWS_HIP_OK;
+}
+// Cap the grid of the handle's launches (max_grid <= 0: the handle's own again), so that a small batch makes one workgroup walk tiles of
+// several members.
+extern "C" int wekws_hip_debug_resample_bank_set_grid(wekws_hip_resample_bank* r, int max_grid) {
+  if (!r) return fail(WEKWS_HIP_EINVAL, "NULL handle");
+  std::lock_guard<std::mutex> lk(r->mu);
+  r->max_grid = max_grid > 0 ? max_grid : r->default_grid;
+  return WEKWS_HIP_OK;
+}
+// wekws_hip_debug_resample_round_taps_f16 for ONE member of a bank: its live table and its full one, in place, same sizes.
+extern "C" int wekws_hip_debug_resample_bank_round_taps_f16(wekws_hip_resample_bank* r, int member) {
+  if (!r) return fail(WEKWS_HIP_EINVAL, "NULL handle");
+  if (member < 0 || member >= int(r->P.size())) return fail(WEKWS_HIP_EINVAL, "member %d outside 0..%d", member, int(r->P.size()) - 1);
+  DeviceGuard guard(r->device);
+  if (!guard.ok) return fail(WEKWS_HIP_EDEVICE, "hipSetDevice(%d)", r->device);
+  const wekws::ResampleParams& P = r->P[size_t(member)];
+  float* const d_live = r->d_live[size_t(member)];
+  float* const d_full = r->d_full[size_t(member)];
+  std::vector<float> live(size_t(P.n) * P.stride), full(size_t(P.n) * P.K);
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(live.data(), d_live, live.size() * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(full.data(), d_full, full.size() * sizeof(float), hipMemcpyDeviceToHost);
+  for (float& v : live) v = float(_Float16(v));
+  for (float& v : full) v = float(_Float16(v));
+  if (e == hipSuccess) e = hipMemcpy(d_live, live.data(), live.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_full, full.data(), full.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "resample bank taps: %s", hipGetErrorString(e));
   return WEKWS_HIP_OK;
 }
 

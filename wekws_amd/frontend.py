@@ -2,7 +2,8 @@
 runtime/core/frontend/fbank.h:138-198, behind ``FeaturePipeline::AcceptWaveform``'s framing rule,
 runtime/core/frontend/feature_pipeline.cc:30-47) and the context-expansion / frame-skip step of the data pipeline
 (wekws/dataset/init_dataset.py:24-68), and in front of both the `resample` step (wekws/dataset/processor.py:83-103).  Thin
-host wrappers over the C ABI (wekws_hip_fbank_*, wekws_hip_splice, wekws_hip_resample_*); no CPU fallback."""
+host wrappers over the C ABI (wekws_hip_fbank_*, wekws_hip_splice, wekws_hip_resample_*, wekws_hip_resample_bank_*); no CPU
+fallback."""
 from __future__ import annotations
 
 import ctypes
@@ -393,10 +394,14 @@ class StreamingResampler:
         self._lib, self._ptr, self.device = _resample_handle(orig_freq, new_freq, out_dtype, num_streams, max_chunk, device)
 
     __del__ = Resample.__del__
+    _ABI = "wekws_hip_resample_"                # the entry points the methods below call: _push, _max_out, _reset, _counts
+
+    def _fn(self, name):
+        return getattr(self._lib, self._ABI + name)
 
     def max_out(self, nmax: int, flush: bool = False) -> int:
         """A row capacity that always suffices for chunks of up to ``nmax`` samples."""
-        return int(self._lib.wekws_hip_resample_max_out(self._ptr, int(nmax), int(bool(flush))))
+        return int(self._fn("max_out")(self._ptr, int(nmax), int(bool(flush))))
 
     def push(self, pcm, samples=None, streams=None, flush: bool = False, capacity: Optional[int] = None):
         """``pcm``: a (B, nmax) int16 device tensor, or a list of ``bytes`` / int16 arrays (uploaded as ONE padded tensor);
@@ -418,7 +423,12 @@ class StreamingResampler:
         pcm = pcm.contiguous()
         B, nmax = int(pcm.size(0)), int(pcm.size(1))
         ids = np.arange(B, dtype=np.int32) if streams is None else np.asarray([int(s) for s in streams], dtype=np.int64)
-        ns = np.full(B, nmax, dtype=np.int32) if samples is None else np.asarray([int(n) for n in samples], dtype=np.int64)
+        if samples is None:
+            ns = np.full(B, nmax, dtype=np.int32)
+        elif isinstance(samples, np.ndarray) and samples.dtype.kind in "iu":            # (thousands of rows: no Python loop)
+            ns = samples.astype(np.int64)
+        else:
+            ns = np.asarray([int(n) for n in samples], dtype=np.int64)
         if ids.shape != (B,) or ns.shape != (B,):
             raise ValueError("streams / samples must have one entry per row of pcm")
         lim = np.iinfo(np.int32)
@@ -428,10 +438,10 @@ class StreamingResampler:
         out = torch.empty((B, cap), dtype=self.out_dtype, device=pcm.device)
         got = np.zeros(max(B, 1), dtype=np.int32)
         stream = torch.cuda.current_stream(pcm.device).cuda_stream
-        _capi.check(self._lib.wekws_hip_resample_push(
+        _capi.check(self._fn("push")(
             self._ptr, pcm.data_ptr() if nmax else None, B, nmax, ids.ctypes.data if B else None, ns.ctypes.data if B else None,
             int(bool(flush)), out.data_ptr() if cap else None, cap, got.ctypes.data, ctypes.c_void_p(stream)),
-            "wekws_hip_resample_push")
+            self._ABI + "push")
         counts = got[:B].tolist()
         if capacity is None:
             out = out[:, :max(counts + [0])]
@@ -439,11 +449,128 @@ class StreamingResampler:
 
     def reset(self, streams=None) -> None:
         ids = list(range(self.num_streams)) if streams is None else [int(s) for s in streams]
-        _capi.check(self._lib.wekws_hip_resample_reset(self._ptr, (ctypes.c_int32 * max(len(ids), 1))(*ids), len(ids)),
-                    "wekws_hip_resample_reset")
+        _capi.check(self._fn("reset")(self._ptr, (ctypes.c_int32 * max(len(ids), 1))(*ids), len(ids)),
+                    self._ABI + "reset")
 
     def counts(self, stream: int) -> Tuple[int, int, int, int]:
         """(samples received, samples emitted, samples kept on the device, flushed) of a stream: host values, no device read."""
         out = (ctypes.c_int64 * 4)()
-        _capi.check(self._lib.wekws_hip_resample_counts(self._ptr, int(stream), out), "wekws_hip_resample_counts")
+        _capi.check(self._fn("counts")(self._ptr, int(stream), out), self._ABI + "counts")
         return tuple(int(v) for v in out)
+
+
+def _resample_bank_handle(orig_freqs, new_freq, out_dtype, max_streams, max_chunk, device, lowpass_filter_width=6, rolloff=0.99):
+    if out_dtype not in (torch.float32, torch.int16):
+        raise ValueError("out_dtype must be torch.float32 or torch.int16")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("the resampler runs on the MI355X HIP path only (no CPU fallback)")
+    rates = [int(r) for r in orig_freqs]
+    cfg = _capi.ResampleCfg()
+    cfg.orig_freq, cfg.new_freq = (rates[0] if rates else 0), int(new_freq)
+    cfg.lowpass_filter_width, cfg.rolloff = int(lowpass_filter_width), float(rolloff)
+    cfg.out_dtype = 1 if out_dtype == torch.int16 else 0
+    cfg.max_streams, cfg.max_chunk = int(max_streams), int(max_chunk)
+    cfg.device = device.index if device.index is not None else torch.cuda.current_device()
+    lib = _capi.load()
+    ptr = ctypes.c_void_p()
+    arr = (ctypes.c_int32 * max(len(rates), 1))(*rates)
+    _capi.check(lib.wekws_hip_resample_bank_create(ctypes.byref(cfg), arr, len(rates), ctypes.byref(ptr)),
+                "wekws_hip_resample_bank_create")
+    return lib, ptr, torch.device("cuda", cfg.device), rates
+
+
+def _bank_member(rates, rate) -> int:
+    try:
+        return rates.index(int(rate))
+    except ValueError:
+        raise ValueError(f"rate {rate} is not in the bank {tuple(rates)}") from None
+
+
+class ResampleBank:
+    """``Resample`` for a batch whose rows have DIFFERENT source rates (the reference resamples per utterance,
+    wekws/dataset/processor.py:94-103), in one launch: a bank of up to 16 source rates and one target rate.
+
+        bank = ResampleBank([8000, 16000, 44100, 48000])
+        out, counts = bank(pcm, rate_of_row)     # pcm (B, nsamp) float32 or int16 on the device; rate_of_row: Hz, one per row
+
+    Row b equals ``Resample(rate_of_row[b])`` of that row bit for bit: ``counts[b]`` samples, zeros behind them.  ``lengths``:
+    the valid samples of each row (default: all).  A rate that is not in the bank raises ``ValueError``."""
+
+    def __init__(self, orig_freqs, new_freq: int = 16000, device="cuda", out_dtype=torch.float32):
+        self.new_freq, self.out_dtype = int(new_freq), out_dtype
+        self._ptr = ctypes.c_void_p()
+        self._lib, self._ptr, self.device, self.orig_freqs = _resample_bank_handle(orig_freqs, new_freq, out_dtype, 0, 0, device)
+
+    def __del__(self):
+        try:
+            if self._ptr:
+                self._lib.wekws_hip_resample_bank_destroy(self._ptr)
+                self._ptr = ctypes.c_void_p()
+        except Exception:
+            pass
+
+    def num_samples(self, rate: int, nsamp: int) -> int:
+        return int(self._lib.wekws_hip_resample_num_samples(int(rate), self.new_freq, int(nsamp)))
+
+    def __call__(self, pcm: torch.Tensor, rate_of_row, lengths=None):
+        if not torch.is_tensor(pcm) or pcm.dim() != 2 or not pcm.is_cuda or pcm.dtype not in (torch.float32, torch.int16):
+            raise ValueError("pcm must be a (B, nsamp) float32 or int16 tensor on a ROCm device")
+        pcm = pcm.contiguous()
+        B, n = int(pcm.size(0)), int(pcm.size(1))
+        members = np.ascontiguousarray([_bank_member(self.orig_freqs, r) for r in rate_of_row], dtype=np.int32)
+        if members.shape != (B,):
+            raise ValueError("rate_of_row must have one entry per row of pcm")
+        if lengths is None:
+            ns = np.full(B, n, dtype=np.int32)
+        else:
+            ns = np.ascontiguousarray(np.clip(np.asarray([int(v) for v in lengths], dtype=np.int64), -1, 2 ** 31 - 1), dtype=np.int32)
+            if ns.shape != (B,):
+                raise ValueError("lengths must have one entry per row of pcm")
+        counts = [self.num_samples(self.orig_freqs[m], max(int(v), 0)) for m, v in zip(members, ns)]
+        m = max([self.num_samples(r, n) for r in set(self.orig_freqs[k] for k in members)] + [0])
+        out = torch.empty((B, m), dtype=self.out_dtype, device=pcm.device)
+        if B:
+            stream = torch.cuda.current_stream(pcm.device).cuda_stream
+            fn = self._lib.wekws_hip_resample_bank_compute if pcm.dtype == torch.float32 else self._lib.wekws_hip_resample_bank_compute_i16
+            _capi.check(fn(self._ptr, pcm.data_ptr() if n else None, B, n, ns.ctypes.data, members.ctypes.data,
+                           out.data_ptr() if m else None, m, ctypes.c_void_p(stream)), "wekws_hip_resample_bank_compute")
+        return out, counts
+
+
+class StreamingResamplerBank(StreamingResampler):
+    """``StreamingResampler`` for streams of DIFFERENT source rates: every stream is assigned one rate of the bank
+    (``set_rate``; streams start at ``orig_freqs[0]``) and a push is one launch whatever the rates of its rows.
+
+        rs = StreamingResamplerBank(4096, [48000, 16000, 8000], max_chunk=14400)
+        rs.set_rate(range(1024, 2048), 8000)
+        out, counts = rs.push(pcm, streams=ids)  # row b continues stream ids[b] at that stream's rate
+
+    ``max_chunk`` counts input samples at whatever rate; ``max_out`` is the largest member's."""
+
+    _ABI = "wekws_hip_resample_bank_"
+
+    def __init__(self, num_streams: int, orig_freqs, new_freq: int = 16000, max_chunk: int = 48000, out_dtype=torch.int16,
+                 device="cuda"):
+        self.num_streams, self.max_chunk = int(num_streams), int(max_chunk)
+        self.new_freq, self.out_dtype = int(new_freq), out_dtype
+        self._ptr = ctypes.c_void_p()
+        self._lib, self._ptr, self.device, self.orig_freqs = _resample_bank_handle(orig_freqs, new_freq, out_dtype, num_streams,
+                                                                                   max_chunk, device)
+
+    __del__ = ResampleBank.__del__
+
+    def set_rate(self, streams, rate: int) -> None:
+        """The streams arrive at ``rate`` (Hz, a member of the bank) from now on and start over: nothing received, nothing
+        kept, not flushed.  A rate outside the bank raises ``ValueError``; a bad stream is refused and changes no stream."""
+        member = _bank_member(self.orig_freqs, rate)
+        ids = list(range(self.num_streams)) if streams is None else [int(s) for s in streams]
+        _capi.check(self._lib.wekws_hip_resample_bank_set_rate(self._ptr, (ctypes.c_int32 * max(len(ids), 1))(*ids), len(ids), member),
+                    "wekws_hip_resample_bank_set_rate")
+
+    def rate_of(self, stream: int) -> int:
+        """The rate in Hz at which the stream arrives."""
+        rate = int(self._lib.wekws_hip_resample_bank_rate_of(self._ptr, int(stream)))
+        if rate <= 0:
+            _capi.check(rate, "wekws_hip_resample_bank_rate_of")
+        return rate

@@ -14,8 +14,27 @@ import torch
 from wekws_amd import pack
 from wekws_amd.ctc import StreamingKeywordSpotter
 from wekws_amd.det import StreamingThresholdSpotter
-from wekws_amd.frontend import StreamingFrontEnd, StreamingResampler
+from wekws_amd.frontend import StreamingFrontEnd, StreamingResampler, StreamingResamplerBank
 from wekws_amd.model.kws_model import StreamCachePool
+
+
+def _input_resampler(num_streams, input_rate, fe, device):
+    """The resampler in front of the front end: none, a StreamingResampler for one input rate, a StreamingResamplerBank for a
+    sequence of them (int16 out).  With one, the front end's ``max_chunk`` becomes the resampler's ``max_out``."""
+    if input_rate is None:
+        return None
+    bank = isinstance(input_rate, (list, tuple))
+    kind, rate = (StreamingResamplerBank, list(input_rate)) if bank else (StreamingResampler, int(input_rate))
+    rs = kind(num_streams, rate, int(fe.get("sample_rate", 16000)), max_chunk=int(fe.get("max_chunk", 16000)), device=device)
+    fe["max_chunk"] = rs.max_out(rs.max_chunk)
+    return rs
+
+
+def _set_input_rate(kws, streams, rate) -> None:
+    if not isinstance(kws.resampler, StreamingResamplerBank):
+        raise ValueError("set_input_rate needs a spotter built with a sequence of rates in input_sample_rate")
+    kws.resampler.set_rate(streams, rate)       # (refuses a bad rate or stream before anything else is reset)
+    kws.reset_all(streams)
 
 
 class BatchedKeyWordSpotter:
@@ -30,6 +49,8 @@ class BatchedKeyWordSpotter:
     StreamingKeywordSpotter's (``min_frames``, ``max_frames``, ``interval_frames``, ``score_beam``, ``path_beam``,
     ``prefix_capacity``); ``downsampling`` is ``skip``.  ``input_sample_rate`` (e.g. 48000): the chunks arrive at that rate and
     pass a StreamingResampler (int16 out) to the front end's ``sample_rate`` first; ``max_chunk`` then counts INPUT samples.
+    A sequence of rates (e.g. ``[16000, 48000, 8000]``) puts a StreamingResamplerBank there instead: every stream has its own
+    input rate, the first one until ``kws.set_input_rate(streams, rate)`` says otherwise, and a step stays the same device calls.
 
     Streams of different users may have different wake words: ``sid = kws.add_keywords({...}, threshold)`` registers a keyword
     set beside the constructor's, ``kws.set_keywords(sid, streams)`` gives it to streams (a new session for them),
@@ -44,11 +65,7 @@ class BatchedKeyWordSpotter:
         self.model = model
         self.device = next(model.parameters()).device
         self.num_streams = int(num_streams)
-        self.resampler = None
-        if input_rate is not None:
-            self.resampler = StreamingResampler(self.num_streams, int(input_rate), int(fe.get("sample_rate", 16000)),
-                                                max_chunk=int(fe.get("max_chunk", 16000)), device=self.device)
-            fe["max_chunk"] = self.resampler.max_out(self.resampler.max_chunk)
+        self.resampler = _input_resampler(self.num_streams, input_rate, fe, self.device)
         self.frontend = StreamingFrontEnd(self.num_streams, device=self.device, **fe)
         shift_ms = 1000.0 * self.frontend.cfg.fbank.frame_shift / self.frontend.cfg.fbank.sample_rate
         self.spotter = StreamingKeywordSpotter(self.num_streams, keywords, threshold, downsampling=self.frontend.skip,
@@ -103,6 +120,11 @@ class BatchedKeyWordSpotter:
         self.frontend.reset(streams)
         self.pool.reset(streams)
 
+    def set_input_rate(self, streams, rate: int) -> None:
+        """The streams (default all) arrive at ``rate`` from now on, one of the constructor's ``input_sample_rate`` sequence.  A
+        new session for them: the resampler's set_rate, and reset_all."""
+        _set_input_rate(self, streams, rate)
+
     def add_keywords(self, keywords, threshold=None) -> int:
         """Register a keyword set beside the constructor's (StreamingKeywordSpotter.add_keywords); returns its id."""
         if self.spotter._hd is None:
@@ -150,11 +172,7 @@ class BatchedThresholdSpotter:
         self.model = model
         self.device = next(model.parameters()).device
         self.num_streams = int(num_streams)
-        self.resampler = None
-        if input_rate is not None:
-            self.resampler = StreamingResampler(self.num_streams, int(input_rate), int(fe.get("sample_rate", 16000)),
-                                                max_chunk=int(fe.get("max_chunk", 16000)), device=self.device)
-            fe["max_chunk"] = self.resampler.max_out(self.resampler.max_chunk)
+        self.resampler = _input_resampler(self.num_streams, input_rate, fe, self.device)
         self.frontend = StreamingFrontEnd(self.num_streams, device=self.device, **fe)
         shift_ms = 1000.0 * self.frontend.cfg.fbank.frame_shift / self.frontend.cfg.fbank.sample_rate
         self.spotter = StreamingThresholdSpotter(self.num_streams, names, threshold, window_shift=window_shift,
@@ -201,3 +219,7 @@ class BatchedThresholdSpotter:
             self.resampler.reset(streams)
         self.frontend.reset(streams)
         self.pool.reset(streams)
+
+    def set_input_rate(self, streams, rate: int) -> None:
+        """As BatchedKeyWordSpotter.set_input_rate."""
+        _set_input_rate(self, streams, rate)
