@@ -841,6 +841,53 @@ int wekws_hip_resample_bank_reset(void* h, const int32_t* ids, int n);
 int wekws_hip_resample_bank_counts(void* h, int id, int64_t counts_out[4]);
 
 /* -------------------------------------------------------------------------------------------
+ * Wire encodings  --  the rate bank fed the bytes a stream arrives in: G.711 telephony (one mu-law or A-law byte per sample),
+ * unsigned 8-bit recordings, WebAudio float32, beside int16.  A member of a wire bank is a (rate, encoding) pair; the decode
+ * happens in the resampler's fetch (no decode kernel, no decoded copy of the chunk in device memory) and every encoding decodes
+ * one sample to one int16 value v, so the history of a stream, the arithmetic and the bit-for-bit contracts above stay as
+ * they are: a wire row's output equals the _i16 call's on wekws_hip_wire_decode of that row, bit for bit.
+ *
+ *   S16    2 bytes, little endian   v = the value
+ *   MULAW  1 byte c  (ITU-T G.711)  u = ~c & 0xFF;  t = (((u & 0x0F) << 3) + 0x84) << ((u & 0x70) >> 4);
+ *                                   v = (u & 0x80) ? 0x84 - t : t - 0x84                   0xFF, 0x7F -> 0;  0x80 -> 32124
+ *   ALAW   1 byte c  (ITU-T G.711)  a = c ^ 0x55;  t = (a & 0x0F) << 4;  s = (a & 0x70) >> 4;  t += s ? 0x108 : 8;
+ *                                   if (s > 1) t <<= s - 1;  v = (a & 0x80) ? t : -t        0xD5 -> 8;  0xAA -> 32256
+ *   U8     1 byte c                 v = (c - 128) * 256
+ *   F32    4 bytes, little endian,  v = rint(x * 32768.0f) (half to even; the product is exact), saturated to
+ *          unit scale               [-32768, 32767] (+-Inf saturate), NaN -> 0: a wire row never takes the non-finite path
+ * ------------------------------------------------------------------------------------------*/
+enum wekws_hip_wire { WEKWS_HIP_WIRE_S16 = 0, WEKWS_HIP_WIRE_MULAW = 1, WEKWS_HIP_WIRE_ALAW = 2,
+                      WEKWS_HIP_WIRE_U8 = 3, WEKWS_HIP_WIRE_F32 = 4 };
+/* Bytes of one sample: 2, 1, 1, 1, 4;  0 for an unknown encoding. */
+int wekws_hip_wire_sample_bytes(int encoding);
+/* On the HOST: the n samples at src (host memory, any alignment) decoded to dst (n int16) by the definition above.
+ * WEKWS_HIP_EINVAL for an unknown encoding, n < 0 or a NULL pointer with n > 0. */
+int wekws_hip_wire_decode(int encoding, const void* src, int64_t n, int16_t* dst);
+/*
+ * wekws_hip_resample_bank_create with an encoding per member (encodings (num_rates) HOST int32, enum wekws_hip_wire).  The same
+ * rate may appear with different encodings; a repeated (rate, encoding) pair and an unknown encoding are WEKWS_HIP_EINVAL, the
+ * other refusals are _create's.  wekws_hip_resample_bank_create is this call with every encoding S16.  _destroy, _set_rate
+ * (a member index), _rate_of, _max_out, _reset and _counts serve both kinds of handle.
+ */
+int wekws_hip_resample_bank_create_wire(const wekws_hip_resample_cfg* cfg, const int32_t* orig_freqs, const int32_t* encodings,
+                                        int num_rates, void** out);
+/*
+ * wekws_hip_resample_bank_compute / _push on wire bytes.  pcm (B, row_bytes) device bytes: row b holds nsamp[b] samples in
+ * its member's encoding from the row's first byte (_compute_wire: nsamp NULL = as many as row_bytes holds).  nsamp, max_chunk,
+ * mcap and the counts keep counting SAMPLES.  Beside every refusal of the int16 calls (nsamp[b] is held against max_chunk, not
+ * against an nmax): pcm not 4-byte aligned, row_bytes % 4 != 0, row_bytes > 2^30 - 4 or nsamp[b] * bytes > row_bytes are
+ * WEKWS_HIP_EINVAL, planned on the host first: nothing is launched and no stream changes.  A push is one launch whatever the
+ * members of its rows.  On a handle with members that are not S16, the int16 and float calls (_compute, _compute_i16, _push)
+ * refuse a row of such a member with WEKWS_HIP_EINVAL; rows of S16 members behave as ever.
+ */
+int wekws_hip_resample_bank_compute_wire(void* h, const uint8_t* pcm, int B, int row_bytes, const int32_t* nsamp,
+                                         const int32_t* member_of_row, void* out, int mcap, void* stream);
+int wekws_hip_resample_bank_push_wire(void* h, const uint8_t* pcm, int B, int row_bytes, const int32_t* stream_ids,
+                                      const int32_t* nsamp, int flush, void* out, int mcap, int32_t* counts, void* stream);
+/* The encoding (enum wekws_hip_wire) of stream id's member; WEKWS_HIP_EINVAL for a bad id. */
+int wekws_hip_resample_bank_encoding_of(void* h, int id);
+
+/* -------------------------------------------------------------------------------------------
  * Augmentation  --  add_reverb, add_noise and spec_aug of the data pipeline (wekws/dataset/processor.py:374-392, 395-430,
  * 206-240) on the device, between the resampler and the front end.  What is drawn at random (whether a row is augmented, which
  * RIR or noise, where the noise starts, the SNR, the masks) is drawn by the caller and passed in HOST tables; every call checks

@@ -157,6 +157,14 @@ SIGNATURES = {
     "wekws_hip_resample_bank_max_out": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "wekws_hip_resample_bank_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "wekws_hip_resample_bank_counts": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
+    "wekws_hip_wire_sample_bytes": (C.c_int, [C.c_int]),
+    "wekws_hip_wire_decode": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "wekws_hip_resample_bank_create_wire": (C.c_int, [C.POINTER(ResampleCfg), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "wekws_hip_resample_bank_compute_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_int, C.c_void_p]),
+    "wekws_hip_resample_bank_push_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                    C.c_int, C.c_void_p, C.c_void_p]),
+    "wekws_hip_resample_bank_encoding_of": (C.c_int, [C.c_void_p, C.c_int]),
     "wekws_hip_threshold_kws_create": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "wekws_hip_threshold_kws_destroy": (None, [C.c_void_p]),
     "wekws_hip_threshold_kws_max_hits": (C.c_int, [C.c_void_p, C.c_int]),

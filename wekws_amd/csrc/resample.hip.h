@@ -22,6 +22,13 @@
 //   history     the workgroup of a row's tile 0 writes the samples the stream keeps into the stream's OTHER buffer: the
 //               other tiles still read the old one.
 //   int16 out   rint (half to even), then saturation to [-32768, 32767]; NaN gives 0.
+//   chunk       what a row's chunk is in memory is apart from the sample type In of the history and of LDS: ResampleChunk<In>,
+//               samples of In themselves, or ResampleWireChunk, the bytes of a wire encoding (wire.h) decoded to int16 where they
+//               are fetched -- in the staging loop and in the history write-back, nowhere else.  The encoding is the row's
+//               (ResampleRow::wire), so it is uniform over the workgroup: the branches on it are scalar.  A group of 4 samples is
+//               one aligned load of a dword (single-byte encodings), of 8 bytes (int16) or of 16 bytes (float32), decoded in
+//               registers and stored to LDS as 8 bytes of int16; the row's ragged head and tail go sample by sample, like the
+//               seam.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,6 +38,7 @@
 #include <vector>
 
 #include "resample_plan.h"
+#include "wire.h"
 
 namespace wekws {
 
@@ -46,7 +54,7 @@ struct ResampleRow {        // what the kernel knows about one row (12 x int32);
   int32_t hist_old, hist_new;   // sample offsets of the stream's history buffers (read / written)
   int32_t keep_from, keep_cnt;  // positions [keep_from, keep_from + keep_cnt) become the new history
   int32_t member, row;          // rate bank alone (resample_bank.hip.h): the row's plan, and its place in x and y
-  int32_t reserved;
+  int32_t wire;                 // wire calls of the rate bank alone: the encoding of the row's chunk (enum wekws_hip_wire); else 0
 };
 
 struct ResampleParams {
@@ -70,11 +78,94 @@ __device__ __forceinline__ float resample_sample(const float* taps, int cnt, con
   return acc;
 }
 
-// position rel of the row's virtual signal [history | chunk], zeros outside
+__device__ __forceinline__ int resample_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+// ---- a row's chunk.  Sample: the type it delivers (the history's and the LDS tile's); kGroup: samples of one staged group, at most
+// kResampleVec (the slack the tile's capacity holds); at(k): sample k; slack(k): how many samples position k lies behind the alignment stage() loads at; stage(dst, k):
+// the group at an aligned position k, whole inside the chunk, to LDS -- returns whether it holds a non-finite value (float alone).
 template <typename In>
-__device__ __forceinline__ In resample_fetch(const ResampleRow& R, const In* hist, const In* chunk, int rel) {
+struct ResampleChunk {                       // samples of the kernel's own type
+  typedef In Sample;
+  typedef In Src;
+  static constexpr int kGroup = 16 / int(sizeof(In));
+  static constexpr bool kPlain = true;       // a sample is a plain load from p
+  const In* p;
+  __device__ __forceinline__ ResampleChunk(const In* row, const ResampleRow&) : p(row) {}
+  __device__ __forceinline__ In at(int k) const { return p[k]; }
+  __device__ __forceinline__ int slack(int k) const {
+    const int64_t src = int64_t(reinterpret_cast<uintptr_t>(p) / sizeof(In)) + k;
+    return int(((src % kGroup) + kGroup) % kGroup);           // down to a 16-byte boundary of the chunk
+  }
+  __device__ __forceinline__ int stage(In* dst, int k) const {
+    const uint4 v = *reinterpret_cast<const uint4*>(p + k);
+    *reinterpret_cast<uint4*>(dst) = v;
+    if constexpr (std::is_same<In, float>::value)
+      return resample_nonfinite(__uint_as_float(v.x)) | resample_nonfinite(__uint_as_float(v.y)) |
+             resample_nonfinite(__uint_as_float(v.z)) | resample_nonfinite(__uint_as_float(v.w));
+    else
+      return 0;
+  }
+};
+
+struct ResampleWireChunk {                   // bytes of the row's wire encoding (wire.h): p is 4-byte aligned (the plan's check)
+  typedef int16_t Sample;
+  typedef uint8_t Src;
+  // Four samples per lane and group: the decode is VALU work of the staging lanes alone, and a tile's input is few groups (an 8 kHz
+  // tile reads ~160 samples), so narrower groups put more lanes to it -- one dword of single bytes, 8 bytes of int16, 16 of float32.
+  static constexpr int kGroup = 4;
+  static constexpr bool kPlain = false;
+  const uint8_t* p;
+  int enc, bytes;                            // uniform over the workgroup (the row's): every branch on them is scalar
+  __device__ __forceinline__ ResampleWireChunk(const uint8_t* row, const ResampleRow& R)
+      : p(row), enc(R.wire), bytes(wire_sample_bytes(R.wire)) {}
+  __device__ __forceinline__ int16_t at(int k) const {
+    if (enc == WEKWS_HIP_WIRE_MULAW) return int16_t(wire_mulaw(p[k]));
+    if (enc == WEKWS_HIP_WIRE_ALAW) return int16_t(wire_alaw(p[k]));
+    if (enc == WEKWS_HIP_WIRE_U8) return int16_t(wire_u8(p[k]));
+    if (enc == WEKWS_HIP_WIRE_F32) return int16_t(wire_f32(reinterpret_cast<const float*>(p)[k]));
+    return reinterpret_cast<const int16_t*>(p)[k];
+  }
+  // a group is 4, 8 or 16 source bytes, loaded at its own size's alignment: at most 3 samples of slack
+  // (sizes and alignments are powers of two: a mask and a shift, where a division by a run-time value would be a long routine)
+  __device__ __forceinline__ int slack(int k) const {
+    const uint64_t addr = uint64_t(reinterpret_cast<uintptr_t>(p)) + uint64_t(int64_t(k) * bytes);
+    return int(uint32_t(addr) & uint32_t(kGroup * bytes - 1)) >> (bytes >> 1);
+  }
+  static __device__ __forceinline__ uint2 pack(int v0, int v1, int v2, int v3) {
+    return make_uint2((uint32_t(v0) & 0xffffu) | (uint32_t(v1) << 16), (uint32_t(v2) & 0xffffu) | (uint32_t(v3) << 16));
+  }
+  __device__ __forceinline__ int stage(int16_t* dst, int k) const {
+    uint2 o;
+    if (bytes == 1) {
+      const uint32_t w = *reinterpret_cast<const uint32_t*>(p + k);
+      const uint32_t c0 = w & 0xffu, c1 = (w >> 8) & 0xffu, c2 = (w >> 16) & 0xffu, c3 = w >> 24;
+      if (enc == WEKWS_HIP_WIRE_MULAW) o = pack(wire_mulaw(c0), wire_mulaw(c1), wire_mulaw(c2), wire_mulaw(c3));
+      else if (enc == WEKWS_HIP_WIRE_ALAW) o = pack(wire_alaw(c0), wire_alaw(c1), wire_alaw(c2), wire_alaw(c3));
+      else o = pack(wire_u8(c0), wire_u8(c1), wire_u8(c2), wire_u8(c3));
+    } else if (bytes == 2) {
+      o = *reinterpret_cast<const uint2*>(p + int64_t(k) * 2);
+    } else {
+      const uint4 a = *reinterpret_cast<const uint4*>(p + int64_t(k) * 4);
+      o = pack(wire_f32(__uint_as_float(a.x)), wire_f32(__uint_as_float(a.y)), wire_f32(__uint_as_float(a.z)),
+               wire_f32(__uint_as_float(a.w)));
+    }
+    *reinterpret_cast<uint2*>(dst) = o;
+    return 0;
+  }
+};
+
+// position rel of the row's virtual signal [history | chunk], zeros outside
+template <typename Chunk>
+__device__ __forceinline__ typename Chunk::Sample resample_fetch(const ResampleRow& R, const typename Chunk::Sample* hist,
+                                                                 const Chunk& chunk, int rel) {
+  typedef typename Chunk::Sample In;
   if (rel < 0 || rel >= R.hi_valid) return In(0);
-  return rel < R.h ? hist[R.hist_old + rel] : chunk[rel - R.h];
+  if constexpr (Chunk::kPlain) {             // one load through the chosen address, not a load under either branch
+    const In* const q = rel < R.h ? hist + (R.hist_old + rel) : chunk.p + (rel - R.h);
+    return *q;
+  } else {
+    return rel < R.h ? hist[R.hist_old + rel] : chunk.at(rel - R.h);
+  }
 }
 
 template <typename Out>
@@ -87,8 +178,6 @@ __device__ __forceinline__ Out resample_out(float v) {
     return Out(int(r));
   }
 }
-
-__device__ __forceinline__ int resample_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
 // The LDS of a workgroup under the plan P: the live table, the live ranges, the input tile.
 template <typename In>
@@ -110,12 +199,15 @@ __device__ __forceinline__ void resample_load_table(const ResampleParams& P, con
   for (int e = tid; e < P.n; e += kResampleTile) { S.first[e] = P.first[e]; S.count[e] = P.count[e]; }
 }
 
-// Tile tl of row R, by the whole workgroup: the history write-back (tile 0), the staging, one output per lane.  chunk / yrow: the
-// row's input and output.  Ends behind a barrier, so the next tile may overwrite the samples (and the table).
-template <typename In, typename Out>
-__device__ __forceinline__ void resample_tile(const ResampleParams& P, const ResampleLds<In>& S, const ResampleRow& R,
-                                              const In* __restrict__ chunk, In* hist, Out* __restrict__ yrow, int mcap, int tl) {
-  constexpr int V = 16 / int(sizeof(In));
+// Tile tl of row R, by the whole workgroup: the history write-back (tile 0), the staging, one output per lane.  src / yrow: the
+// row's input (as Chunk reads it) and output.  Ends behind a barrier, so the next tile may overwrite the samples (and the table).
+template <typename Chunk, typename Out>
+__device__ __forceinline__ void resample_tile(const ResampleParams& P, const ResampleLds<typename Chunk::Sample>& S,
+                                              const ResampleRow& R, const typename Chunk::Src* __restrict__ src,
+                                              typename Chunk::Sample* hist, Out* __restrict__ yrow, int mcap, int tl) {
+  typedef typename Chunk::Sample In;
+  const Chunk chunk(src, R);
+  constexpr int V = Chunk::kGroup;
   constexpr bool kFloatIn = std::is_same<In, float>::value;
   const float* const taps = S.taps;
   const int* const first = S.first;
@@ -132,18 +224,13 @@ __device__ __forceinline__ void resample_tile(const ResampleParams& P, const Res
   // ---- the samples under the full windows of the tile's outputs, from position tile_lo on
   const int jt0 = (R.i0 + r0) / P.n;
   int tile_lo = R.base_rel + jt0 * P.o;
-  const int64_t src = int64_t(reinterpret_cast<uintptr_t>(chunk) / sizeof(In)) + (tile_lo - R.h);
-  const int a = int(((src % V) + V) % V);                      // down to a 16-byte boundary of the chunk
+  const int a = chunk.slack(tile_lo - R.h);                    // down to the alignment of the chunk's group loads
   tile_lo -= a;
   int bad = 0;
   for (int g = tid; g < P.tile_cap / V; g += kResampleTile) {
     const int rel = tile_lo + g * V;
     if (rel >= 0 && rel >= R.h && rel + V <= R.hi_valid) {
-      const uint4 v = *reinterpret_cast<const uint4*>(chunk + (rel - R.h));
-      *reinterpret_cast<uint4*>(tile + g * V) = v;
-      if constexpr (kFloatIn)
-        bad |= resample_nonfinite(__uint_as_float(v.x)) | resample_nonfinite(__uint_as_float(v.y)) |
-               resample_nonfinite(__uint_as_float(v.z)) | resample_nonfinite(__uint_as_float(v.w));
+      bad |= chunk.stage(tile + g * V, rel - R.h);
     } else {
 #pragma unroll
       for (int k = 0; k < V; ++k) {
@@ -185,7 +272,7 @@ __global__ __launch_bounds__(kResampleTile) void resample_kernel(const ResampleP
   for (int64_t t = blockIdx.x; t < total_tiles; t += gridDim.x) {
     const int b = int(t / tiles_per_row), tl = int(t - int64_t(b) * tiles_per_row);
     const ResampleRow R = rows[b];
-    resample_tile<In, Out>(P, S, R, x + int64_t(b) * xstride, hist, y + int64_t(b) * mcap, mcap, tl);
+    resample_tile<ResampleChunk<In>, Out>(P, S, R, x + int64_t(b) * xstride, hist, y + int64_t(b) * mcap, mcap, tl);
   }
 }
 

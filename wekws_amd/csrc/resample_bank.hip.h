@@ -12,18 +12,23 @@
 //   LDS         the layout of the loaded member, exactly as the single-rate kernel lays it out; the launch asks for the largest
 //               member's bytes.
 //   rows        the row table is uploaded in slot order (sorted by member); a row carries its member and its place in x and y.
+//   wire        a third source beside int16 and float rows: rows of BYTES in their member's wire encoding (wire.h), decoded to int16
+//               in the fetch (resample.hip.h: ResampleWireChunk).  x is then (B, xstride) bytes and the row carries its encoding; the
+//               history, the LDS tile and the arithmetic are the int16 rows'.  The list is ordered by member, so the encoding is
+//               uniform over a workgroup's current row.
 #pragma once
 #include "resample.hip.h"
 #include "resample_bank_plan.h"
 
 namespace wekws {
 
-template <typename In, typename Out>
+template <typename Chunk, typename Out>
 __global__ __launch_bounds__(kResampleTile) void resample_bank_kernel(const ResampleParams* __restrict__ members,
                                                                       const ResampleRow* __restrict__ rows,
-                                                                      const In* __restrict__ x, int64_t xstride, In* hist,
-                                                                      Out* __restrict__ y, int mcap, int tiles_per_row,
-                                                                      int64_t total_tiles) {
+                                                                      const typename Chunk::Src* __restrict__ x, int64_t xstride,
+                                                                      typename Chunk::Sample* hist, Out* __restrict__ y, int mcap,
+                                                                      int tiles_per_row, int64_t total_tiles) {
+  typedef typename Chunk::Sample In;
   extern __shared__ __attribute__((aligned(16))) unsigned char resample_bank_lds[];
   const int64_t t0 = resample_bank_span_begin(total_tiles, gridDim.x, blockIdx.x);
   const int64_t t1 = resample_bank_span_begin(total_tiles, gridDim.x, int64_t(blockIdx.x) + 1);
@@ -38,12 +43,13 @@ __global__ __launch_bounds__(kResampleTile) void resample_bank_kernel(const Resa
       loaded = R.member;
       __syncthreads();
     }
-    resample_tile<In, Out>(P, ResampleLds<In>(resample_bank_lds, P), R, x + int64_t(R.row) * xstride, hist,
-                           y + int64_t(R.row) * mcap, mcap, resample_bank_tile(t, tiles_per_row));
+    resample_tile<Chunk, Out>(P, ResampleLds<In>(resample_bank_lds, P), R, x + int64_t(R.row) * xstride, hist,
+                              y + int64_t(R.row) * mcap, mcap, resample_bank_tile(t, tiles_per_row));
   }
 }
 
-int launch_resample_bank(const ResampleParams* members, size_t lds, int in_i16, int out_i16, const ResampleRow* rows, const void* x,
+enum ResampleBankSource { kResampleBankF32 = 0, kResampleBankI16 = 1, kResampleBankWireBytes = 2 };   // what x holds; xstride in its units
+int launch_resample_bank(const ResampleParams* members, size_t lds, int source, int out_i16, const ResampleRow* rows, const void* x,
                          int64_t xstride, int16_t* hist, void* y, int B, int mcap, int max_grid, hipStream_t stream);
 
 }  // namespace wekws
@@ -52,7 +58,7 @@ int launch_resample_bank(const ResampleParams* members, size_t lds, int in_i16, 
 struct wekws_hip_resample_bank {
   int device = 0;
   wekws::ResampleBankPlan bank;
-  std::vector<int32_t> rates;                      // orig_freq of every member
+  std::vector<int32_t> rates;                      // orig_freq of every member (its encoding: bank.wire)
   std::vector<wekws::ResampleParams> P;            // of every member, as the device table holds them
   wekws::ResampleParams* d_params = nullptr;
   size_t lds = 0;

@@ -2,7 +2,7 @@
 // libwekws_hip.so: the sinks are empty, the unit exports nothing and holds no kernel.  libwekws_hip_hooks.so (make hooks: this unit
 // compiled with -DWEKWS_TEST_HOOKS, every other object shared with the product library): the sinks record, and the unit carries the test
 // hooks: the route trace of a forward, the routing functions of route.h and the blob layout of blob_layout.h without a device, the GRU
-// epoch, a CU hog, the fbank's plan and table, the row softmax on chosen logits, the resampler's taps and plan (a rate bank's too), the CTC decoder's keyword-set table.  Not part of the ABI in include/wekws_hip.h.
+// epoch, a CU hog, the fbank's plan and table, the row softmax on chosen logits, the resampler's taps and plan (a rate bank's too, and the check of a bank call's rows, wire bytes included), the CTC decoder's keyword-set table.  Not part of the ABI in include/wekws_hip.h.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -447,6 +447,27 @@ extern "C" int wekws_hip_debug_resample_bank_plan(const int32_t* rates, int num,
     list_tile[t] = wekws::resample_bank_tile(t, tiles_per_row);
   }
   for (int w = 0; w <= grid; ++w) span_begin[w] = wekws::resample_bank_span_begin(total, grid, w);
+  return WEKWS_HIP_OK;
+}
+// The rows of a rate-bank call, WITHOUT a device: the bank of (rates, encs) pairs (encs NULL: every member s16), then the function
+// every compute and push call checks its rows with (resample_bank_plan.h: resample_bank_check_rows).  wire_call: a _wire call, width
+// its row_bytes and pcm_addr the address of its bytes; otherwise an int16 / float call, width its nmax.  members (B): the member of
+// every row (a push looks it up per stream); nsamp (B) or NULL; limit: the most samples of a row (a push: max_chunk).
+// out[4]: the refusal (0: none; 1 pcm alignment, 2 row_bytes, 3 member, 4 length, 5 a row that is not s16 in an int16 / float call),
+// the row it is about (-1: the call), bytes per sample of member 0, members.  Returns 0, or what the bank's own plan refuses with
+// (WEKWS_HIP_EINVAL, WEKWS_HIP_EUNSUPPORTED; out[1] is then the member).
+extern "C" int wekws_hip_debug_resample_bank_check_rows(const int32_t* rates, const int32_t* encs, int num, int neu, int lpw, double rolloff,
+                                                        int wire_call, uint64_t pcm_addr, int64_t width, const int32_t* nsamp,
+                                                        const int32_t* members, int B, int64_t limit, int64_t* out) {
+  if (!out || B < 0 || (B > 0 && !members)) return WEKWS_HIP_EINVAL;
+  wekws::ResampleBankPlan bp;
+  int bad = -1;
+  const wekws::ResampleBankRefusal r = wekws::resample_bank_plan(rates, encs, num, neu, lpw, rolloff, &bp, &bad);
+  out[0] = 0; out[1] = bad; out[2] = 0; out[3] = 0;
+  if (r == wekws::kResampleBankLds) return WEKWS_HIP_EUNSUPPORTED;
+  if (r != wekws::kResampleBankOk) return WEKWS_HIP_EINVAL;
+  out[0] = wekws::resample_bank_check_rows(bp, wire_call, pcm_addr, width, nsamp, members, B, limit, &bad);
+  out[1] = bad; out[2] = bp.wire_bytes[0]; out[3] = int64_t(bp.members.size());
   return WEKWS_HIP_OK;
 }
 // Cap the grid of the handle's launches (max_grid <= 0: the handle's own again), so that a small batch makes one workgroup walk tiles of

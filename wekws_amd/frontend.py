@@ -2,7 +2,7 @@
 runtime/core/frontend/fbank.h:138-198, behind ``FeaturePipeline::AcceptWaveform``'s framing rule,
 runtime/core/frontend/feature_pipeline.cc:30-47) and the context-expansion / frame-skip step of the data pipeline
 (wekws/dataset/init_dataset.py:24-68), and in front of both the `resample` step (wekws/dataset/processor.py:83-103).  Thin
-host wrappers over the C ABI (wekws_hip_fbank_*, wekws_hip_splice, wekws_hip_resample_*, wekws_hip_resample_bank_*); no CPU
+host wrappers over the C ABI (wekws_hip_fbank_*, wekws_hip_splice, wekws_hip_resample_*, wekws_hip_resample_bank_* with the wire encodings of its members); no CPU
 fallback."""
 from __future__ import annotations
 
@@ -422,9 +422,20 @@ class StreamingResampler:
             raise ValueError("pcm must be a (B, nmax) int16 tensor on a ROCm device")
         pcm = pcm.contiguous()
         B, nmax = int(pcm.size(0)), int(pcm.size(1))
-        ids = np.arange(B, dtype=np.int32) if streams is None else np.asarray([int(s) for s in streams], dtype=np.int64)
+        ids, ns = self._rows(B, streams, samples, lambda: np.full(B, nmax, dtype=np.int32))
+        return self._launch("push", pcm, nmax, nmax, ids, ns, flush, capacity)
+
+    @staticmethod
+    def _rows(B, streams, samples, default_samples):
+        """``streams`` / ``samples`` of a push as int32 arrays of B entries (out of range stays out of range: EINVAL)."""
+        if streams is None:
+            ids = np.arange(B, dtype=np.int32)
+        elif isinstance(streams, np.ndarray) and streams.dtype.kind in "iu":            # (thousands of rows: no Python loop)
+            ids = streams.astype(np.int64)
+        else:
+            ids = np.asarray([int(s) for s in streams], dtype=np.int64)
         if samples is None:
-            ns = np.full(B, nmax, dtype=np.int32)
+            ns = default_samples()
         elif isinstance(samples, np.ndarray) and samples.dtype.kind in "iu":            # (thousands of rows: no Python loop)
             ns = samples.astype(np.int64)
         else:
@@ -432,16 +443,20 @@ class StreamingResampler:
         if ids.shape != (B,) or ns.shape != (B,):
             raise ValueError("streams / samples must have one entry per row of pcm")
         lim = np.iinfo(np.int32)
-        ids = np.ascontiguousarray(np.clip(ids, lim.min, lim.max), dtype=np.int32)     # (out of range stays out of range: EINVAL)
-        ns = np.ascontiguousarray(np.clip(ns, lim.min, lim.max), dtype=np.int32)
+        return (np.ascontiguousarray(np.clip(ids, lim.min, lim.max), dtype=np.int32),
+                np.ascontiguousarray(np.clip(ns, lim.min, lim.max), dtype=np.int32))
+
+    def _launch(self, entry, pcm, width, nmax, ids, ns, flush, capacity):
+        """The push ``entry`` on pcm (B, width) -- width in the entry point's unit, nmax the most samples of a row."""
+        B = int(pcm.size(0))
         cap = self.max_out(nmax, flush) if capacity is None else int(capacity)
         out = torch.empty((B, cap), dtype=self.out_dtype, device=pcm.device)
         got = np.zeros(max(B, 1), dtype=np.int32)
         stream = torch.cuda.current_stream(pcm.device).cuda_stream
-        _capi.check(self._fn("push")(
-            self._ptr, pcm.data_ptr() if nmax else None, B, nmax, ids.ctypes.data if B else None, ns.ctypes.data if B else None,
+        _capi.check(self._fn(entry)(
+            self._ptr, pcm.data_ptr() if width else None, B, width, ids.ctypes.data if B else None, ns.ctypes.data if B else None,
             int(bool(flush)), out.data_ptr() if cap else None, cap, got.ctypes.data, ctypes.c_void_p(stream)),
-            self._ABI + "push")
+            self._ABI + entry)
         counts = got[:B].tolist()
         if capacity is None:
             out = out[:, :max(counts + [0])]
@@ -465,7 +480,8 @@ def _resample_bank_handle(orig_freqs, new_freq, out_dtype, max_streams, max_chun
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("the resampler runs on the MI355X HIP path only (no CPU fallback)")
-    rates = [int(r) for r in orig_freqs]
+    members = [_bank_pair(m) for m in orig_freqs]
+    rates = [r for r, _ in members]
     cfg = _capi.ResampleCfg()
     cfg.orig_freq, cfg.new_freq = (rates[0] if rates else 0), int(new_freq)
     cfg.lowpass_filter_width, cfg.rolloff = int(lowpass_filter_width), float(rolloff)
@@ -475,16 +491,40 @@ def _resample_bank_handle(orig_freqs, new_freq, out_dtype, max_streams, max_chun
     lib = _capi.load()
     ptr = ctypes.c_void_p()
     arr = (ctypes.c_int32 * max(len(rates), 1))(*rates)
-    _capi.check(lib.wekws_hip_resample_bank_create(ctypes.byref(cfg), arr, len(rates), ctypes.byref(ptr)),
-                "wekws_hip_resample_bank_create")
-    return lib, ptr, torch.device("cuda", cfg.device), rates
+    if all(e == "s16" for _, e in members):
+        _capi.check(lib.wekws_hip_resample_bank_create(ctypes.byref(cfg), arr, len(rates), ctypes.byref(ptr)),
+                    "wekws_hip_resample_bank_create")
+    else:
+        encs = (ctypes.c_int32 * len(members))(*[ENCODINGS.index(e) for _, e in members])
+        _capi.check(lib.wekws_hip_resample_bank_create_wire(ctypes.byref(cfg), arr, encs, len(rates), ctypes.byref(ptr)),
+                    "wekws_hip_resample_bank_create_wire")
+    return lib, ptr, torch.device("cuda", cfg.device), rates, members
 
 
-def _bank_member(rates, rate) -> int:
+# the wire encodings of a bank member (enum wekws_hip_wire, in its order) and the bytes of one sample
+ENCODINGS = ("s16", "mulaw", "alaw", "u8", "f32")
+_WIRE_BYTES = {"s16": 2, "mulaw": 1, "alaw": 1, "u8": 1, "f32": 4}
+_WIRE_DTYPE = {"s16": np.dtype("<i2"), "mulaw": np.dtype(np.uint8), "alaw": np.dtype(np.uint8), "u8": np.dtype(np.uint8),
+               "f32": np.dtype("<f4")}
+
+
+def _bank_pair(member):
+    """A bank member as ``(rate, encoding)``: an int rate means ``(rate, "s16")``."""
+    if isinstance(member, (tuple, list)):
+        if len(member) != 2 or member[1] not in ENCODINGS:
+            raise ValueError(f"a bank member is a rate or a (rate, encoding) pair with an encoding of {ENCODINGS}, not {member!r}")
+        return int(member[0]), str(member[1])
+    return int(member), "s16"
+
+
+def _bank_member(members, key) -> int:
+    """The index of ``key`` (a rate, meaning (rate, "s16"), or a (rate, encoding) pair) among the bank's (rate, encoding) pairs."""
     try:
-        return rates.index(int(rate))
+        return members.index(_bank_pair(key))
     except ValueError:
-        raise ValueError(f"rate {rate} is not in the bank {tuple(rates)}") from None
+        shown = tuple(r if e == "s16" else (r, e) for r, e in members)
+        what = f"rate {key}" if not isinstance(key, (tuple, list)) else f"{tuple(key)}"
+        raise ValueError(f"{what} is not in the bank {shown}") from None
 
 
 class ResampleBank:
@@ -495,12 +535,22 @@ class ResampleBank:
         out, counts = bank(pcm, rate_of_row)     # pcm (B, nsamp) float32 or int16 on the device; rate_of_row: Hz, one per row
 
     Row b equals ``Resample(rate_of_row[b])`` of that row bit for bit: ``counts[b]`` samples, zeros behind them.  ``lengths``:
-    the valid samples of each row (default: all).  A rate that is not in the bank raises ``ValueError``."""
+    the valid samples of each row (default: all).  A rate that is not in the bank raises ``ValueError``.
+
+    A member may also be a ``(rate, encoding)`` pair, the encoding one of ``ENCODINGS``: the bytes the audio arrives in (G.711
+    mu-law / A-law, unsigned 8-bit, float32 at unit scale), decoded to int16 inside the resampler's fetch.
+
+        bank = ResampleBank([(8000, "mulaw"), 16000, (48000, "f32")])
+        out, counts = bank(wire, [(8000, "mulaw"), 16000, (48000, "f32")])     # wire (B, row_bytes) uint8 on the device
+
+    Row b of a uint8 tensor holds ``lengths[b]`` samples of its member's encoding from its first byte (default: as many as the row
+    holds; ``row_bytes`` a multiple of 4) and equals the int16 call on the decoded samples bit for bit."""
 
     def __init__(self, orig_freqs, new_freq: int = 16000, device="cuda", out_dtype=torch.float32):
         self.new_freq, self.out_dtype = int(new_freq), out_dtype
         self._ptr = ctypes.c_void_p()
-        self._lib, self._ptr, self.device, self.orig_freqs = _resample_bank_handle(orig_freqs, new_freq, out_dtype, 0, 0, device)
+        self._lib, self._ptr, self.device, self.orig_freqs, self.members = _resample_bank_handle(orig_freqs, new_freq, out_dtype,
+                                                                                                 0, 0, device)
 
     def __del__(self):
         try:
@@ -510,31 +560,33 @@ class ResampleBank:
         except Exception:
             pass
 
-    def num_samples(self, rate: int, nsamp: int) -> int:
-        return int(self._lib.wekws_hip_resample_num_samples(int(rate), self.new_freq, int(nsamp)))
+    def num_samples(self, rate, nsamp: int) -> int:
+        return int(self._lib.wekws_hip_resample_num_samples(_bank_pair(rate)[0], self.new_freq, int(nsamp)))
 
     def __call__(self, pcm: torch.Tensor, rate_of_row, lengths=None):
-        if not torch.is_tensor(pcm) or pcm.dim() != 2 or not pcm.is_cuda or pcm.dtype not in (torch.float32, torch.int16):
-            raise ValueError("pcm must be a (B, nsamp) float32 or int16 tensor on a ROCm device")
+        if not torch.is_tensor(pcm) or pcm.dim() != 2 or not pcm.is_cuda or pcm.dtype not in (torch.float32, torch.int16, torch.uint8):
+            raise ValueError("pcm must be a (B, nsamp) float32 or int16 tensor, or (B, row_bytes) uint8 wire bytes, on a ROCm device")
         pcm = pcm.contiguous()
-        B, n = int(pcm.size(0)), int(pcm.size(1))
-        members = np.ascontiguousarray([_bank_member(self.orig_freqs, r) for r in rate_of_row], dtype=np.int32)
+        wire = pcm.dtype == torch.uint8
+        B, n = int(pcm.size(0)), int(pcm.size(1))               # (n: samples of a row, or bytes of a wire row)
+        members = np.ascontiguousarray([_bank_member(self.members, r) for r in rate_of_row], dtype=np.int32)
         if members.shape != (B,):
             raise ValueError("rate_of_row must have one entry per row of pcm")
+        holds = [n // _WIRE_BYTES[self.members[m][1]] if wire else n for m in members]      # samples a row has room for
         if lengths is None:
-            ns = np.full(B, n, dtype=np.int32)
+            ns = np.asarray(holds, dtype=np.int32).reshape(B)
         else:
             ns = np.ascontiguousarray(np.clip(np.asarray([int(v) for v in lengths], dtype=np.int64), -1, 2 ** 31 - 1), dtype=np.int32)
             if ns.shape != (B,):
                 raise ValueError("lengths must have one entry per row of pcm")
         counts = [self.num_samples(self.orig_freqs[m], max(int(v), 0)) for m, v in zip(members, ns)]
-        m = max([self.num_samples(r, n) for r in set(self.orig_freqs[k] for k in members)] + [0])
+        m = max([self.num_samples(r, h) for r, h in set((self.orig_freqs[k], h) for k, h in zip(members, holds))] + [0])
         out = torch.empty((B, m), dtype=self.out_dtype, device=pcm.device)
         if B:
             stream = torch.cuda.current_stream(pcm.device).cuda_stream
-            fn = self._lib.wekws_hip_resample_bank_compute if pcm.dtype == torch.float32 else self._lib.wekws_hip_resample_bank_compute_i16
-            _capi.check(fn(self._ptr, pcm.data_ptr() if n else None, B, n, ns.ctypes.data, members.ctypes.data,
-                           out.data_ptr() if m else None, m, ctypes.c_void_p(stream)), "wekws_hip_resample_bank_compute")
+            name = "wekws_hip_resample_bank_compute" + {torch.float32: "", torch.int16: "_i16", torch.uint8: "_wire"}[pcm.dtype]
+            _capi.check(getattr(self._lib, name)(self._ptr, pcm.data_ptr() if n else None, B, n, ns.ctypes.data, members.ctypes.data,
+                                                 out.data_ptr() if m else None, m, ctypes.c_void_p(stream)), name)
         return out, counts
 
 
@@ -546,7 +598,14 @@ class StreamingResamplerBank(StreamingResampler):
         rs.set_rate(range(1024, 2048), 8000)
         out, counts = rs.push(pcm, streams=ids)  # row b continues stream ids[b] at that stream's rate
 
-    ``max_chunk`` counts input samples at whatever rate; ``max_out`` is the largest member's."""
+    ``max_chunk`` counts input samples at whatever rate; ``max_out`` is the largest member's.
+
+    Members may be ``(rate, encoding)`` pairs (``ENCODINGS``), e.g. ``[(8000, "mulaw"), 16000, (48000, "f32")]``: the streams of
+    such a member arrive as G.711 bytes, unsigned 8-bit or float32 and are decoded inside the same launch.  ``push`` then takes
+    a (B, row_bytes) uint8 device tensor -- row b holds ``samples[b]`` samples of its stream's encoding from its first byte,
+    ``row_bytes`` a multiple of 4 -- or a list of ``bytes`` / arrays, each read in its stream's encoding (``len // bytes``
+    samples) and uploaded as one padded uint8 tensor.  int16 tensors go where they always went and may only carry rows of
+    ``"s16"`` streams."""
 
     _ABI = "wekws_hip_resample_bank_"
 
@@ -555,18 +614,75 @@ class StreamingResamplerBank(StreamingResampler):
         self.num_streams, self.max_chunk = int(num_streams), int(max_chunk)
         self.new_freq, self.out_dtype = int(new_freq), out_dtype
         self._ptr = ctypes.c_void_p()
-        self._lib, self._ptr, self.device, self.orig_freqs = _resample_bank_handle(orig_freqs, new_freq, out_dtype, num_streams,
-                                                                                   max_chunk, device)
+        self._lib, self._ptr, self.device, self.orig_freqs, self.members = _resample_bank_handle(
+            orig_freqs, new_freq, out_dtype, num_streams, max_chunk, device)
+        self._wire = any(e != "s16" for _, e in self.members)
+        self._bytes = np.asarray([_WIRE_BYTES[e] for _, e in self.members], dtype=np.int64)
+        self._member_of = np.zeros(self.num_streams, dtype=np.int64)      # the library's own record, mirrored: streams start on member 0
 
     __del__ = ResampleBank.__del__
 
-    def set_rate(self, streams, rate: int) -> None:
-        """The streams arrive at ``rate`` (Hz, a member of the bank) from now on and start over: nothing received, nothing
-        kept, not flushed.  A rate outside the bank raises ``ValueError``; a bad stream is refused and changes no stream."""
-        member = _bank_member(self.orig_freqs, rate)
+    def set_rate(self, streams, rate) -> None:
+        """The streams arrive at ``rate`` (Hz, or a ``(rate, encoding)`` pair: a member of the bank) from now on and start over:
+        nothing received, nothing kept, not flushed.  A member outside the bank raises ``ValueError``; a bad stream is refused
+        and changes no stream."""
+        member = _bank_member(self.members, rate)
         ids = list(range(self.num_streams)) if streams is None else [int(s) for s in streams]
         _capi.check(self._lib.wekws_hip_resample_bank_set_rate(self._ptr, (ctypes.c_int32 * max(len(ids), 1))(*ids), len(ids), member),
                     "wekws_hip_resample_bank_set_rate")
+        self._member_of[ids] = member
+
+    def encoding_of(self, stream: int) -> str:
+        """The encoding (one of ``ENCODINGS``) in which the stream arrives."""
+        enc = int(self._lib.wekws_hip_resample_bank_encoding_of(self._ptr, int(stream)))
+        if enc < 0:
+            _capi.check(enc, "wekws_hip_resample_bank_encoding_of")
+        return ENCODINGS[enc]
+
+    def _row_bytes(self, ids):
+        """Bytes of one sample of every row's stream (1 for an id outside the streams: the library refuses the row)."""
+        ok = (ids >= 0) & (ids < self.num_streams)
+        return np.where(ok, self._bytes[self._member_of[np.where(ok, ids, 0)]], 1)
+
+    def push(self, pcm, samples=None, streams=None, flush: bool = False, capacity: Optional[int] = None):
+        """As StreamingResampler.push; with members that are not ``"s16"`` also wire bytes (the class's text)."""
+        if not self._wire:
+            return super().push(pcm, samples, streams, flush, capacity)
+        if not torch.is_tensor(pcm):
+            chunks = list(pcm)
+            ids = np.arange(len(chunks)) if streams is None else np.asarray([int(s) for s in streams], dtype=np.int64)
+            if ids.shape != (len(chunks),):
+                raise ValueError("streams / samples must have one entry per row of pcm")
+            ok = (ids >= 0) & (ids < self.num_streams)
+            rows = []
+            for c, i, good in zip(chunks, ids, ok):
+                enc = self.members[self._member_of[i]][1] if good else "s16"
+                if isinstance(c, (bytes, bytearray, memoryview)):
+                    a = np.frombuffer(c, dtype=np.uint8)
+                    a = a[:a.size // _WIRE_BYTES[enc] * _WIRE_BYTES[enc]]
+                else:
+                    a = np.asarray(c)
+                    if a.ndim != 1 or a.dtype != _WIRE_DTYPE[enc]:
+                        raise ValueError(f"a chunk of a {enc!r} stream must be bytes or a 1-d {_WIRE_DTYPE[enc].name} array")
+                    a = np.ascontiguousarray(a).view(np.uint8)
+                rows.append(a)
+            if samples is None:
+                samples = [int(a.size) // int(b) for a, b in zip(rows, self._row_bytes(ids))]
+            host = np.zeros((len(rows), (max([int(a.size) for a in rows] + [0]) + 3) // 4 * 4), dtype=np.uint8)
+            for i, a in enumerate(rows):
+                host[i, :a.size] = a
+            pcm = torch.from_numpy(host).to(self.device)
+        if pcm.dtype != torch.uint8:
+            return super().push(pcm, samples, streams, flush, capacity)
+        if pcm.dim() != 2 or not pcm.is_cuda:
+            raise ValueError("pcm must be a (B, row_bytes) uint8 tensor on a ROCm device")
+        pcm = pcm.contiguous()
+        B, row_bytes = int(pcm.size(0)), int(pcm.size(1))
+        ids, ns = self._rows(B, streams, samples, lambda: np.zeros(B, dtype=np.int32))
+        if samples is None:                                                          # every row as full as its encoding fills it
+            ns = np.ascontiguousarray(row_bytes // self._row_bytes(ids.astype(np.int64)), dtype=np.int32)
+        nmax = int(np.clip(ns, 0, row_bytes).max()) if B else 0
+        return self._launch("push_wire", pcm, row_bytes, nmax, ids, ns, flush, capacity)
 
     def rate_of(self, stream: int) -> int:
         """The rate in Hz at which the stream arrives."""

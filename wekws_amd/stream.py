@@ -51,6 +51,10 @@ class BatchedKeyWordSpotter:
     pass a StreamingResampler (int16 out) to the front end's ``sample_rate`` first; ``max_chunk`` then counts INPUT samples.
     A sequence of rates (e.g. ``[16000, 48000, 8000]``) puts a StreamingResamplerBank there instead: every stream has its own
     input rate, the first one until ``kws.set_input_rate(streams, rate)`` says otherwise, and a step stays the same device calls.
+    A member may be a ``(rate, encoding)`` pair (``wekws_amd.frontend.ENCODINGS``), e.g. ``[(8000, "mulaw"), 16000, (48000,
+    "f32")]`` with ``kws.set_input_rate(streams, (8000, "mulaw"))``: those streams' chunks are G.711 bytes, unsigned 8-bit or
+    float32, given as a list of ``bytes`` / arrays (each read in its stream's encoding) or as one (B, row_bytes) uint8 device
+    tensor, and decoded inside the resampler's launch -- still the same device calls.
 
     Streams of different users may have different wake words: ``sid = kws.add_keywords({...}, threshold)`` registers a keyword
     set beside the constructor's, ``kws.set_keywords(sid, streams)`` gives it to streams (a new session for them),
@@ -120,9 +124,9 @@ class BatchedKeyWordSpotter:
         self.frontend.reset(streams)
         self.pool.reset(streams)
 
-    def set_input_rate(self, streams, rate: int) -> None:
-        """The streams (default all) arrive at ``rate`` from now on, one of the constructor's ``input_sample_rate`` sequence.  A
-        new session for them: the resampler's set_rate, and reset_all."""
+    def set_input_rate(self, streams, rate) -> None:
+        """The streams (default all) arrive at ``rate`` from now on, one of the constructor's ``input_sample_rate`` sequence (Hz,
+        or a ``(rate, encoding)`` pair).  A new session for them: the resampler's set_rate, and reset_all."""
         _set_input_rate(self, streams, rate)
 
     def add_keywords(self, keywords, threshold=None) -> int:
