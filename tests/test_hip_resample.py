@@ -116,6 +116,65 @@ def test_one_shot_calls_queue_without_a_synchronise():
     within_bar(p, queued[9][1, :p.num_samples(lens[9][1])].cpu().numpy(), xs[9][1, :lens[9][1]].cpu().numpy(), "queued call 9 row 1")
 
 
+def alternate_one_shot_and_push(make, one_shot, rows, synchronise):
+    """Ten calls on ONE handle of 3 streams (make()), alternately a one-shot call -- call k has 1 + (5 k mod 7) rows of 3000 samples,
+    more than a table made for 3 streams holds -- and a push of 500 samples per stream.  one_shot(rs, x) -> out.  Returns every call's
+    output, the pushes' counts and the streams' counts at the end."""
+    rs = make()
+    g = torch.Generator(device="cpu").manual_seed(11)
+    xs = [torch.randint(-32768, 32768, (rows(k), 3000) if k % 2 == 0 else (3, 500), dtype=torch.int16, generator=g).to(DEV)
+          for k in range(10)]
+    torch.cuda.synchronize()
+    outs, counts = [], []
+    for k, x in enumerate(xs):
+        if k % 2 == 0:
+            outs.append(one_shot(rs, x))
+        else:
+            y, c = rs.push(x)
+            outs.append(y)
+            counts.append(c)
+        if synchronise:
+            torch.cuda.synchronize()
+    torch.cuda.synchronize()
+    return xs, outs, counts, [rs.counts(s) for s in range(3)]
+
+
+def assert_queued_calls_equal_synchronised_ones(make, one_shot, rows=lambda k: 1 + (5 * k) % 7):
+    xs, queued, counts_q, state_q = alternate_one_shot_and_push(make, one_shot, rows, False)
+    _, single, counts_s, state_s = alternate_one_shot_and_push(make, one_shot, rows, True)
+    assert [x.size(0) for x in xs[::2]] == [1, 4, 7, 3, 6]
+    assert counts_q == counts_s and state_q == state_s and state_q[0][0] == 5 * 500 and all(sum(c) > 0 for c in counts_q)
+    for k, (q, s) in enumerate(zip(queued, single)):
+        assert q.dtype == torch.int16 and q.shape == s.shape and torch.equal(q, s), f"call {k}"
+    return xs, queued
+
+
+def within_bar_i16(p, got, x, what):
+    """an int16 output row: the rounding adds half a unit to the bar, the saturation nothing (a clamp never widens a distance)"""
+    want, mag = RR.resample(p, x)
+    err = np.abs(got.astype(np.float64) - np.clip(want, -32768, 32767))
+    bar = RR.bar(p, mag) + 0.5
+    print(f"{what}: worst error {float((err / bar).max()):.3f} of the bar")
+    assert got.shape == want.shape and (err <= bar).all(), what
+
+
+def test_one_shot_calls_and_pushes_share_one_ring():
+    """one-shot calls and pushes of one handle, queued back to back through the one ring of row tables, equal the same calls made
+    one at a time: outputs bit for bit, counts, and the streams' state"""
+    lib = _capi.load()
+
+    def one_shot(rs, x):
+        B, n = int(x.size(0)), int(x.size(1))
+        m = int(lib.wekws_hip_resample_num_samples(44100, 16000, n))
+        out = torch.empty((B, m), dtype=torch.int16, device=DEV)
+        _capi.check(lib.wekws_hip_resample_compute_i16(rs._ptr, x.data_ptr(), B, n, None, out.data_ptr(), m,
+                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)), "compute_i16")
+        return out
+
+    xs, queued = assert_queued_calls_equal_synchronised_ones(lambda: StreamingResampler(3, 44100, max_chunk=600), one_shot)
+    within_bar_i16(plan(44100, 16000), queued[8][5].cpu().numpy(), xs[8][5].cpu().numpy(), "queued call 8 row 5")
+
+
 def test_equal_rates_copy():
     rs = Resample(16000, 16000)
     x = torch.randint(-32768, 32768, (3, 1000), dtype=torch.int16, device=DEV)

@@ -12,7 +12,8 @@ import pytest
 import torch
 
 from tests import resample_ref as RR
-from tests.test_hip_resample import HOOKS, TILE, one_shot_rows, plan, within_bar
+from tests.test_hip_resample import (HOOKS, TILE, assert_queued_calls_equal_synchronised_ones, one_shot_rows, plan, within_bar,
+                                     within_bar_i16)
 from wekws_amd import _capi
 from wekws_amd.frontend import Resample, ResampleBank, StreamingResampler, StreamingResamplerBank
 
@@ -331,6 +332,35 @@ def test_set_rate_restarts_the_streams_it_names(streams):
     rs.reset([3])
     out, counts = rs.push(chunk, streams=[3])
     assert rs.rate_of(3) == 48000 and counts[0] == plan(48000, NEW).step(0, 100, False)[0] and not out.any()
+
+
+def test_one_shot_calls_and_pushes_share_one_ring():
+    """tests/test_hip_resample.py's test of the same name on a bank: the one-shot rows are of mixed members (so every table is
+    sorted on its way into the ring), the three streams one per member"""
+    lib = _capi.load()
+    rates = (8000, 44100, 48000)
+
+    def make():
+        rs = StreamingResamplerBank(3, rates, NEW, max_chunk=600)
+        for s, rate in enumerate(rates):
+            rs.set_rate([s], rate)
+        return rs
+
+    def one_shot(rs, x):
+        B, n = int(x.size(0)), int(x.size(1))
+        members = np.asarray([(2 * b + B) % 3 for b in range(B)], dtype=np.int32)
+        m = max(int(lib.wekws_hip_resample_num_samples(r, NEW, n)) for r in rates)
+        out = torch.empty((B, m), dtype=torch.int16, device=DEV)
+        _capi.check(lib.wekws_hip_resample_bank_compute_i16(rs._ptr, x.data_ptr(), B, n, None, members.ctypes.data, out.data_ptr(), m,
+                                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "bank compute_i16")
+        return out
+
+    xs, queued = assert_queued_calls_equal_synchronised_ones(make, one_shot)
+    B = int(xs[8].size(0))
+    for b in (0, 4, 5):                                             # B = 6: members 0, 2, 1
+        p = plan(rates[(2 * b + B) % 3], NEW)
+        within_bar_i16(p, queued[8][b, :p.num_samples(3000)].cpu().numpy(), xs[8][b].cpu().numpy(), f"queued call 8 row {b}")
+        assert not queued[8][b, p.num_samples(3000):].any()
 
 
 # ------------------------------------------------------------------------------------------ negative control

@@ -42,7 +42,7 @@
 
 namespace wekws {
 
-constexpr int kResampleRing = 4;              // plan tables in flight (resample.hip)
+constexpr int kResampleRing = 4;              // row tables in flight (resample_bank.hip: take_slot)
 
 struct ResampleRow {        // what the kernel knows about one row (12 x int32); positions are relative to the row's origin:
                             // sample 0 of an utterance, the first kept sample of a stream
@@ -281,39 +281,4 @@ int launch_resample(const ResampleParams& P, size_t lds, int in_i16, int out_i16
 
 }  // namespace wekws
 
-// the handle of wekws_hip_resample_* (resample.hip; the hooks unit rounds its tables)
-struct wekws_hip_resample {
-  int device = 0;
-  wekws::ResamplePlan plan;
-  wekws::ResampleParams P{};
-  size_t lds = 0;
-  int out_i16 = 0, max_streams = 0, max_chunk = 0, hist_cap = 0, max_grid = 1;
-  float* d_live = nullptr;
-  float* d_full = nullptr;
-  int32_t* d_meta = nullptr;           // first (n) | count (n)
-  int16_t* hist = nullptr;             // (max_streams, 2, hist_cap) kept samples, ping-ponged per stream
-  // the plan table of a push travels through a ring of pinned host tables, each with its device twin and an event recorded
-  // behind the push that used it (as the streaming front end's)
-  wekws::ResampleRow* h_rows[wekws::kResampleRing] = {};
-  wekws::ResampleRow* d_rows[wekws::kResampleRing] = {};
-  hipEvent_t ev[wekws::kResampleRing] = {};
-  bool ev_used[wekws::kResampleRing] = {};
-  int next = 0;
-  // the row table of a one-shot call: the same kind of ring, every slot grown on demand (B is the caller's)
-  struct OnceSlot {
-    wekws::ResampleRow* h = nullptr;
-    wekws::ResampleRow* d = nullptr;
-    size_t cap = 0;
-    hipEvent_t ev = nullptr;
-    bool used = false;
-  };
-  OnceSlot once_ring[wekws::kResampleRing];
-  int once_next = 0;
-  std::mutex mu;
-  // per-stream counts live on the host: the outputs of every row are known without a device read-back
-  std::vector<int64_t> received, emitted, origin;   // origin: the first kept sample
-  std::vector<int32_t> par, seen, flushed;
-  int32_t epoch = 0;
-  std::vector<wekws::ResampleStep> steps;           // of the push being planned
-  std::vector<wekws::ResampleRow> once;             // of the one-shot call being planned
-};
+// (the handle of wekws_hip_resample_* is the rate bank's, with one member: resample_bank.hip.h)

@@ -19,6 +19,7 @@
 #pragma once
 #include "resample.hip.h"
 #include "resample_bank_plan.h"
+#include "resample_streams.h"
 
 namespace wekws {
 
@@ -54,20 +55,24 @@ int launch_resample_bank(const ResampleParams* members, size_t lds, int source, 
 
 }  // namespace wekws
 
-// the handle of wekws_hip_resample_bank_* (resample_bank.hip; the hooks unit caps its grid and rounds a member's tables)
-struct wekws_hip_resample_bank {
+// The host handle of wekws_hip_resample_* AND of wekws_hip_resample_bank_* (resample_bank.hip holds everything that works on it; the
+// hooks unit caps its grid and rounds a member's tables).  A single-rate handle is this struct with one S16 member: the bank's sizes are
+// maxima over one plan.  It differs in `kind` alone -- which kernel a call launches and which name its messages carry.
+struct wekws_hip_resample {
+  enum Kind { kSingle = 0, kBank = 1 };
+  int kind = kBank;
   int device = 0;
-  wekws::ResampleBankPlan bank;
-  std::vector<int32_t> rates;                      // orig_freq of every member (its encoding: bank.wire)
+  wekws::ResampleBankPlan bank;                    // (a member's rate: bank.members[m].orig; its encoding: bank.wire[m])
   std::vector<wekws::ResampleParams> P;            // of every member, as the device table holds them
   wekws::ResampleParams* d_params = nullptr;
   size_t lds = 0;
-  int out_i16 = 0, max_streams = 0, max_chunk = 0, hist_cap = 0, max_grid = 1, default_grid = 1;
+  int out_i16 = 0, max_grid = 1, default_grid = 1;
   std::vector<float*> d_live, d_full;              // per member
   std::vector<int32_t*> d_meta;                    // per member: first (n) | count (n)
-  int16_t* hist = nullptr;                         // (max_streams, 2, hist_cap), ping-ponged per stream
-  // the row table of a call travels through a ring of pinned host tables with device twins, as the single-rate handle's does;
-  // a slot too small for a one-shot call is replaced (a push never has more rows than streams)
+  int16_t* hist = nullptr;                         // (max_streams, 2, hist_cap) kept samples, ping-ponged per stream
+  // The row table of EVERY call, one-shot or push, travels through one ring of pinned host tables, each with its device twin and an
+  // event recorded behind the call that used it: calls queue back to back without a synchronise.  Slots are allocated for max_streams
+  // rows at create (a push never has more); a one-shot call with more rows replaces its slot.
   struct Slot {
     wekws::ResampleRow* h = nullptr;
     wekws::ResampleRow* d = nullptr;
@@ -78,11 +83,24 @@ struct wekws_hip_resample_bank {
   Slot ring[wekws::kResampleRing];
   int next = 0;
   std::mutex mu;
-  // per-stream state lives on the host: the outputs of every row are known without a device read-back
-  std::vector<int64_t> received, emitted, origin;
-  std::vector<int32_t> par, seen, flushed, member;
-  int32_t epoch = 0;
-  std::vector<wekws::ResampleStep> steps;          // of the push being planned
-  std::vector<wekws::ResampleRow> table;           // of the call being planned, in row order
-  std::vector<int32_t> members_of, order;          // of the call being planned: member of every row, rows sorted by member
+  wekws::ResampleStreams streams;                  // per-stream state lives on the host: no call reads the device back
+  const char* name() const { return kind == kSingle ? "resample" : "resample_bank"; }
 };
+
+namespace wekws {
+
+// what the C entry points of both families are (resample.hip, resample_bank.hip); h: a wekws_hip_resample
+int resample_create(int kind, const wekws_hip_resample_cfg* cfg, const int32_t* rates, const int32_t* encs, int num, void** out);
+void resample_destroy(void* h);
+int resample_max_out(void* h, int nmax, int flush);
+// member_of_row: NULL on a single-rate handle (every row member 0)
+int resample_compute(void* h, int source, const void* pcm, int B, int width, const int32_t* nsamp, const int32_t* member_of_row, void* out,
+                     int mcap, void* stream);
+int resample_push(void* h, int wire_call, const void* pcm, int B, int width, const int32_t* stream_ids, const int32_t* nsamp, int flush,
+                  void* out, int mcap, int32_t* counts, void* stream);
+// member: NULL for reset (every stream stays the member it is), or set_rate's
+int resample_reset(void* h, const int32_t* ids, int n, const int* member);
+int resample_counts(void* h, int id, int64_t counts_out[4]);
+
+}  // namespace wekws
+

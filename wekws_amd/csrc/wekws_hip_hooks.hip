@@ -2,7 +2,7 @@
 // libwekws_hip.so: the sinks are empty, the unit exports nothing and holds no kernel.  libwekws_hip_hooks.so (make hooks: this unit
 // compiled with -DWEKWS_TEST_HOOKS, every other object shared with the product library): the sinks record, and the unit carries the test
 // hooks: the route trace of a forward, the routing functions of route.h and the blob layout of blob_layout.h without a device, the GRU
-// epoch, a CU hog, the fbank's plan and table, the row softmax on chosen logits, the resampler's taps and plan (a rate bank's too, and the check of a bank call's rows, wire bytes included), the CTC decoder's keyword-set table.  Not part of the ABI in include/wekws_hip.h.
+// epoch, a CU hog, the fbank's plan and table, the row softmax on chosen logits, the resampler's taps and plan (a rate bank's too, and the check of a bank call's rows, wire bytes included; the stream planner of both handles through a script of calls), the CTC decoder's keyword-set table.  Not part of the ABI in include/wekws_hip.h.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -398,23 +398,90 @@ extern "C" int wekws_hip_debug_resample_schedule(int orig, int neu, int lpw, dou
   }
   return WEKWS_HIP_OK;
 }
-// Round the handle's taps -- the live table and the full one -- to fp16 values, in place: the negative control of the resampler's bar
-// (a kernel that took its taps at half precision must miss it).  There is no way back: destroy the handle afterwards.
-extern "C" int wekws_hip_debug_resample_round_taps_f16(wekws_hip_resample* r) {
+// Round the taps of one member of the handle -- its live table and its full one -- to fp16 values, in place: the negative control of
+// the resampler's bar (a kernel that took its taps at half precision must miss it).  There is no way back: destroy the handle afterwards.
+static int resample_round_taps_f16(wekws_hip_resample* r, int member) {
   if (!r) return fail(WEKWS_HIP_EINVAL, "NULL handle");
+  if (member < 0 || member >= int(r->P.size())) return fail(WEKWS_HIP_EINVAL, "member %d outside 0..%d", member, int(r->P.size()) - 1);
   DeviceGuard guard(r->device);
   if (!guard.ok) return fail(WEKWS_HIP_EDEVICE, "hipSetDevice(%d)", r->device);
-  std::vector<float> live(size_t(r->P.n) * r->P.stride), full(size_t(r->P.n) * r->P.K);
+  const wekws::ResampleParams& P = r->P[size_t(member)];
+  float* const d_live = r->d_live[size_t(member)];
+  float* const d_full = r->d_full[size_t(member)];
+  std::vector<float> live(size_t(P.n) * P.stride), full(size_t(P.n) * P.K);
   hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(live.data(), r->d_live, live.size() * sizeof(float), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(full.data(), r->d_full, full.size() * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(live.data(), d_live, live.size() * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(full.data(), d_full, full.size() * sizeof(float), hipMemcpyDeviceToHost);
   for (float& v : live) v = float(_Float16(v));
   for (float& v : full) v = float(_Float16(v));
-  if (e == hipSuccess) e = hipMemcpy(r->d_live, live.data(), live.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(r->d_full, full.data(), full.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_live, live.data(), live.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_full, full.data(), full.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "resample taps: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "%s taps: %s", r->name(), hipGetErrorString(e));
   return WEKWS_HIP_OK;
+}
+extern "C" int wekws_hip_debug_resample_round_taps_f16(wekws_hip_resample* r) { return resample_round_taps_f16(r, 0); }
+extern "C" int wekws_hip_debug_resample_bank_round_taps_f16(wekws_hip_resample* r, int member) { return resample_round_taps_f16(r, member); }
+
+// The stream planner of both handles (resample_streams.h), WITHOUT a device, through a script of calls on max_streams streams of a
+// bank of (rates, encs) pairs (encs NULL: every member s16).  single: planned as the single-rate handle plans (num must be 1).
+// script: n_ints int32, one call after the other:
+//   0, wire_call, B, width, flush, mcap, ids[B], nsamp[B]   a push (pcm at address 0), committed if it is accepted
+//   1, n, ids[n]                                            reset
+//   2, member, n, ids[n]                                    set_rate
+// Per call k < max_calls: outcome[4 k ..]: the refusal (ResampleStreamsRefusal; reset / set_rate: 1 for an id outside, else 0), the
+// row or index it is about (-1: none), the rows' refusal (ResampleBankRowRefusal), the most outputs of a row (of a call planned to its end);
+// rows (max_calls, max_streams, 12): the table of an accepted push as it is uploaded, in slot order; counts (max_calls, max_streams, 4):
+// wekws_hip_resample_counts of every stream after the call.  Returns the number of calls, or a negative code for a bank no resampler
+// has, a malformed script or more calls than max_calls.
+extern "C" int wekws_hip_debug_resample_streams_script(const int32_t* rates, const int32_t* encs, int num, int neu, int lpw, double rolloff,
+                                                       int single, int max_streams, int max_chunk, const int32_t* script, int n_ints,
+                                                       int max_calls, int64_t* outcome, int32_t* rows, int64_t* counts) {
+  static_assert(sizeof(wekws::ResampleRow) == 12 * sizeof(int32_t), "rows are 12 ints");
+  if (!script || !outcome || !rows || !counts || max_streams < 1 || max_chunk < 1 || (single && num != 1)) return WEKWS_HIP_EINVAL;
+  wekws::ResampleBankPlan bp;
+  int bad = -1;
+  const wekws::ResampleBankRefusal r = wekws::resample_bank_plan(rates, encs, num, neu, lpw, rolloff, &bp, &bad);
+  if (r == wekws::kResampleBankLds) return WEKWS_HIP_EUNSUPPORTED;
+  if (r != wekws::kResampleBankOk) return WEKWS_HIP_EINVAL;
+  wekws::ResampleStreams S;
+  wekws::resample_streams_init(&S, max_streams, max_chunk, wekws::resample_bank_hist_cap(bp), single != 0);
+  std::vector<int32_t> yields(max_streams, 0);
+  int k = 0;
+  for (int at = 0; at < n_ints; ++k) {
+    if (k >= max_calls) return WEKWS_HIP_EINVAL;
+    int64_t* const res = outcome + 4 * int64_t(k);
+    res[0] = 0; res[1] = -1; res[2] = 0; res[3] = 0;
+    const int op = script[at];
+    if (op == 0) {
+      if (at + 6 > n_ints) return WEKWS_HIP_EINVAL;
+      const int wire_call = script[at + 1], B = script[at + 2], width = script[at + 3], flush = script[at + 4], mcap = script[at + 5];
+      if (B < 0 || B > max_streams || at + 6 + 2 * B > n_ints) return WEKWS_HIP_EINVAL;
+      const int32_t* ids = script + at + 6;
+      const int32_t* nsamp = ids + B;
+      at += 6 + 2 * B;
+      res[0] = wekws::resample_streams_plan(&S, bp, wire_call, 0, width, ids, nsamp, B, flush, mcap, &bad);
+      res[1] = bad; res[2] = S.rows; res[3] = S.need_cap;
+      if (res[0] == wekws::kResampleStreamsOk) {
+        wekws::ResampleRow* const table = reinterpret_cast<wekws::ResampleRow*>(rows + int64_t(k) * max_streams * 12);
+        const int32_t* pos = wekws::resample_slot_positions(&S, S.members_of.data(), B, num);
+        wekws::resample_streams_push_rows(S, bp, wire_call, ids, nsamp, B, pos, table);
+        wekws::resample_streams_commit(&S, ids, nsamp, B, flush, yields.data());
+      }
+    } else if (op == 1 || op == 2) {
+      const int head = op == 2 ? 3 : 2;
+      if (at + head > n_ints) return WEKWS_HIP_EINVAL;
+      const int member = op == 2 ? script[at + 1] : -1, n = script[at + head - 1];
+      if (n < 0 || at + head + n > n_ints || (op == 2 && (member < 0 || member >= num))) return WEKWS_HIP_EINVAL;
+      res[1] = wekws::resample_streams_reset(&S, script + at + head, n, member);
+      res[0] = res[1] >= 0;
+      at += head + n;
+    } else {
+      return WEKWS_HIP_EINVAL;
+    }
+    for (int id = 0; id < max_streams; ++id) wekws::resample_streams_counts(S, id, counts + (int64_t(k) * max_streams + id) * 4);
+  }
+  return k;
 }
 
 // --------------------------------------------- resample bank ---------------------------------------------
@@ -472,31 +539,10 @@ extern "C" int wekws_hip_debug_resample_bank_check_rows(const int32_t* rates, co
 }
 // Cap the grid of the handle's launches (max_grid <= 0: the handle's own again), so that a small batch makes one workgroup walk tiles of
 // several members.
-extern "C" int wekws_hip_debug_resample_bank_set_grid(wekws_hip_resample_bank* r, int max_grid) {
+extern "C" int wekws_hip_debug_resample_bank_set_grid(wekws_hip_resample* r, int max_grid) {
   if (!r) return fail(WEKWS_HIP_EINVAL, "NULL handle");
   std::lock_guard<std::mutex> lk(r->mu);
   r->max_grid = max_grid > 0 ? max_grid : r->default_grid;
-  return WEKWS_HIP_OK;
-}
-// wekws_hip_debug_resample_round_taps_f16 for ONE member of a bank: its live table and its full one, in place, same sizes.
-extern "C" int wekws_hip_debug_resample_bank_round_taps_f16(wekws_hip_resample_bank* r, int member) {
-  if (!r) return fail(WEKWS_HIP_EINVAL, "NULL handle");
-  if (member < 0 || member >= int(r->P.size())) return fail(WEKWS_HIP_EINVAL, "member %d outside 0..%d", member, int(r->P.size()) - 1);
-  DeviceGuard guard(r->device);
-  if (!guard.ok) return fail(WEKWS_HIP_EDEVICE, "hipSetDevice(%d)", r->device);
-  const wekws::ResampleParams& P = r->P[size_t(member)];
-  float* const d_live = r->d_live[size_t(member)];
-  float* const d_full = r->d_full[size_t(member)];
-  std::vector<float> live(size_t(P.n) * P.stride), full(size_t(P.n) * P.K);
-  hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(live.data(), d_live, live.size() * sizeof(float), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(full.data(), d_full, full.size() * sizeof(float), hipMemcpyDeviceToHost);
-  for (float& v : live) v = float(_Float16(v));
-  for (float& v : full) v = float(_Float16(v));
-  if (e == hipSuccess) e = hipMemcpy(d_live, live.data(), live.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_full, full.data(), full.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "resample bank taps: %s", hipGetErrorString(e));
   return WEKWS_HIP_OK;
 }
 
