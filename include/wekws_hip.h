@@ -975,6 +975,54 @@ int wekws_hip_cmvn_stats_reset(void* h, void* stream);
 /* mean_stat, var_stat (dim) HOST doubles; counts = {frame_num, bad_rows}.  The one call that synchronises (with `stream`). */
 int wekws_hip_cmvn_stats_read(void* h, double* mean_stat, double* var_stat, int64_t counts[2], void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The criterion's backward pass  --  the gradient of wekws/model/loss.py::criterion with respect to its input, what
+ * torch's autograd gives for those statements, in closed form from what the forward kernels compute.  Conventions of the
+ * forward calls: stateless, device pointers, no call synchronises or allocates, a row's gradient depends on that row alone,
+ * every sum is a fixed-order reduction (the same inputs give the same bits on every run).  Every call writes
+ *     g * upstream / divisor
+ * into EVERY element of `grad` (so it may be uninitialised): g the gradient of the row's own loss (of the row's K loss terms
+ * for max-pooling), exactly 0 in the frames t >= lengths[b];  upstream: a DEVICE pointer to one float, read by the kernel --
+ * autograd's grad_output -- NULL = 1;  divisor: an int >= 1 -- B gives the gradient of the batch loss the reference returns,
+ * 1 the rows' own gradients.  WEKWS_HIP_EINVAL (nothing launched) for a NULL pointer, a size < 1 or divisor < 1.
+ * ------------------------------------------------------------------------------------------*/
+/*
+ * max_pooling_loss (loss.py:26-71) with respect to the posteriors; arguments as wekws_hip_criterion_max_pooling.
+ *   column target[b]:  p_t = clamp(masked_t ? 0 : x_t, 1e-8, 1), masked_t = (t >= len or t < min_duration);  P = max_t p_t over
+ *     ALL T frames, n = #{t : p_t == P} (masked frames count);  grad = -(1 / P) / n where p_t == P, the frame is not masked and
+ *     1e-8 <= x_t <= 1 (the clamp's gate, inclusive: a winning 1.25 gets 0, a winning 1.0 gets -1), else 0
+ *   other columns:  q_t = clamp(t >= len ? 1 : 1 - x_t, 1e-8, 1), Q = min_t q_t, n its ties over all T frames;
+ *     grad = +(1 / Q) / n where q_t == Q, t < len and 1e-8 <= 1 - x_t <= 1, else 0
+ * torch's full max() / min() split the gradient evenly among ties; so does this.  A NaN in an unmasked frame of a column
+ * makes its pooled value NaN and the column's gradient all zeros (autograd routes the gradient to the NaN frames, where the
+ * clamp's gate is false).  grad (B, T, K).
+ */
+int wekws_hip_criterion_max_pooling_grad(const float* scores, int B, int T, int K, const int32_t* target, const int32_t* lengths,
+                                         int min_duration, const float* upstream, int divisor, float* grad /* (B,T,K) */,
+                                         void* stream);
+/*
+ * cross_entropy (loss.py:178) with respect to the logits: grad (B, D) = softmax(row) - [d == target], from one read of the
+ * row (running max, rescaled sum).  A target outside [0, D) or a NaN logit makes the whole row NaN (the forward's deviation).
+ */
+int wekws_hip_criterion_ce_grad(const float* logits, int B, int D, const int32_t* target, const float* upstream, int divisor,
+                                float* grad /* (B,D) */, void* stream);
+/*
+ * ctc_loss (loss.py:154-162) with its gradient with respect to the logits; arguments and limits as wekws_hip_ctc_loss.
+ *   loss_rows (B), loss (1): bit-identical to wekws_hip_ctc_loss on the same inputs (the same kernels).
+ *   grad (B, T, V): on the frames t < len  softmax_t(v) - occ_t(v),  occ_t(v) = sum over the extended states s with
+ *     l'_s == v of exp(alpha_t(s) + beta_t(s) - lp_t(v) + nll_b) -- alpha and beta in double, a class's states added in
+ *     ascending order by one owner (no atomics);  0 on the frames t >= len;  NaN on the valid frames of a row no alignment
+ *     fits (nll = +Inf, as torch) and of a row with a label outside [1, V) or a NaN logit;  all zeros for len == 0.
+ *   workspace: wekws_hip_ctc_loss_grad_workspace_bytes(B, T, Lmax) bytes of device scratch, 8-byte aligned: the double alphas /
+ *     occupancies of every frame (B T (2 Lmax + 1) doubles), the forward's log-probabilities, per frame the max and log-sum.
+ * Five launches; the logits are read twice (the log-sum pass, the gradient pass), the gradient is written once.
+ */
+size_t wekws_hip_ctc_loss_grad_workspace_bytes(int B, int T, int Lmax);
+int wekws_hip_ctc_loss_grad(const float* logits, int B, int T, int V, const int32_t* targets, int Lmax,
+                            const int32_t* logit_lengths, const int32_t* target_lengths, const float* upstream, int divisor,
+                            float* loss_rows, float* loss, float* grad /* (B,T,V) */, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,12 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "wekws_hip_ctc_edit_distance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
+    "wekws_hip_criterion_max_pooling_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "wekws_hip_criterion_ce_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "wekws_hip_ctc_loss_grad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "wekws_hip_ctc_loss_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "wekws_hip_stream_frontend_create": (C.c_int, [C.POINTER(StreamFrontendCfg), C.POINTER(C.c_void_p)]),
     "wekws_hip_stream_frontend_create_mfcc": (C.c_int, [C.POINTER(StreamFrontendCfg), C.c_int, C.c_float, C.POINTER(C.c_void_p)]),
     "wekws_hip_stream_frontend_destroy": (None, [C.c_void_p]),

@@ -1,6 +1,13 @@
-"""The validation criterion on the device: wekws/model/loss.py::criterion (``max_pooling``, ``ce``, ``ctc``), forward only --
-what Executor.cv / Executor.test call after every forward -- through ``wekws_hip_criterion_*`` / ``wekws_hip_ctc_loss`` /
-``wekws_hip_ctc_edit_distance`` (csrc/criterion.hip.h).
+"""The criterion on the device: wekws/model/loss.py::criterion (``max_pooling``, ``ce``, ``ctc``) -- what Executor.cv /
+Executor.test call after every forward -- through ``wekws_hip_criterion_*`` / ``wekws_hip_ctc_loss`` /
+``wekws_hip_ctc_edit_distance`` (csrc/criterion.hip.h), and its backward pass through ``wekws_hip_criterion_*_grad`` /
+``wekws_hip_ctc_loss_grad`` (csrc/criterion_grad.hip.h).
+
+When ``logits.requires_grad and torch.is_grad_enabled()`` the returned loss carries a ``grad_fn``: the forward is the very same
+call (the same buffers, the same bits), and ``backward`` runs the gradient kernel with autograd's ``grad_output`` as a device
+pointer and B as the divisor, so ``criterion(...)[0].backward()`` works for any torch module that produced ``logits`` on the
+device.  ``ce`` and ``ctc`` differentiate with respect to the logits, ``max_pooling`` with respect to the posteriors it is
+given; the accuracy outputs carry no gradient.  ``*_grad_device`` return the raw gradient tensors.
 
 ``criterion(type, logits, target, lengths, target_lengths=None, min_duration=0, validation=False)`` has the reference's
 signature and returns ``(loss, acc)``: loss a 0-dim float32 device tensor, acc a Python float (reading it synchronises, as
@@ -19,6 +26,8 @@ from typing import Dict, NamedTuple, Optional, Tuple
 import torch
 
 from wekws_amd import _capi
+
+_Function = torch.autograd.Function
 
 
 class MaxPoolingResult(NamedTuple):
@@ -75,8 +84,164 @@ def _scalar(v: int, dev: torch.device) -> torch.Tensor:
     return torch.full((), float(v), dtype=torch.float64, device=dev)
 
 
+def _wants_grad(logits) -> bool:
+    return isinstance(logits, torch.Tensor) and logits.requires_grad and torch.is_grad_enabled()
+
+
+def _upstream(upstream, dev: torch.device) -> Optional[torch.Tensor]:
+    """None (the library reads 1), or one float32 on the device: a tensor is passed on by pointer, never read here."""
+    if upstream is None:
+        return None
+    if isinstance(upstream, torch.Tensor):
+        if not upstream.is_cuda or upstream.numel() != 1:
+            raise ValueError("upstream must be one float on a ROCm device (no CPU fallback)")
+        return upstream.to(device=dev, dtype=torch.float32).contiguous()
+    return torch.full((), float(upstream), dtype=torch.float32, device=dev)
+
+
+def _divisor(divisor, B: int) -> int:
+    d = B if divisor is None else int(divisor)
+    if d < 1:
+        raise ValueError(f"divisor must be >= 1, got {d}")
+    return d
+
+
+def max_pooling_grad_device(logits: torch.Tensor, target: torch.Tensor, lengths: Optional[torch.Tensor], min_duration: int = 0,
+                            upstream=None, divisor: Optional[int] = None) -> torch.Tensor:
+    """d(max_pooling_loss) / d(logits) * upstream / divisor, (B, T, K) float32; ``divisor`` None: B (the batch loss)."""
+    x = _f32(logits.detach(), 3, "max_pooling_grad")
+    B, T, K = (int(v) for v in x.shape)
+    dev = x.device
+    tg = _i32(target, B, dev, "target")
+    ln = None if lengths is None else _i32(lengths, B, dev, "lengths")
+    up = _upstream(upstream, dev)
+    grad = torch.empty((B, T, K), dtype=torch.float32, device=dev)
+    _capi.check(_capi.load().wekws_hip_criterion_max_pooling_grad(
+        x.data_ptr(), B, T, K, tg.data_ptr(), ln.data_ptr() if ln is not None else None, int(min_duration),
+        up.data_ptr() if up is not None else None, _divisor(divisor, B), grad.data_ptr(), _stream(dev)),
+        "wekws_hip_criterion_max_pooling_grad")
+    return grad
+
+
+def cross_entropy_grad_device(logits: torch.Tensor, target: torch.Tensor, upstream=None,
+                              divisor: Optional[int] = None) -> torch.Tensor:
+    """d(cross_entropy) / d(logits) * upstream / divisor, (B, D) float32."""
+    x = _f32(logits.detach(), 2, "cross_entropy_grad")
+    B, D = (int(v) for v in x.shape)
+    dev = x.device
+    tg = _i32(target, B, dev, "target")
+    up = _upstream(upstream, dev)
+    grad = torch.empty((B, D), dtype=torch.float32, device=dev)
+    _capi.check(_capi.load().wekws_hip_criterion_ce_grad(x.data_ptr(), B, D, tg.data_ptr(), up.data_ptr() if up is not None else None,
+                                                         _divisor(divisor, B), grad.data_ptr(), _stream(dev)),
+                "wekws_hip_criterion_ce_grad")
+    return grad
+
+
+def ctc_loss_grad_device(logits: torch.Tensor, target: torch.Tensor, logits_lengths: torch.Tensor, target_lengths: torch.Tensor,
+                         upstream=None, divisor: Optional[int] = None):
+    """-> (grad (B, T, V), loss_rows (B), loss ()): d(ctc_loss) / d(logits) * upstream / divisor, and the loss with the bits
+    of ``ctc_loss_device``."""
+    x = _f32(logits.detach(), 3, "ctc_loss_grad")
+    B, T, V = (int(v) for v in x.shape)
+    dev = x.device
+    if not isinstance(target, torch.Tensor) or not target.is_cuda:
+        raise ValueError("target must be a tensor on a ROCm device (no CPU fallback)")
+    tg = target.to(device=dev, dtype=torch.int32).reshape(B, -1).contiguous()
+    Lmax = int(tg.size(1))
+    ll = _i32(logits_lengths, B, dev, "logits_lengths")
+    tl = _i32(target_lengths, B, dev, "target_lengths")
+    up = _upstream(upstream, dev)
+    lib = _capi.load()
+    rows = torch.empty((B,), dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    grad = torch.empty((B, T, V), dtype=torch.float32, device=dev)
+    nbytes = int(lib.wekws_hip_ctc_loss_grad_workspace_bytes(B, T, Lmax))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    _capi.check(lib.wekws_hip_ctc_loss_grad(x.data_ptr(), B, T, V, tg.data_ptr() if Lmax else None, Lmax, ll.data_ptr(), tl.data_ptr(),
+                                            up.data_ptr() if up is not None else None, _divisor(divisor, B), rows.data_ptr(),
+                                            loss.data_ptr(), grad.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)),
+                "wekws_hip_ctc_loss_grad")
+    return grad, rows, loss
+
+
+class _MaxPoolingLoss(_Function):
+    """loss = max_pooling_loss(logits): the forward call unchanged; backward: the gradient kernel, grad_output by pointer."""
+
+    @staticmethod
+    def forward(ctx, logits, target, lengths, min_duration, box):
+        r = _max_pooling_forward(logits, target, lengths, min_duration)
+        ctx.save_for_backward(logits, target, *([] if lengths is None else [lengths]))
+        ctx.min_duration = min_duration
+        box.append(r)
+        return r.loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        logits, target, *rest = ctx.saved_tensors
+        g = max_pooling_grad_device(logits, target, rest[0] if rest else None, ctx.min_duration, upstream=grad_output)
+        return g, None, None, None, None
+
+
+class _CrossEntropyLoss(_Function):
+
+    @staticmethod
+    def forward(ctx, logits, target, box):
+        r = _cross_entropy_forward(logits, target)
+        ctx.save_for_backward(logits, target)
+        box.append(r)
+        return r.loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        logits, target = ctx.saved_tensors
+        return cross_entropy_grad_device(logits, target, upstream=grad_output), None, None
+
+
+class _CtcLoss(_Function):
+
+    @staticmethod
+    def forward(ctx, logits, target, logits_lengths, target_lengths, need_acc, box):
+        r = _ctc_loss_forward(logits, target, logits_lengths, target_lengths, need_acc)
+        ctx.save_for_backward(logits, target, logits_lengths, target_lengths)
+        box.append(r)
+        return r.loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        logits, target, logits_lengths, target_lengths = ctx.saved_tensors
+        g = ctc_loss_grad_device(logits, target, logits_lengths, target_lengths, upstream=grad_output)[0]
+        return g, None, None, None, None, None
+
+
 def max_pooling_loss_device(logits: torch.Tensor, target: torch.Tensor, lengths: Optional[torch.Tensor],
                             min_duration: int = 0) -> MaxPoolingResult:
+    if not _wants_grad(logits):
+        return _max_pooling_forward(logits, target, lengths, min_duration)
+    box = []
+    loss = _MaxPoolingLoss.apply(logits, target, lengths, int(min_duration), box)
+    return box[0]._replace(loss=loss)
+
+
+def cross_entropy_device(logits: torch.Tensor, target: torch.Tensor) -> CrossEntropyResult:
+    if not _wants_grad(logits):
+        return _cross_entropy_forward(logits, target)
+    box = []
+    loss = _CrossEntropyLoss.apply(logits, target, box)
+    return box[0]._replace(loss=loss)
+
+
+def ctc_loss_device(logits: torch.Tensor, target: torch.Tensor, logits_lengths: torch.Tensor,
+                    target_lengths: torch.Tensor, need_acc: bool = False) -> CtcResult:
+    if not _wants_grad(logits):
+        return _ctc_loss_forward(logits, target, logits_lengths, target_lengths, need_acc)
+    box = []
+    loss = _CtcLoss.apply(logits, target, logits_lengths, target_lengths, bool(need_acc), box)
+    return box[0]._replace(loss=loss)
+
+
+def _max_pooling_forward(logits: torch.Tensor, target: torch.Tensor, lengths: Optional[torch.Tensor],
+                         min_duration: int = 0) -> MaxPoolingResult:
     x = _f32(logits, 3, "max_pooling_loss")
     B, T, K = (int(v) for v in x.shape)
     dev = x.device
@@ -93,7 +258,7 @@ def max_pooling_loss_device(logits: torch.Tensor, target: torch.Tensor, lengths:
     return MaxPoolingResult(loss, num.to(torch.float64) / _scalar(B, dev), pooled, terms, correct, num)
 
 
-def cross_entropy_device(logits: torch.Tensor, target: torch.Tensor) -> CrossEntropyResult:
+def _cross_entropy_forward(logits: torch.Tensor, target: torch.Tensor) -> CrossEntropyResult:
     x = _f32(logits, 2, "cross_entropy")
     B, D = (int(v) for v in x.shape)
     dev = x.device
@@ -121,8 +286,8 @@ def _decoder(dev: torch.device, vocab: int):
     return _decoders[key]
 
 
-def ctc_loss_device(logits: torch.Tensor, target: torch.Tensor, logits_lengths: torch.Tensor,
-                    target_lengths: torch.Tensor, need_acc: bool = False) -> CtcResult:
+def _ctc_loss_forward(logits: torch.Tensor, target: torch.Tensor, logits_lengths: torch.Tensor,
+                      target_lengths: torch.Tensor, need_acc: bool = False) -> CtcResult:
     x = _f32(logits, 3, "ctc_loss")
     B, T, V = (int(v) for v in x.shape)
     dev = x.device

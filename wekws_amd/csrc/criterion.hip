@@ -25,10 +25,11 @@ int launch_criterion_ce(const float* logits, int B, int D, const int32_t* target
 }
 
 int launch_ctc_loss(const float* logits, int B, int T, int V, const int32_t* targets, int Lmax, const int32_t* logit_lengths,
-                    const int32_t* target_lengths, float* loss_rows, float* loss, float* probs, float* lp, hipStream_t stream) {
+                    const int32_t* target_lengths, float* loss_rows, float* loss, float* probs, float* lp, float* stats,
+                    hipStream_t stream) {
   const int64_t frames = int64_t(B) * T;
   hipLaunchKernelGGL(ctc_loss_lp_kernel, dim3(unsigned((frames + 3) / 4)), dim3(256), 0, stream, logits, B, T, V, targets, Lmax,
-                     logit_lengths, target_lengths, lp, probs);
+                     logit_lengths, target_lengths, lp, probs, stats);
   const int W = 2 * Lmax + 1;
   const int threads = W <= 64 ? 64 : 256;                    // one wave needs no cross-wave barrier
   const size_t lds = (size_t(2) * W + size_t(Lmax > 0 ? Lmax : 1)) * 4;
@@ -106,7 +107,7 @@ int wekws_hip_ctc_loss(const float* logits, int B, int T, int V, const int32_t* 
   if (workspace_bytes < need)
     return fail(WEKWS_HIP_EINVAL, "ctc_loss: workspace of %zu bytes, need %zu (wekws_hip_ctc_loss_workspace_bytes)", workspace_bytes, need);
   if (wekws::launch_ctc_loss(logits, B, T, V, targets, Lmax, logit_lengths, target_lengths, loss_rows, loss, probs,
-                             static_cast<float*>(workspace), static_cast<hipStream_t>(stream)))
+                             static_cast<float*>(workspace), nullptr, static_cast<hipStream_t>(stream)))
     return launch_fail("ctc_loss");
   return WEKWS_HIP_OK;
 }

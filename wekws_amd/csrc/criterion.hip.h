@@ -13,13 +13,10 @@
 // The pooled values and the correctness flags involve comparisons only and are bit-exact against the reference; fmaxf /
 // fminf drop a NaN where torch's max / min / clamp keep it, so NaNs travel in flags of their own.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "criterion_util.hip.h"
 
 namespace wekws {
 
-constexpr int kCritWave = 64;
-constexpr int kCtcLossMaxLabels = 3000;     // LDS of the alpha kernel: (2 (2 L + 1) + L) * 4 bytes <= 64 KiB
 constexpr int kEditMaxLabels = 3000;        // LDS of the edit-distance kernel: 3 (L + 1) * 4 bytes
 constexpr int kEditMaxPathBeam = 64;        // wekws_hip_ctc_kws_create's limit
 
@@ -28,9 +25,6 @@ inline size_t edit_beam_bytes(int PB, int cap) {
   const size_t pc = size_t(PB) * cap;
   return (8 + 4 * size_t((PB + 1) & ~1) + 16 * size_t(PB) + 8 * pc + 4 * (pc & 1) + 8 * pc + 15) & ~size_t(15);
 }
-
-__device__ __forceinline__ float crit_nan() { return __int_as_float(0x7fc00000); }
-__device__ __forceinline__ int crit_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // ------------------------------------------------------------------------------------------------ max pooling
 // One wave per utterance, one pass over its (T * K) row.  K <= 64: the wave reads 64 / K whole frames per step (lane = frame
@@ -143,14 +137,13 @@ __global__ __launch_bounds__(256) void criterion_ce_kernel(const float* __restri
 // ------------------------------------------------------------------------------------------------ CTC loss
 // Kernel one: per valid frame the row's log-sum-exp in ONE pass over the logits (running max and rescaled sum per lane,
 // merged across the wave), then only lp[b][t][0 .. S_b] = log-probability of the blank and of the row's own labels
-// (and, if asked for, the frame's posteriors exp(lp) for the beam search of acc_utterance).
-__device__ __forceinline__ float crit_scale(float from, float to) { return from == -INFINITY ? 0.0f : expf(from - to); }
-
+// (and, if asked for, the frame's posteriors exp(lp) for the beam search of acc_utterance, and the frame's max and
+// log-sum for the gradient pass, criterion_grad.hip.h).
 __global__ __launch_bounds__(256) void ctc_loss_lp_kernel(const float* __restrict__ logits, int B, int T, int V,
                                                           const int32_t* __restrict__ targets, int Lmax,
                                                           const int32_t* __restrict__ logit_lengths,
                                                           const int32_t* __restrict__ target_lengths, float* __restrict__ lp,
-                                                          float* __restrict__ probs) {
+                                                          float* __restrict__ probs, float* __restrict__ stats) {
   const int64_t f = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);       // frame = b * T + t
   if (f >= int64_t(B) * T) return;
   const int lane = threadIdx.x & 63;
@@ -173,6 +166,7 @@ __global__ __launch_bounds__(256) void ctc_loss_lp_kernel(const float* __restric
     m = nm;
   }
   const float ls = logf(s);                                  // lp = (x - max) - log(sum): near 0 it keeps the bits that x - (max + log(sum)) loses
+  if (stats && lane == 0) { stats[2 * f] = m; stats[2 * f + 1] = ls; }
   const int S = crit_clampi(target_lengths[b], 0, Lmax);
   float* o = lp + f * (Lmax + 1);
   const int32_t* lab = targets + int64_t(b) * Lmax;
@@ -321,8 +315,6 @@ int launch_criterion_max_pooling(const float* scores, int B, int T, int K, const
                                  int32_t* num_correct, hipStream_t stream);
 int launch_criterion_ce(const float* logits, int B, int D, const int32_t* target, float* loss_rows, int32_t* pred,
                         int32_t* correct, float* loss, int32_t* num_correct, hipStream_t stream);
-int launch_ctc_loss(const float* logits, int B, int T, int V, const int32_t* targets, int Lmax, const int32_t* logit_lengths,
-                    const int32_t* target_lengths, float* loss_rows, float* loss, float* probs, float* lp, hipStream_t stream);
 int launch_ctc_edit_distance(const char* beams, size_t beam_stride, int PB, int cap, int B, const int32_t* targets, int Lmax,
                              const int32_t* target_lengths, int32_t* dist, int32_t* totals, hipStream_t stream);
 

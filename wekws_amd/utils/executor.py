@@ -2,10 +2,15 @@
 its running totals in float64 device scalars, so a whole evaluation moves two numbers to the host.  The totals follow the
 reference statement by statement (``num_seen_utts`` starts at 1; a batch whose loss is not finite is skipped; ``loss.item()
 * num_utts`` and ``acc * num_utts`` are float64 products added in batch order), so the result equals the host loop over the
-same per-batch values bit for bit (tests/test_criterion_oracle.py).  Training is out of scope: ``train`` raises."""
+same per-batch values bit for bit (tests/test_criterion_oracle.py).  ``Executor`` stays the evaluation loop of a packed,
+inference-only KWSModel and its ``train`` raises; ``TrainExecutor.train`` is Executor.train of wekws/utils/executor.py:28-68
+for a torch module on the device, with the criterion and its backward pass on the device (wekws_amd.criterion)."""
 from __future__ import annotations
 
+import logging
+
 import torch
+from torch.nn.utils import clip_grad_norm_
 
 from wekws_amd.criterion import criterion_device
 
@@ -43,7 +48,7 @@ class Executor:
         self.step = 0
 
     def train(self, model, optimizer, data_loader, device, writer, args):
-        raise NotImplementedError("wekws_amd is an inference library: the criterion has no backward pass, train with the reference")
+        raise NotImplementedError("Executor runs packed, inference-only models: train a torch module with TrainExecutor")
 
     def cv(self, model, data_loader, device, args):
         model.eval()
@@ -67,3 +72,38 @@ class Executor:
 
     def test(self, model, data_loader, device, args):
         return self.cv(model, data_loader, device, args)
+
+
+class TrainExecutor(Executor):
+    """One epoch of training, statement by statement what the reference's Executor.train does -- ``min_duration`` and
+    ``criterion`` from ``args``, zero_grad, backward, ``clip_grad_norm_(model.parameters(), args.get('grad_clip', 50.0))``, a
+    step only when the norm is finite -- with ``criterion_device``: nothing but the log line every ``log_interval`` batches
+    (formatted only when DEBUG logging is on) reads a value (``torch.isfinite(grad_norm)`` in the ``if`` is the reference's own read).  ``model`` is any torch module
+    returning ``(logits, cache)``; differentiating it is torch's job."""
+
+    def train(self, model, optimizer, data_loader, device, writer, args):
+        model.train()
+        clip = args.get('grad_clip', 50.0)
+        log_interval = args.get('log_interval', 10)
+        epoch = args.get('epoch', 0)
+        min_duration = args.get('min_duration', 0)
+        for batch_idx, batch_dict in enumerate(data_loader):
+            target = batch_dict['target']
+            target = target[:, 0] if target.shape[1] == 1 else target
+            feats = batch_dict['feats'].to(device)
+            target = target.to(device)
+            feats_lengths = batch_dict['feats_lengths'].to(device)
+            label_lengths = batch_dict['target_lengths'].to(device)
+            num_utts = feats_lengths.size(0)
+            if num_utts == 0:
+                continue
+            logits, _ = model(feats)
+            r = criterion_device(args.get('criterion', 'max_pooling'), logits, target, feats_lengths,
+                                 target_lengths=label_lengths, min_duration=min_duration, validation=False)
+            optimizer.zero_grad()
+            r.loss.backward()
+            grad_norm = clip_grad_norm_(model.parameters(), clip)
+            if torch.isfinite(grad_norm):
+                optimizer.step()
+            if batch_idx % log_interval == 0 and logging.getLogger().isEnabledFor(logging.DEBUG):
+                logging.debug('TRAIN Batch {}/{} loss {:.8f} acc {:.8f}'.format(epoch, batch_idx, r.loss.item(), float(r.acc)))
