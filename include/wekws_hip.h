@@ -1023,6 +1023,58 @@ int wekws_hip_ctc_loss_grad(const float* logits, int B, int T, int V, const int3
                             float* loss_rows, float* loss, float* grad /* (B,T,V) */, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The optimiser step  --  the last three statements of the reference's training step (wekws/utils/executor.py:58-60 with the
+ * optimiser of wekws/bin/train.py:201):  grad_norm = clip_grad_norm_(parameters, clip);  if isfinite(grad_norm):
+ * Adam.step()  --  over four flat float32 buffers of n elements each that the caller owns: params, grads, exp_avg,
+ * exp_avg_sq.  The kernels take the four base pointers and n, never a table of per-tensor pointers.  Stateless calls, device
+ * pointers, no call synchronises, allocates or reads a value on the host; every sum is a fixed-order reduction over tiles of a
+ * fixed size (the bits of a step are a function of the buffers, the state block and the hyper-parameters alone; no
+ * floating-point atomics).
+ *
+ * The state block: wekws_hip_optim_state_bytes() = 64 bytes of device memory, 16-byte aligned, zeroed by the caller before the
+ * first step and from then on written by the calls alone:
+ *     offset  0  int64   step         steps applied so far
+ *             8  int64   skipped      steps not applied because the norm was not finite
+ *            16  double  norm         the 2-norm of grads at the last call, from the double sum
+ *            24  double  bc1          1 - beta1^step            (pow in double)
+ *            32  double  bc2sqrt      sqrt(1 - beta2^step)
+ *            40  float   coef         min(1, max_norm / (norm + 1e-6)) of the last call; exactly 1 for max_norm = +Inf
+ *            44  float   norm_f32     float32(norm): what clip_grad_norm_ returns
+ *            48  int32   apply        1: the last call stepped;  0: it wrote nothing but this block
+ *            52  int32   finite       isfinite(norm_f32)
+ *            56  float   step_size    float32(lr / bc1) of the last applied step
+ *            60  float   bc2sqrt_f32  float32(bc2sqrt)
+ *
+ * A step, three launches (a fourth for more than 256 tiles):
+ *     norm = sqrt(sum g^2), every square and every add in double;  finite = isfinite(float32(norm));
+ *     apply = finite || !skip_nonfinite;  if apply: step += 1, else: skipped += 1 and nothing else is written;
+ *     g~ = coef g + weight_decay p;  m' = beta1 m + (1 - beta1) g~;  v' = beta2 v + (1 - beta2) g~^2;
+ *     p' = p - (lr / bc1) m' / (sqrt(v') / bc2sqrt + eps)
+ * in float32, with correctly rounded sqrt and division: torch's single-tensor Adam.  grads is left as it was (the reference
+ * scales it in place; here the coefficient is folded into the update).  The norm is summed in double: a gradient whose float32
+ * sum of squares overflows while its norm is a finite float32 is clipped and stepped, where the reference skips the step.
+ *
+ * The hyper-parameters are doubles, as torch holds them: Adam forms 1 - beta2 in double before it rounds, and a float32
+ * 0.999 would put that factor off by 1.3e-5 relative.
+ * ------------------------------------------------------------------------------------------*/
+/* Without a device: out = {floats a tile of the norm holds (a constant), tiles of n floats, bytes of workspace a call needs:
+ * one double a tile and, for more than 256 tiles, one more per 256 tiles, rounded up to 16}.  WEKWS_HIP_EINVAL for n outside
+ * 1 .. 2^28. */
+int wekws_hip_optim_plan(int64_t n, int64_t out[3]);
+size_t wekws_hip_optim_state_bytes(void);
+/* WEKWS_HIP_EINVAL, before any launch, for: a NULL pointer; n outside 1 .. 2^28; a pointer that is not 16-byte aligned; two of
+ * the four buffers overlapping; lr, eps or weight_decay negative, NaN or infinite; a beta outside [0, 1); max_norm <= 0 or NaN
+ * (+Inf: no clipping); a workspace smaller than wekws_hip_optim_plan says.  skip_nonfinite 0: the step is applied whatever the
+ * norm (plain Adam.step()). */
+int wekws_hip_clip_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                             void* state /* device, zero-initialised by the caller before the first step */, double lr, double beta1,
+                             double beta2, double eps, double weight_decay, double max_norm /* +Inf: no clipping */,
+                             int skip_nonfinite, void* workspace, size_t workspace_bytes, void* stream);
+/* *norm_out (device) = float32 of the same norm, by the same two (three) launches: the bits of `norm_f32` above. */
+int wekws_hip_grad_norm(const float* grads, int64_t n, float* norm_out /* device */, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,11 @@ SIGNATURES = {
     "wekws_hip_cmvn_stats_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "wekws_hip_cmvn_stats_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "wekws_hip_cmvn_stats_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]),
+    "wekws_hip_optim_plan": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
+    "wekws_hip_optim_state_bytes": (C.c_size_t, []),
+    "wekws_hip_clip_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_double,
+                                           C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "wekws_hip_grad_norm": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 OPTIONS = {"w16": 0, "mdtc16": 1, "stream": 2, "mm": 3, "head_slices": 4, "g16": 5, "envelope": 6, "gru_pipe": 7}   # enum wekws_hip_option

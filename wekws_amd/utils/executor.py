@@ -78,8 +78,10 @@ class TrainExecutor(Executor):
     """One epoch of training, statement by statement what the reference's Executor.train does -- ``min_duration`` and
     ``criterion`` from ``args``, zero_grad, backward, ``clip_grad_norm_(model.parameters(), args.get('grad_clip', 50.0))``, a
     step only when the norm is finite -- with ``criterion_device``: nothing but the log line every ``log_interval`` batches
-    (formatted only when DEBUG logging is on) reads a value (``torch.isfinite(grad_norm)`` in the ``if`` is the reference's own read).  ``model`` is any torch module
-    returning ``(logits, cache)``; differentiating it is torch's job."""
+    (formatted only when DEBUG logging is on) reads a value (``torch.isfinite(grad_norm)`` in the ``if`` is the reference's own read).  With an
+    optimiser that has ``clip_and_step`` (wekws_amd.optim.ClipAdam) those three statements are that one call, on the device, and
+    the step reads nothing on the host.  ``model`` is any torch module returning ``(logits, cache)``; differentiating it is
+    torch's job."""
 
     def train(self, model, optimizer, data_loader, device, writer, args):
         model.train()
@@ -102,8 +104,11 @@ class TrainExecutor(Executor):
                                  target_lengths=label_lengths, min_duration=min_duration, validation=False)
             optimizer.zero_grad()
             r.loss.backward()
-            grad_norm = clip_grad_norm_(model.parameters(), clip)
-            if torch.isfinite(grad_norm):
-                optimizer.step()
+            if hasattr(optimizer, 'clip_and_step'):
+                grad_norm = optimizer.clip_and_step(clip)          # wekws_amd.optim.ClipAdam: the three statements on the device
+            else:
+                grad_norm = clip_grad_norm_(model.parameters(), clip)
+                if torch.isfinite(grad_norm):
+                    optimizer.step()
             if batch_idx % log_interval == 0 and logging.getLogger().isEnabledFor(logging.DEBUG):
                 logging.debug('TRAIN Batch {}/{} loss {:.8f} acc {:.8f}'.format(epoch, batch_idx, r.loss.item(), float(r.acc)))
