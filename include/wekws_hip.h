@@ -1075,6 +1075,37 @@ int wekws_hip_clip_adam_step(float* params, const float* grads, float* exp_avg, 
 int wekws_hip_grad_norm(const float* grads, int64_t n, float* norm_out /* device */, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The trainable FSMN memory block  --  FSMNBlock.forward with an empty cache (wekws/model/fsmn.py:214-253) and its autograd, as a
+ * causal sparse FIR per channel.  x, y, grad_y, grad_x: (B, T, D) float32, contiguous;  w_left: (D, lorder), the memory of
+ * conv_left.weight (D, 1, lorder, 1);  w_right: (D, rorder), the same for conv_right.weight.  With R = rorder * rstride and
+ * x[b, n, d] = 0 for n < 0:
+ *     y[b,t,d]   = x[b,t-R,d] + sum_i w_left[d,i] x[b, t-R-(lorder-1-i) lstride, d] + sum_j w_right[d,j] x[b, t-R+(j+1) rstride, d]
+ *     grad_x     = the same taps run the other way over grad_y (terms past the row's end do not exist)
+ *     grad_w_*   = the sums over b and t of grad_y times the frame of x the tap reads
+ * Products are exact float32 fmaf in one order: skip term, left taps with i ascending, right taps with j ascending; the zeros
+ * before frame 0 are arithmetic zeros (an Inf or NaN tap makes the first frames NaN, as the reference's padding does).  A row's
+ * y and grad_x depend on that row alone.  The tap gradients are summed in double, per tile of 128 frames of a row in ascending
+ * frame order, then over the tiles in a fixed order, and rounded to float32 once: their bits are a function of the inputs and
+ * the shape.  Stateless calls, device pointers, no floating-point atomics; no call synchronises, allocates or reads on the host;
+ * every element of every output is written.  16-byte accesses where D % 4 == 0 and the tensors' bases are 16-byte aligned,
+ * scalar accesses with the same bits otherwise.
+ *
+ * Limits (WEKWS_HIP_EINVAL, before any launch): B, T, D >= 1;  lorder, rorder >= 1;  strides >= 1;  lorder + rorder <= 32;
+ * a window R + (lorder-1) lstride + 1 of at most 256 frames.  forward: one launch;  backward: at most three.
+ * ------------------------------------------------------------------------------------------*/
+/* Without a device: bytes of workspace a backward call that wants the tap gradients needs: one double per tile of 128 frames of a
+ * row, tap and channel, rounded up to 16.  0 on bad arguments. */
+size_t wekws_hip_fsmn_memory_workspace_bytes(int B, int T, int D, int lorder, int rorder);
+int wekws_hip_fsmn_memory_forward(const float* x, int B, int T, int D, const float* w_left, int lorder, int lstride,
+                                  const float* w_right, int rorder, int rstride, float* y, void* stream);
+/* grad_x NULL: not wanted.  grad_w_left and grad_w_right: both or neither (NULL: not wanted; then workspace may be NULL).  Also
+ * WEKWS_HIP_EINVAL for: one tap gradient without the other; a workspace that is NULL, not 16-byte aligned or smaller than
+ * wekws_hip_fsmn_memory_workspace_bytes says, when the tap gradients are wanted. */
+int wekws_hip_fsmn_memory_backward(const float* x, const float* grad_y, int B, int T, int D, const float* w_left, int lorder,
+                                   int lstride, const float* w_right, int rorder, int rstride, float* grad_x /* NULL: not wanted */,
+                                   float* grad_w_left, float* grad_w_right, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
