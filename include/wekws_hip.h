@@ -1106,6 +1106,38 @@ int wekws_hip_fsmn_memory_backward(const float* x, const float* grad_y, int B, i
                                    int lstride, const float* w_right, int rorder, int rstride, float* grad_x /* NULL: not wanted */,
                                    float* grad_w_left, float* grad_w_right, void* workspace, size_t workspace_bytes, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The trainable depthwise Conv1d  --  nn.Conv1d(C, C, K, dilation=d, groups=C) behind F.pad(x, (left_pad, 0)): DsCnnBlock.cnn[0]
+ * (wekws/model/tcn.py:102-107) and DSDilatedConv1d.conv (wekws/model/mdtc.py:37-46), and its autograd.  x, grad_x: (B, C, Tin)
+ * float32, contiguous, time innermost;  y, grad_y: (B, C, Tout), Tout = Tin + left_pad - (K-1) d;  w: (C, K), the memory of
+ * conv.weight (C, 1, K);  bias: (C) or NULL.  left_pad = P counts zeros the kernels supply in front of every row in place of
+ * F.pad.  With xp[b, c, n] = 0 for n < 0:
+ *     y[b,c,t]      = bias[c] + sum_k w[c,k] xp[b,c, t + k d - P]
+ *     grad_x[b,c,n] = sum_k w[c,k] grad_y[b,c, n + P - k d]      (terms with an index outside [0, Tout) do not exist)
+ *     grad_w[c,k]   = sum_{b,t} grad_y[b,c,t] xp[b,c, t + k d - P]          grad_bias[c] = sum_{b,t} grad_y[b,c,t]
+ * y starts from the bias (+0 without one) and adds the taps with k ascending by exact float32 fmaf; grad_x adds the same taps,
+ * k ascending.  The padding's zeros are arithmetic zeros in y and grad_w (an Inf or NaN tap makes the first P frames NaN, as the
+ * reference's padding does).  A row's y and grad_x depend on that row alone.  grad_w and grad_bias are summed in double, per
+ * tile of 128 frames of a (b, c) row in a fixed order, then over the tiles in a fixed order, and rounded to float32 once: their
+ * bits are a function of the inputs and the shape.  Stateless calls, device pointers, no floating-point atomics; no call
+ * synchronises, allocates or reads on the host; every element of every output is written.  16-byte accesses where Tin % 4 == 0,
+ * Tout % 4 == 0 and the tensors' bases are 16-byte aligned, scalar accesses with the same bits otherwise.
+ *
+ * Limits (WEKWS_HIP_EINVAL, before any launch): B, C, Tin >= 1;  1 <= K <= 32;  d >= 1;  a window (K-1) d + 1 of at most 256
+ * frames;  0 <= left_pad <= (K-1) d;  Tout >= 1.  forward: one launch;  backward: at most three.
+ * ------------------------------------------------------------------------------------------*/
+/* Without a device: bytes of workspace a backward call that wants grad_w or grad_bias needs: one double per batch row, tile of
+ * 128 output frames, channel and tap (and one for the bias), rounded up to 16.  0 on bad arguments. */
+size_t wekws_hip_depthwise_conv1d_workspace_bytes(int B, int C, int Tin, int K, int dilation, int left_pad);
+int wekws_hip_depthwise_conv1d_forward(const float* x, int B, int C, int Tin, const float* w, const float* bias /* NULL: none */,
+                                       int K, int dilation, int left_pad, float* y, void* stream);
+/* grad_x, grad_w, grad_bias: each NULL when not wanted; its work is dropped.  workspace may be NULL when neither grad_w nor
+ * grad_bias is wanted; otherwise also WEKWS_HIP_EINVAL for a workspace that is NULL, not 16-byte aligned or smaller than
+ * wekws_hip_depthwise_conv1d_workspace_bytes says. */
+int wekws_hip_depthwise_conv1d_backward(const float* x, const float* grad_y, int B, int C, int Tin, const float* w, int K, int dilation,
+                                        int left_pad, float* grad_x, float* grad_w, float* grad_bias, void* workspace,
+                                        size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@
 //     dx[n] = sum_k c_k g[n + d_k]       the same taps with the delays negated (terms with n + d_k >= T do not exist)
 //     dc_k  = sum_{b,t} g[t] x[t - d_k]  for the lorder + rorder taps that have a weight
 // The table says where a tap's coefficient comes from and how many frames it looks back; it says nothing about how the
-// tensor lies in memory, so a (B, C, T) depthwise convolution can be planned by the same table.
+// tensor lies in memory, so a (B, C, T) depthwise convolution is planned by the same table (depthwise_conv_plan.h).
 #pragma once
 #include <stdint.h>
 
