@@ -1138,6 +1138,50 @@ int wekws_hip_depthwise_conv1d_backward(const float* x, const float* grad_y, int
                                         int left_pad, float* grad_x, float* grad_w, float* grad_bias, void* workspace,
                                         size_t workspace_bytes, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The trainable BatchNorm1d with the ReLU and the residual add that follow it  --  DsCnnBlock.cnn[1:3] / [4:6] (wekws/model/tcn.py),
+ * DSDilatedConv1d.bn, TCNBlock.bn1 / relu1 and TCNBlock.bn2 + inputs + relu2 (wekws/model/mdtc.py), and their autograd.  x, y,
+ * residual, grad_*: (B, C, T) float32, contiguous, time innermost (a (B, C) input is T = 1);  weight, bias, running_mean,
+ * running_var, save_mean, save_invstd, grad_weight, grad_bias: (C);  num_batches_tracked: one int64.  N = B T.  Per channel:
+ *     batch_stats != 0:  mean = sum x / N,  var = sum (x - mean)^2 / N (biased),  invstd = 1 / sqrt(var + eps)
+ *     batch_stats == 0:  mean = running_mean,  invstd = 1 / sqrt(running_var + eps)
+ *     z = (x - mean) invstd weight + bias (+ residual)          y = relu ? max(z, 0) : z   (a NaN stays a NaN)
+ *     batch_stats and running buffers:  num_batches_tracked += 1;  f = momentum, or 1 / num_batches_tracked when momentum < 0;
+ *         running_mean <- (1 - f) running_mean + f mean;  running_var <- (1 - f) running_var + f var N / (N - 1)
+ *     backward, g' = grad_y where the ReLU passed (not y <= 0), all of it without ReLU:
+ *         grad_residual = g'      grad_bias = sum g'      grad_weight = invstd sum g' (x - mean)
+ *         grad_x = weight invstd (g' - grad_bias / N - (x - mean) invstd^2 sum g' (x - mean) / N)      (batch_stats)
+ *         grad_x = weight invstd g'                                                                      (otherwise)
+ * The sums are double sums over tiles of 128 frames of a (b, c) row in a fixed order, then over the tiles in a fixed order; the
+ * statistics' sums are taken of x minus the channel's first element.  Every statistic, running value and parameter gradient is
+ * computed in double and rounded to float32 once, so their bits are a function of the inputs and the shape; the float32
+ * operation order of y and grad_x is stated in csrc/batchnorm.hip.h.  save_mean and save_invstd are written in both modes and are
+ * what backward reads.  Stateless calls, device pointers, no floating-point atomics; no call synchronises, allocates or reads on
+ * the host (num_batches_tracked is read and written on the device); every element of every output is written.  16-byte accesses
+ * where T % 4 == 0 and the tensors' bases are 16-byte aligned, scalar accesses with the same bits otherwise.
+ *
+ * Limits (WEKWS_HIP_EINVAL, before any launch): B, C, T >= 1;  batch_stats with B T < 2;  batch_stats == 0 without running
+ * buffers;  one running buffer without the other;  momentum < 0 with running buffers and no num_batches_tracked;  eps <= 0;
+ * momentum > 1;  ceil(B C / 8) ceil(T / 128) workgroups above 2^31 - 1.  forward: three launches with batch statistics, one
+ * without;  backward: at most three.
+ * ------------------------------------------------------------------------------------------*/
+/* Without a device: bytes of workspace a call needs: two doubles per batch row, tile of 128 frames and channel, two floats per
+ * channel and 16 bytes, each part rounded up to 16.  0 on bad arguments. */
+size_t wekws_hip_batchnorm_workspace_bytes(int B, int C, int T);
+/* The workspace may be NULL when batch_stats == 0; otherwise also WEKWS_HIP_EINVAL for a workspace that is NULL, not 16-byte
+ * aligned or smaller than wekws_hip_batchnorm_workspace_bytes says. */
+int wekws_hip_batchnorm_forward(const float* x, const float* residual /* NULL: none */, int B, int C, int T,
+                                const float* weight /* NULL: 1 */, const float* bias /* NULL: 0 */, float* running_mean /* NULL: none */,
+                                float* running_var /* NULL: none */, int64_t* num_batches_tracked /* NULL: none */, int batch_stats,
+                                double momentum /* < 0: cumulative */, double eps, int relu, float* y, float* save_mean,
+                                float* save_invstd, void* workspace, size_t workspace_bytes, void* stream);
+/* y: needed iff relu (WEKWS_HIP_EINVAL without it).  grad_x, grad_residual, grad_weight, grad_bias: each NULL when not wanted;
+ * its work is dropped.  The workspace is needed for grad_weight, grad_bias and for grad_x under batch_stats. */
+int wekws_hip_batchnorm_backward(const float* x, const float* y, const float* grad_y, int B, int C, int T,
+                                 const float* weight /* NULL: 1 */, const float* save_mean, const float* save_invstd, int batch_stats,
+                                 int relu, float* grad_x, float* grad_residual, float* grad_weight, float* grad_bias, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,9 @@ state dicts go both ways (and into the packed inference model, ``wekws_amd.model
 The depthwise convolution of a ``DSDilatedConv1d`` is a ``wekws_amd.model.depthwise.DepthwiseConv1d``: with an empty cache a
 ``TCNBlock`` calls it with ``left_pad = padding``, so the block's ``F.pad`` copy is not made and, for float32 device tensors,
 the HIP kernels run.  With a non-empty cache (streaming) the block does what the reference does:
-``torch.cat``, then the convolution.  BatchNorm, the pointwise convolutions and ReLU stay torch's.
+``torch.cat``, then the convolution.  The pointwise convolutions stay torch's; so do BatchNorm and ReLU unless
+``wekws_amd.model.batchnorm.use_device_batchnorms`` has set a block's ``fused_norm``: then each BatchNorm is a
+``DeviceBatchNorm1d`` and a ``TCNBlock`` hands ``relu1``, the residual add and ``relu2`` to its calls.
 """
 from __future__ import annotations
 
@@ -21,6 +23,8 @@ from wekws_amd.model.tcn import _empty_cache, padded_tail
 class DSDilatedConv1d(nn.Module):
     """Dilated depthwise-separable convolution: depthwise ``conv``, ``bn``, ``pointwise``."""
 
+    fused_norm = False      # set by use_device_batchnorms: bn is a DeviceBatchNorm1d (nothing follows it that could be fused)
+
     def __init__(self, in_channels: int, out_channels: int, kernel_size: int, dilation: int = 1, stride: int = 1, bias: bool = True):
         super().__init__()
         self.padding = dilation * (kernel_size - 1)
@@ -35,6 +39,8 @@ class DSDilatedConv1d(nn.Module):
 
 
 class TCNBlock(nn.Module):
+
+    fused_norm = False      # set by use_device_batchnorms: bn1 and bn2 are DeviceBatchNorm1ds that apply the ReLUs and the residual add
 
     def __init__(self, in_channels: int, res_channels: int, kernel_size: int, dilation: int, causal: bool):
         super().__init__()
@@ -62,6 +68,10 @@ class TCNBlock(nn.Module):
             assert outputs.size(2) > self.padding
             new_cache = outputs[:, :, -self.padding:]
             outputs = self.conv1(outputs, 0)
+        if self.fused_norm:
+            outputs = self.bn1(outputs, relu=True)
+            residual = inputs if self.in_channels == self.res_channels else None
+            return self.bn2(self.conv2(outputs), residual=residual, relu=True), new_cache
         outputs = self.relu1(self.bn1(outputs))
         outputs = self.bn2(self.conv2(outputs))
         if self.in_channels == self.res_channels:

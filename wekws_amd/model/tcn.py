@@ -6,7 +6,9 @@
 The depthwise convolution of a ``DsCnnBlock`` is a ``wekws_amd.model.depthwise.DepthwiseConv1d``: with an empty cache it is
 called with ``left_pad = padding``, so the block's ``F.pad`` copy is not made and, for float32 device tensors, the HIP kernels
 run.  With a non-empty cache (streaming) the block does what the reference does: ``torch.cat``, then the
-convolution.  BatchNorm, the pointwise and the dense convolutions, ReLU and dropout stay torch's.
+convolution.  The pointwise and the dense convolutions and dropout stay torch's; so do BatchNorm and ReLU unless
+``wekws_amd.model.batchnorm.use_device_batchnorms`` has set a ``DsCnnBlock``'s ``fused_norm``: then each BatchNorm is a
+``DeviceBatchNorm1d`` that is called with ``relu=True`` and the ReLU modules are skipped.
 """
 from __future__ import annotations
 
@@ -78,6 +80,8 @@ class CnnBlock(Block):
 class DsCnnBlock(Block):
     """Depthwise separable convolution."""
 
+    fused_norm = False      # set by use_device_batchnorms: cnn[1] and cnn[4] are DeviceBatchNorm1ds that apply the ReLUs behind them
+
     def __init__(self, channel: int, kernel_size: int, dilation: int, dropout: float = 0.1):
         super().__init__(channel, kernel_size, dilation, dropout)
         self.cnn = nn.Sequential(
@@ -92,6 +96,10 @@ class DsCnnBlock(Block):
 
     def _convolve(self, y, left_pad):
         y = self.cnn[0](y, left_pad)
+        if self.fused_norm:
+            y = self.cnn[1](y, relu=True)
+            y = self.cnn[4](self.cnn[3](y), relu=True)
+            return self.cnn[6](y)
         for layer in list(self.cnn)[1:]:
             y = layer(y)
         return y
