@@ -1182,6 +1182,37 @@ int wekws_hip_batchnorm_backward(const float* x, const float* y, const float* gr
                                  int relu, float* grad_x, float* grad_residual, float* grad_weight, float* grad_bias, void* workspace,
                                  size_t workspace_bytes, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The trainable GRU's recurrent scan  --  the time loop of one layer of torch.nn.GRU(batch_first=True), the reference's gru
+ * backbone (wekws/model/kws_model.py:128-133), and its backward through time.  PyTorch's gate order r, z, n; H the hidden size.
+ * gi, grad_gi, grad_gh: (B, T, 3H) float32, contiguous;  y, grad_y: (B, T, H);  h0, hn, grad_hn, grad_h0: (B, H);  w_hh: (3H, H),
+ * the parameter weight_hh_l* as it is;  b_hh: (3H);  reserve: (B, T, 4H), r, z, n and q of every step.  gi = W_ih x + b_ih is the
+ * caller's GEMM.  With s the logistic function:
+ *     gh = W_hh h[t-1] + b_hh      r = s(gi_r + gh_r)   z = s(gi_z + gh_z)   q = gh_n   n = tanh(gi_n + r q)
+ *     y[t] = h[t] = (1 - z) n + z h[t-1]          hn = h[T-1]
+ *     backward, t = T-1 .. 0, dh = grad_y[t] + carry (carry starts at grad_hn):
+ *         dn = dh (1 - z)(1 - n^2)    dz = dh (h[t-1] - n) z (1 - z)    dr = dn q r (1 - r)
+ *         grad_gi[t] = (dr, dz, dn)   grad_gh[t] = (dr, dz, dn r)       carry = dh z + W_hh^T grad_gh[t]
+ *     grad_h0 = the last carry
+ * The weight, bias and input gradients are the caller's GEMMs and column sums: dW_ih = grad_gi^T x, dW_hh = grad_gh^T h_prev,
+ * dx = grad_gi W_ih, db_ih = sum grad_gi, db_hh = sum grad_gh.  Products are exact float32 on the matrix cores, added over
+ * k ascending; the float32 operation order of the cell and of its gradient is stated in csrc/gru_train.hip.h; s and tanh saturate
+ * without a NaN and a NaN goes through.  A row's results depend on that row alone: the same bits in any batch position, alone,
+ * and on any run.  Stateless calls, device pointers, no floating-point atomics; no call synchronises, allocates or reads on the
+ * host; every element of every output is written.  Each call is one launch: a workgroup owns 16 batch rows for all T steps.
+ *
+ * Limits (WEKWS_HIP_EINVAL, before any launch): B, T >= 1;  H % 16 == 0;  16 <= H <= 128;  every tensor 16-byte aligned;  the
+ * pointers a call needs (forward: gi, w_hh, y, hn;  backward: y, reserve, w_hh, grad_gi, grad_gh).
+ * ------------------------------------------------------------------------------------------*/
+/* Without a device: bytes of the reserve a forward call leaves for the backward, B T 4H floats.  0 on bad arguments. */
+size_t wekws_hip_gru_scan_reserve_bytes(int B, int T, int H);
+int wekws_hip_gru_scan_forward(const float* gi, const float* w_hh, const float* b_hh /* NULL: none */, const float* h0 /* NULL: zeros */,
+                               int B, int T, int H, float* y, float* hn, float* reserve /* NULL: not wanted */, void* stream);
+/* y and reserve: what the forward call wrote;  h0: what it was given.  grad_y and grad_hn: each NULL for zeros.  grad_h0 NULL:
+ * not wanted. */
+int wekws_hip_gru_scan_backward(const float* grad_y, const float* grad_hn, const float* y, const float* h0, const float* reserve,
+                                const float* w_hh, int B, int T, int H, float* grad_gi, float* grad_gh, float* grad_h0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
