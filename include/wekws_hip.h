@@ -1213,6 +1213,35 @@ int wekws_hip_gru_scan_forward(const float* gi, const float* w_hh, const float* 
 int wekws_hip_gru_scan_backward(const float* grad_y, const float* grad_hn, const float* y, const float* h0, const float* reserve,
                                 const float* w_hh, int B, int T, int H, float* grad_gi, float* grad_gh, float* grad_h0, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The Linear layers' weight and bias gradients  --  for y = x W^T + b with x (R, I) and the upstream gradient g (R, O), float32,
+ * row-major and contiguous (R = B T rows, tens of thousands; O and I a few hundred):
+ *     grad_w (O, I) = g^T x          grad_bias (O) = the column sums of g
+ * as a split-K product whose arithmetic is stated, so the bits are a function of the inputs and the shape:
+ *     chains   the R axis is cut into chains of 512 rows counted from row 0; per chain the float32 fmaf chain over its rows
+ *              ascending from +0, on the matrix cores (exact float32 products); the boundaries depend on R alone
+ *     slices   a slice is a run of consecutive chains, one workgroup's work for one 64 x 64 tile of grad_w: its chains are added
+ *              in double, ascending, and the double partial goes to the workspace
+ *     fold     the slices' doubles are added in ascending order and rounded to float32 once
+ *     bias     the same on a column of ones: per chain a float32 ascending sum, then the same doubles
+ * The number of slices depends on (R, O, I) alone, never on the device.  The forward product and the input gradient g W are
+ * regular GEMMs and stay the caller's.  Stateless calls, device pointers, no floating-point atomics, no waits between
+ * workgroups; no call synchronises, allocates or reads on the host; every element of every requested output is written.  Two
+ * launches.  x and g may have any 4-byte alignment: 16-byte loads are taken where O % 4 == 0, I % 4 == 0 and both bases are
+ * 16-byte aligned, scalar loads with the same bits otherwise.
+ *
+ * Limits (WEKWS_HIP_EINVAL, before any launch, outputs untouched): R >= 1;  1 <= O, I <= 65535;  a grid within 2^31 - 1;  at least
+ * one of grad_w and grad_bias;  x and g;  a workspace that is not NULL, 16-byte aligned and at least
+ * wekws_hip_linear_wgrad_workspace_bytes(R, O, I) large.
+ * ------------------------------------------------------------------------------------------*/
+/* Without a device: out = {rows a chain, chains, slices, workgroups of the partial launch, workspace bytes}. */
+int wekws_hip_linear_wgrad_plan(int64_t R, int O, int I, int64_t out[5]);
+/* Without a device: slices x padded O x padded I doubles and slices x padded O for the bias, rounded up to 16 bytes (padded: to a
+ * multiple of 64).  0 on bad arguments. */
+size_t wekws_hip_linear_wgrad_workspace_bytes(int64_t R, int O, int I);
+int wekws_hip_linear_wgrad(const float* x, const float* g, int64_t R, int O, int I, float* grad_w /* NULL: not wanted */,
+                           float* grad_bias /* NULL: not wanted */, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

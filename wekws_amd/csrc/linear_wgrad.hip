@@ -1,0 +1,67 @@
+// The Linear layers' weight and bias gradients: launches and C entry points (kernels: linear_wgrad.hip.h; the plan:
+// linear_wgrad_plan.h).
+#include "linear_wgrad.hip.h"
+
+#include "host_util.h"
+
+namespace {
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+template <bool VEC>
+bool launch_partial(const float* x, const float* g, int64_t R, int O, int I, bool want_w, double* ws_w, double* ws_b, hipStream_t s) {
+  const int64_t grid = want_w ? wekws::linear_wgrad_grid(R, O, I) : wekws::linear_wgrad_bias_grid(R, O, I);
+  const int tiles_i = want_w ? int(wekws::wgrad_ceil_div(I, wekws::kWgradTile)) : 1;
+  hipLaunchKernelGGL(wekws::linear_wgrad_partial<VEC>, dim3(unsigned(grid)), dim3(wekws::kWgradThreads), 0, s, x, g, R, O, I, tiles_i,
+                     wekws::linear_wgrad_chains_per_slice(R, O, I), wekws::linear_wgrad_padded(O), wekws::linear_wgrad_padded(I),
+                     want_w ? ws_w : nullptr, ws_b);
+  return hipGetLastError() == hipSuccess;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wekws_hip_linear_wgrad_plan(int64_t R, int O, int I, int64_t out[5]) {
+  if (!out) return fail(WEKWS_HIP_EINVAL, "linear_wgrad_plan: out is NULL");
+  if (const char* why = wekws::linear_wgrad_shape_check(R, O, I))
+    return fail(WEKWS_HIP_EINVAL, "linear_wgrad_plan: %s (R=%lld O=%d I=%d)", why, static_cast<long long>(R), O, I);
+  if (wekws::linear_wgrad_grid(R, O, I) > INT32_MAX) return fail(WEKWS_HIP_EINVAL, "linear_wgrad_plan: grid too large for one launch");
+  out[0] = wekws::kWgradChain;
+  out[1] = wekws::linear_wgrad_chains(R);
+  out[2] = wekws::linear_wgrad_slices(R, O, I);
+  out[3] = wekws::linear_wgrad_grid(R, O, I);
+  out[4] = wekws::linear_wgrad_workspace_bytes(R, O, I);
+  return WEKWS_HIP_OK;
+}
+
+size_t wekws_hip_linear_wgrad_workspace_bytes(int64_t R, int O, int I) {
+  if (const char* why = wekws::linear_wgrad_shape_check(R, O, I)) {
+    fail(WEKWS_HIP_EINVAL, "linear_wgrad_workspace_bytes: %s (R=%lld O=%d I=%d)", why, static_cast<long long>(R), O, I);
+    return 0;
+  }
+  return size_t(wekws::linear_wgrad_workspace_bytes(R, O, I));
+}
+
+int wekws_hip_linear_wgrad(const float* x, const float* g, int64_t R, int O, int I, float* grad_w, float* grad_bias, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  if (const char* why = wekws::linear_wgrad_check(x, g, R, O, I, grad_w, grad_bias, workspace, workspace_bytes))
+    return fail(WEKWS_HIP_EINVAL, "linear_wgrad: %s (R=%lld O=%d I=%d)", why, static_cast<long long>(R), O, I);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  double* const ws = static_cast<double*>(workspace);
+  const int64_t bias_offset = wekws::linear_wgrad_bias_offset(R, O, I);
+  double* const ws_b = grad_bias ? ws + bias_offset : nullptr;
+  const bool vec = O % 4 == 0 && I % 4 == 0 && aligned16(x) && aligned16(g);
+  const bool ok = vec ? launch_partial<true>(x, g, R, O, I, grad_w != nullptr, ws, ws_b, s)
+                      : launch_partial<false>(x, g, R, O, I, grad_w != nullptr, ws, ws_b, s);
+  if (!ok) return fail(WEKWS_HIP_EDEVICE, "linear_wgrad: the partial launch failed");
+  const int64_t n_w = int64_t(O) * I;
+  const int64_t first = grad_w ? 0 : n_w, last = grad_bias ? n_w + O : n_w;
+  hipLaunchKernelGGL(wekws::linear_wgrad_fold, dim3(unsigned(wekws::wgrad_ceil_div(last - first, wekws::kWgradFoldThreads))),
+                     dim3(wekws::kWgradFoldThreads), 0, s, ws, O, I, wekws::linear_wgrad_slices(R, O, I), wekws::linear_wgrad_padded(O),
+                     wekws::linear_wgrad_padded(I), bias_offset, first, last, grad_w, grad_bias);
+  if (hipGetLastError() != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "linear_wgrad: the fold launch failed");
+  return WEKWS_HIP_OK;
+}
+
+}  // extern "C"

@@ -1,7 +1,8 @@
 """A trainable GRU whose recurrence runs on the device: ``gru_scan`` is the time loop of one layer of ``torch.nn.GRU`` and its
 backward through time as two persistent HIP kernels (csrc/gru_train.hip.h) -- one launch each where torch makes
 several per step.  The input product ``gi = W_ih x + b_ih`` and the weight, bias and input gradients are large GEMMs and column
-sums; they stay torch's (rocBLAS).
+sums; they stay torch's (rocBLAS) unless ``device_weight_grads`` is on, which hands the weight and bias gradients -- products
+over all ``B T`` rows -- to the split-K kernels of ``wekws_amd.model.linear``.
 
 ``DeviceGRU`` is an ``nn.GRU``: the same constructor, parameter names and state-dict keys, so state dicts go both ways (and into
 the packed inference model, ``wekws_amd.model.kws_model``).  ``use_device_grus(module)`` swaps the eligible ``nn.GRU`` children of
@@ -45,7 +46,8 @@ def _ptr(t: Optional[torch.Tensor]):
 class _GruScan(torch.autograd.Function):
 
     @staticmethod
-    def forward(ctx, gi, w_hh, b_hh, h0):
+    def forward(ctx, gi, w_hh, b_hh, h0, device_weight_grads=False):
+        ctx.device_weight_grads = bool(device_weight_grads)
         B, T, H3 = gi.shape
         H = H3 // 3
         gi, w = gi.contiguous(), w_hh.contiguous()
@@ -67,9 +69,9 @@ class _GruScan(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_y, grad_hn):
-        want_gi, want_w, want_b, want_h0 = ctx.needs_input_grad
+        want_gi, want_w, want_b, want_h0 = ctx.needs_input_grad[:4]
         if grad_y is None and grad_hn is None:
-            return None, None, None, None
+            return None, None, None, None, None
         y, reserve, w, h0 = ctx.saved_tensors
         B, T, H = y.shape
         gy = None if grad_y is None else grad_y.contiguous()
@@ -82,6 +84,20 @@ class _GruScan(torch.autograd.Function):
                                                                  w.data_ptr(), B, T, H, dgi.data_ptr(), dgh.data_ptr(), _ptr(dh0),
                                                                  _stream(y.device)), "wekws_hip_gru_scan_backward")
         dw = db = None
+        if ctx.device_weight_grads and (want_w or want_b):
+            from wekws_amd.model.linear import _weight_grad
+            g2 = dgh.view(B * T, 3 * H)
+            if want_w:
+                h_prev = torch.empty_like(y)
+                h_prev[:, 1:] = y[:, :-1]
+                if h0 is None:
+                    h_prev[:, 0].zero_()
+                else:
+                    h_prev[:, 0] = h0
+                dw, db = _weight_grad(h_prev.view(B * T, H), g2, True, want_b)
+            else:
+                _, db = _weight_grad(g2, g2, False, True)          # x is not read without grad_w
+            return dgi if want_gi else None, dw, db, dh0, None
         if want_w:
             # dW_hh = dgh^T h_prev over all (b, t): h_prev[t] = y[t-1], h_prev[0] = h0
             h_prev = torch.empty_like(y)
@@ -93,16 +109,17 @@ class _GruScan(torch.autograd.Function):
             dw = dgh.view(B * T, 3 * H).t().mm(h_prev.view(B * T, H))
         if want_b:
             db = dgh.view(B * T, 3 * H).sum(0)
-        return dgi if want_gi else None, dw, db, dh0
+        return dgi if want_gi else None, dw, db, dh0, None
 
 
-def gru_scan(gi: torch.Tensor, w_hh: torch.Tensor, b_hh: Optional[torch.Tensor], h0: Optional[torch.Tensor] = None
-             ) -> Tuple[torch.Tensor, torch.Tensor]:
+def gru_scan(gi: torch.Tensor, w_hh: torch.Tensor, b_hh: Optional[torch.Tensor], h0: Optional[torch.Tensor] = None,
+             device_weight_grads: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """The recurrence of one GRU layer on the device, differentiable once: ``gi`` (B, T, 3H) float32 on a ROCm device, the input
     product ``W_ih x + b_ih`` in PyTorch's gate order r, z, n; ``w_hh`` (3H, H); ``b_hh`` (3H) or None; ``h0`` (B, H) or None for
     zeros.  Returns ``(y, hn)``: every step's hidden state (B, T, H) and the last one (B, H).  One launch forward and one backward,
-    on the current stream; nothing is read on the host, and only the gradients autograd asks for are computed.  No CPU
-    fallback: anything else raises."""
+    on the current stream; nothing is read on the host, and only the gradients autograd asks for are computed.  The gradients of
+    ``w_hh`` and ``b_hh`` are torch's ``mm`` and ``sum`` over the scan's ``dgh``; with ``device_weight_grads`` they are
+    ``wekws_amd.model.linear``'s split-K kernels.  No CPU fallback: anything else raises."""
     tensors = [("gi", gi), ("w_hh", w_hh)] + ([("b_hh", b_hh)] if b_hh is not None else []) + ([("h0", h0)] if h0 is not None else [])
     for name, t in tensors:
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
@@ -121,14 +138,22 @@ def gru_scan(gi: torch.Tensor, w_hh: torch.Tensor, b_hh: Optional[torch.Tensor],
         raise ValueError(f"gru_scan: b_hh must be ({H3},), got {tuple(b_hh.shape)}")
     if h0 is not None and tuple(h0.shape) != (B, H):
         raise ValueError(f"gru_scan: h0 must be ({B}, {H}), got {tuple(h0.shape)}")
-    return _GruScan.apply(gi, w_hh, b_hh, h0)
+    return _GruScan.apply(gi, w_hh, b_hh, h0, bool(device_weight_grads))
 
 
 class DeviceGRU(nn.GRU):
     """``torch.nn.GRU`` whose recurrence runs in ``gru_scan``: per layer one ``torch.addmm`` for ``gi``, then the scan.
     ``forward(x, hx=None) -> (output, h_n)`` with nn.GRU's shapes; an ``hx`` with zero elements means zeros, as the packed model
     treats the reference's empty ``in_cache``.  The device path never calls ``flatten_parameters``, so the parameters may be views
-    of an optimiser's flat buffers (``wekws_amd.optim.ClipAdam``)."""
+    of an optimiser's flat buffers (``wekws_amd.optim.ClipAdam``).  ``device_weight_grads`` (off by default; turned on by
+    ``wekws_amd.model.linear.use_device_weight_grads``) takes all four parameter gradients of a layer from the split-K kernels of
+    ``wekws_amd.model.linear`` instead of rocBLAS."""
+
+    device_weight_grads = False            # (the class's default: a module unpickled from before the switch has it off)
+
+    def __init__(self, *args, device_weight_grads: bool = False, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.device_weight_grads = bool(device_weight_grads)
 
     @classmethod
     def sharing(cls, gru: nn.GRU) -> "DeviceGRU":
@@ -138,6 +163,7 @@ class DeviceGRU(nn.GRU):
                   dropout=gru.dropout, bidirectional=gru.bidirectional, device=p.device, dtype=p.dtype)
         for name, param in gru.named_parameters(recurse=False):
             setattr(new, name, param)
+        new.device_weight_grads = bool(getattr(gru, "device_weight_grads", False))
         new.train(gru.training)
         return new
 
@@ -164,8 +190,12 @@ class DeviceGRU(nn.GRU):
             b_ih = getattr(self, f"bias_ih_l{layer}") if self.bias else None
             b_hh = getattr(self, f"bias_hh_l{layer}") if self.bias else None
             flat = x.reshape(B * T, x.shape[2])
-            gi = torch.addmm(b_ih, flat, w_ih.t()) if b_ih is not None else flat.mm(w_ih.t())
-            x, hn = gru_scan(gi.view(B, T, 3 * H), w_hh, b_hh, None if hx is None else hx[layer])
+            if self.device_weight_grads:
+                from wekws_amd.model.linear import linear
+                gi = linear(flat, w_ih, b_ih)
+            else:
+                gi = torch.addmm(b_ih, flat, w_ih.t()) if b_ih is not None else flat.mm(w_ih.t())
+            x, hn = gru_scan(gi.view(B, T, 3 * H), w_hh, b_hh, None if hx is None else hx[layer], self.device_weight_grads)
             last.append(hn)
         return x, torch.stack(last, 0)
 
