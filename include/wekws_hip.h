@@ -1242,6 +1242,35 @@ size_t wekws_hip_linear_wgrad_workspace_bytes(int64_t R, int O, int I);
 int wekws_hip_linear_wgrad(const float* x, const float* g, int64_t R, int O, int I, float* grad_w /* NULL: not wanted */,
                            float* grad_bias /* NULL: not wanted */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The pointwise (kernel_size 1) Conv1d of the TCN and MDTC blocks, forward and backward: x (B, Ci, T), y and grad_y (B, Co, T),
+ * float32, contiguous; w (Co, Ci), the (Co, Ci, 1) weight of nn.Conv1d; bias (Co) or none.  The arithmetic:
+ *     forward   y[b][o][t]: acc = +0; i ascending, acc = fmaf(w[o][i], x[b][i][t], acc); then one float32 addition of bias[o]
+ *               (none without a bias) -- the exact-float32 matrix instruction from a zeroed accumulator
+ *     grad_x    grad_x[b][i][t]: the same chain over o ascending, fmaf(w[o][i], grad_y[b][o][t], acc)
+ *     grad_w, grad_bias   wekws_hip_linear_wgrad's contract, unchanged, with rows r = b T + t, R = B T, O = Co, I = Ci: the bits
+ *               are those of wekws_hip_linear_wgrad on the (R, Ci) and (R, Co) transposes of x and grad_y, which are not made
+ * A (b, t) column's y and grad_x depend on that column alone.  Stateless calls, device pointers, no floating-point atomics, no
+ * waits between workgroups; no call synchronises, allocates or reads on the host; every element of every requested output is
+ * written.  One launch for the forward; one for grad_x and two for grad_w / grad_bias.  Operands may have any 4-byte alignment:
+ * 16-byte loads are taken where T % 4 == 0 (Ci % 4 == 0 for w) and the base is 16-byte aligned, scalar loads with the same bits
+ * otherwise.
+ *
+ * Limits (WEKWS_HIP_EINVAL, before any launch, outputs untouched): B, T >= 1;  1 <= Ci, Co <= 65535;  every grid within 2^31 - 1;
+ * no NULL operand;  at least one of the three gradients;  where grad_w or grad_bias is wanted, a workspace that is not NULL,
+ * 16-byte aligned and at least wekws_hip_pointwise_conv1d_workspace_bytes(B, Ci, T, Co) large (grad_x alone needs none).
+ * ------------------------------------------------------------------------------------------*/
+/* Without a device: out = {rows a chain, chains, slices, workgroups of the weight gradient's partial launch, workspace bytes,
+ * workgroups of the forward, workgroups of grad_x}; the first five are wekws_hip_linear_wgrad_plan(B T, Co, Ci)'s. */
+int wekws_hip_pointwise_conv1d_plan(int B, int Ci, int T, int Co, int64_t out[7]);
+/* Without a device: wekws_hip_linear_wgrad_workspace_bytes(B T, Co, Ci).  0 on bad arguments. */
+size_t wekws_hip_pointwise_conv1d_workspace_bytes(int B, int Ci, int T, int Co);
+int wekws_hip_pointwise_conv1d_forward(const float* x, int B, int Ci, int T, const float* w, const float* bias /* NULL: none */, int Co,
+                                       float* y, void* stream);
+int wekws_hip_pointwise_conv1d_backward(const float* x, const float* grad_y, int B, int Ci, int T, const float* w, int Co,
+                                        float* grad_x /* NULL: not wanted */, float* grad_w /* NULL: not wanted */,
+                                        float* grad_bias /* NULL: not wanted */, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

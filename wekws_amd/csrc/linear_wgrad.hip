@@ -8,17 +8,49 @@ namespace {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-template <bool VEC>
-bool launch_partial(const float* x, const float* g, int64_t R, int O, int I, bool want_w, double* ws_w, double* ws_b, hipStream_t s) {
+template <bool VEC, bool BCT>
+bool launch_partial(const float* x, const float* g, int64_t R, int O, int I, int64_t T, bool want_w, double* ws_w, double* ws_b,
+                    hipStream_t s) {
   const int64_t grid = want_w ? wekws::linear_wgrad_grid(R, O, I) : wekws::linear_wgrad_bias_grid(R, O, I);
   const int tiles_i = want_w ? int(wekws::wgrad_ceil_div(I, wekws::kWgradTile)) : 1;
-  hipLaunchKernelGGL(wekws::linear_wgrad_partial<VEC>, dim3(unsigned(grid)), dim3(wekws::kWgradThreads), 0, s, x, g, R, O, I, tiles_i,
+  hipLaunchKernelGGL((wekws::linear_wgrad_partial<VEC, BCT>), dim3(unsigned(grid)), dim3(wekws::kWgradThreads), 0, s, x, g, R, O, I, tiles_i,
                      wekws::linear_wgrad_chains_per_slice(R, O, I), wekws::linear_wgrad_padded(O), wekws::linear_wgrad_padded(I),
-                     want_w ? ws_w : nullptr, ws_b);
+                     want_w ? ws_w : nullptr, ws_b, T);
   return hipGetLastError() == hipSuccess;
 }
 
 }  // namespace
+
+namespace wekws {
+
+const char* linear_wgrad_launch(const float* x, const float* g, int64_t R, int O, int I, int64_t frames, float* grad_w, float* grad_bias,
+                                void* workspace, void* stream) {
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  double* const ws = static_cast<double*>(workspace);
+  const int64_t bias_offset = linear_wgrad_bias_offset(R, O, I);
+  double* const ws_b = grad_bias ? ws + bias_offset : nullptr;
+  const bool want_w = grad_w != nullptr;
+  bool ok;
+  if (frames > 0) {
+    const bool vec = frames % 4 == 0 && aligned16(x) && aligned16(g);
+    ok = vec ? launch_partial<true, true>(x, g, R, O, I, frames, want_w, ws, ws_b, s)
+             : launch_partial<false, true>(x, g, R, O, I, frames, want_w, ws, ws_b, s);
+  } else {
+    const bool vec = O % 4 == 0 && I % 4 == 0 && aligned16(x) && aligned16(g);
+    ok = vec ? launch_partial<true, false>(x, g, R, O, I, 0, want_w, ws, ws_b, s)
+             : launch_partial<false, false>(x, g, R, O, I, 0, want_w, ws, ws_b, s);
+  }
+  if (!ok) return "the partial launch failed";
+  const int64_t n_w = int64_t(O) * I;
+  const int64_t first = grad_w ? 0 : n_w, last = grad_bias ? n_w + O : n_w;
+  hipLaunchKernelGGL(linear_wgrad_fold, dim3(unsigned(wgrad_ceil_div(last - first, kWgradFoldThreads))), dim3(kWgradFoldThreads), 0, s, ws,
+                     O, I, linear_wgrad_slices(R, O, I), linear_wgrad_padded(O), linear_wgrad_padded(I), bias_offset, first, last, grad_w,
+                     grad_bias);
+  if (hipGetLastError() != hipSuccess) return "the fold launch failed";
+  return nullptr;
+}
+
+}  // namespace wekws
 
 extern "C" {
 
@@ -47,20 +79,8 @@ int wekws_hip_linear_wgrad(const float* x, const float* g, int64_t R, int O, int
                            size_t workspace_bytes, void* stream) {
   if (const char* why = wekws::linear_wgrad_check(x, g, R, O, I, grad_w, grad_bias, workspace, workspace_bytes))
     return fail(WEKWS_HIP_EINVAL, "linear_wgrad: %s (R=%lld O=%d I=%d)", why, static_cast<long long>(R), O, I);
-  const hipStream_t s = static_cast<hipStream_t>(stream);
-  double* const ws = static_cast<double*>(workspace);
-  const int64_t bias_offset = wekws::linear_wgrad_bias_offset(R, O, I);
-  double* const ws_b = grad_bias ? ws + bias_offset : nullptr;
-  const bool vec = O % 4 == 0 && I % 4 == 0 && aligned16(x) && aligned16(g);
-  const bool ok = vec ? launch_partial<true>(x, g, R, O, I, grad_w != nullptr, ws, ws_b, s)
-                      : launch_partial<false>(x, g, R, O, I, grad_w != nullptr, ws, ws_b, s);
-  if (!ok) return fail(WEKWS_HIP_EDEVICE, "linear_wgrad: the partial launch failed");
-  const int64_t n_w = int64_t(O) * I;
-  const int64_t first = grad_w ? 0 : n_w, last = grad_bias ? n_w + O : n_w;
-  hipLaunchKernelGGL(wekws::linear_wgrad_fold, dim3(unsigned(wekws::wgrad_ceil_div(last - first, wekws::kWgradFoldThreads))),
-                     dim3(wekws::kWgradFoldThreads), 0, s, ws, O, I, wekws::linear_wgrad_slices(R, O, I), wekws::linear_wgrad_padded(O),
-                     wekws::linear_wgrad_padded(I), bias_offset, first, last, grad_w, grad_bias);
-  if (hipGetLastError() != hipSuccess) return fail(WEKWS_HIP_EDEVICE, "linear_wgrad: the fold launch failed");
+  if (const char* why = wekws::linear_wgrad_launch(x, g, R, O, I, 0, grad_w, grad_bias, workspace, stream))
+    return fail(WEKWS_HIP_EDEVICE, "linear_wgrad: %s", why);
   return WEKWS_HIP_OK;
 }
 

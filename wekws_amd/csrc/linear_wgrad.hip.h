@@ -15,6 +15,13 @@
 //                               are added into 16 doubles and zeroed.  Rows past the slice's end and columns past O / I are
 //                               zeros in LDS; padded results are never stored.  The workgroups of I-tile 0 also sum the columns
 //                               of the g stage they hold (wave 0, one column a lane).  Without grad_w only those run, and no MFMA.
+//                               BCT: the operands are laid out (B, C, T) -- the activations of a pointwise Conv1d
+//                               (pointwise_conv_plan.h) -- so row r = b T + t of column c is at base + ((r / T) C + c) T + r % T
+//                               and the contiguous axis is k.  A thread then fetches rows 4 (tid >> 6) + 16 j + 0 .. 3 of column
+//                               tid & 63 -- one 16-byte load where T % 4 == 0 and the bases are 16-byte aligned, four scalar loads
+//                               that step over the batch-row boundary otherwise -- and stores them to the same LDS layout by four
+//                               4-byte stores, a wave's 64 lanes on 64 consecutive banks: no conflict.  A stage may straddle
+//                               batch rows.  Everything after the fetch is the row-major kernel's, so are the bits.
 //   linear_wgrad_fold           one lane per element of grad_w and of grad_bias: the slices' doubles added in ascending order,
 //                               eight loads in flight, rounded once.
 #pragma once
@@ -43,11 +50,36 @@ __device__ inline float4 wgrad_fetch(const float* __restrict__ base, int64_t row
   return v;
 }
 
+// (B, C, T) operands: rows row .. row + 3 of column col, row = b T + t.  VEC: T % 4 == 0 and row % 4 == 0, so the four rows lie
+// in one batch row, 16-byte aligned, and are inside row_end together (R % 4 == 0 and the chains' ends are multiples of 4).
 template <bool VEC>
+__device__ inline float4 wgrad_fetch_bct(const float* __restrict__ base, int64_t row, int64_t row_end, int64_t b, int64_t t, int64_t T,
+                                         int col, int cols) {
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (col >= cols || row >= row_end) return v;
+  if (VEC) {
+    v = *reinterpret_cast<const float4*>(base + (b * cols + col) * T + t);
+  } else {
+    float e[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (row + u < row_end) e[u] = base[(b * cols + col) * T + t];
+      if (++t == T) {
+        t = 0;
+        ++b;
+      }
+    }
+    v = make_float4(e[0], e[1], e[2], e[3]);
+  }
+  return v;
+}
+
+// T: frames of a batch row of the (B, C, T) operands (BCT); unused otherwise
+template <bool VEC, bool BCT = false>
 __global__ __launch_bounds__(kWgradThreads) void linear_wgrad_partial(const float* __restrict__ x, const float* __restrict__ g,
                                                                       int64_t R, int O, int I, int tiles_i, int64_t chains_per_slice,
                                                                       int64_t o_pad, int64_t i_pad, double* __restrict__ ws_w,
-                                                                      double* __restrict__ ws_b) {
+                                                                      double* __restrict__ ws_b, int64_t T) {
   constexpr int S = kWgradStride, ST = kWgradStage, BUF = kWgradStage * kWgradStride;
   constexpr int kStagesPerChain = kWgradChain / kWgradStage;
   __shared__ __attribute__((aligned(16))) float lds[2 * 2 * BUF];      // [buffer][g, x][row][S]
@@ -67,23 +99,50 @@ __global__ __launch_bounds__(kWgradThreads) void linear_wgrad_partial(const floa
   const int64_t r_end = r_stop < R ? r_stop : R;
   const int stages = int((r_end - r_begin + ST - 1) / ST);
 
-  // what this thread fetches of a stage: rows frow and frow + 16, columns fcol .. fcol + 3 of the tile
-  const int frow = tid >> 4, fcol = (tid & 15) * 4;
+  // what this thread fetches of a stage: rows frow and frow + 16, columns fcol .. fcol + 3 of the tile; BCT: rows
+  // frow + 16 j + 0 .. 3 of column fcol, with (fb[j], ft[j]) the batch row and frame of the first of them
+  const int frow = BCT ? (tid >> 6) * 4 : tid >> 4, fcol = BCT ? (tid & 63) : (tid & 15) * 4;
   float4 gq[2], xq[2];
-  auto fetch = [&](int s) {
+  int64_t fb[2] = {0, 0}, ft[2] = {0, 0};
+  if (BCT) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int64_t r0 = r_begin + frow + 16 * j;
+      fb[j] = r0 / T;
+      ft[j] = r0 - fb[j] * T;
+    }
+  }
+  auto fetch = [&](int s) {                                  // BCT: called for s = 0, 1, 2, ... in order
     const int64_t r0 = r_begin + int64_t(s) * ST + frow;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      gq[j] = wgrad_fetch<VEC>(g, r0 + 16 * j, r_end, O, o_base + fcol, O);
-      xq[j] = want_w ? wgrad_fetch<VEC>(x, r0 + 16 * j, r_end, I, i_base + fcol, I) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (BCT) {
+        gq[j] = wgrad_fetch_bct<VEC>(g, r0 + 16 * j, r_end, fb[j], ft[j], T, o_base + fcol, O);
+        xq[j] = want_w ? wgrad_fetch_bct<VEC>(x, r0 + 16 * j, r_end, fb[j], ft[j], T, i_base + fcol, I)
+                       : make_float4(0.f, 0.f, 0.f, 0.f);
+        ft[j] += ST;                                         // the same rows of the next stage
+        while (ft[j] >= T) {
+          ft[j] -= T;
+          ++fb[j];
+        }
+      } else {
+        gq[j] = wgrad_fetch<VEC>(g, r0 + 16 * j, r_end, O, o_base + fcol, O);
+        xq[j] = want_w ? wgrad_fetch<VEC>(x, r0 + 16 * j, r_end, I, i_base + fcol, I) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
     }
   };
   auto stash = [&](int s) {
     float* const bg = lds + (s & 1) * 2 * BUF;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      *reinterpret_cast<float4*>(bg + (frow + 16 * j) * S + fcol) = gq[j];
-      if (want_w) *reinterpret_cast<float4*>(bg + BUF + (frow + 16 * j) * S + fcol) = xq[j];
+      if (BCT) {                                             // the transposing store: a wave's lanes on 64 consecutive banks
+        float* const pg = bg + (frow + 16 * j) * S + fcol;
+        pg[0] = gq[j].x, pg[S] = gq[j].y, pg[2 * S] = gq[j].z, pg[3 * S] = gq[j].w;
+        if (want_w) pg[BUF] = xq[j].x, pg[BUF + S] = xq[j].y, pg[BUF + 2 * S] = xq[j].z, pg[BUF + 3 * S] = xq[j].w;
+      } else {
+        *reinterpret_cast<float4*>(bg + (frow + 16 * j) * S + fcol) = gq[j];
+        if (want_w) *reinterpret_cast<float4*>(bg + BUF + (frow + 16 * j) * S + fcol) = xq[j];
+      }
     }
   };
 

@@ -92,4 +92,9 @@ inline const char* linear_wgrad_check(const void* x, const void* g, int64_t R, i
   return nullptr;
 }
 
+// linear_wgrad.hip: the partial and the fold launch for arguments already checked.  frames == 0: x (R, I) and g (R, O) row-major;
+// frames > 0: x (B, I, frames) and g (B, O, frames) with R = B frames (pointwise_conv_plan.h).  0, or which launch failed.
+const char* linear_wgrad_launch(const float* x, const float* g, int64_t R, int O, int I, int64_t frames, float* grad_w, float* grad_bias,
+                                void* workspace, void* stream);
+
 }  // namespace wekws

@@ -5,7 +5,9 @@ state dicts go both ways (and into the packed inference model, ``wekws_amd.model
 The depthwise convolution of a ``DSDilatedConv1d`` is a ``wekws_amd.model.depthwise.DepthwiseConv1d``: with an empty cache a
 ``TCNBlock`` calls it with ``left_pad = padding``, so the block's ``F.pad`` copy is not made and, for float32 device tensors,
 the HIP kernels run.  With a non-empty cache (streaming) the block does what the reference does:
-``torch.cat``, then the convolution.  The pointwise convolutions stay torch's; so do BatchNorm and ReLU unless
+``torch.cat``, then the convolution.  The pointwise convolutions (``conv1.pointwise`` and ``conv2`` of a ``TCNBlock``) are
+constructed as ``nn.Conv1d`` and stay torch's unless ``wekws_amd.model.pointwise.use_device_pointwise_convs`` has swapped them
+for ``PointwiseConv1d``s; BatchNorm and ReLU stay torch's unless
 ``wekws_amd.model.batchnorm.use_device_batchnorms`` has set a block's ``fused_norm``: then each BatchNorm is a
 ``DeviceBatchNorm1d`` and a ``TCNBlock`` hands ``relu1``, the residual add and ``relu2`` to its calls.
 """

@@ -6,7 +6,9 @@
 The depthwise convolution of a ``DsCnnBlock`` is a ``wekws_amd.model.depthwise.DepthwiseConv1d``: with an empty cache it is
 called with ``left_pad = padding``, so the block's ``F.pad`` copy is not made and, for float32 device tensors, the HIP kernels
 run.  With a non-empty cache (streaming) the block does what the reference does: ``torch.cat``, then the
-convolution.  The pointwise and the dense convolutions and dropout stay torch's; so do BatchNorm and ReLU unless
+convolution.  The pointwise convolution of a ``DsCnnBlock`` is constructed as an ``nn.Conv1d`` and stays torch's unless
+``wekws_amd.model.pointwise.use_device_pointwise_convs`` has swapped it for a ``PointwiseConv1d``.  The dense
+convolution of a ``CnnBlock`` and dropout stay torch's; so do BatchNorm and ReLU unless
 ``wekws_amd.model.batchnorm.use_device_batchnorms`` has set a ``DsCnnBlock``'s ``fused_norm``: then each BatchNorm is a
 ``DeviceBatchNorm1d`` that is called with ``relu=True`` and the ReLU modules are skipped.
 """
