@@ -389,3 +389,10 @@ K_SOFTMAX = 32.0
 
 def pow2_at_or_above(v):
     return 2.0 ** int(np.ceil(np.log2(v)))
+
+
+POSTERIOR_TOL = 1e-4
+
+
+def tol_for(ref):
+    return POSTERIOR_TOL * max(1.0, float(np.abs(ref).max()))

@@ -3,23 +3,18 @@ three ``TrainExecutor`` steps (max_pooling, ClipAdam) of a tiny DS-TCN and a tin
 (float32 and float64), no host read in the step, and the trained state dict served by the packed inference model."""
 import copy
 
-import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from tests import batchnorm_matrix as bm
-from tests.helpers import pow2_at_or_above
-from tests.test_hip_conv_train import ARGS, BACKBONES, HDIM, IDIM, ODIM, Kws, _distances, _Float64, _loader
-from tests.test_hip_optim import HYPER, _Counter
-from tests.test_hip_parity import tol_for
+from tests.helpers import pow2_at_or_above, tol_for
+from tests.train_step import (ARGS, BACKBONES, HDIM, HYPER, IDIM, ODIM, SWAPPED, Kws, _bound, _Counter, _distances, _Float64, _grad_errors,
+                              _loader)
 from wekws_amd.model import batchnorm
 
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -24
-SWAPPED = {"ds_tcn": 4, "mdtc": 15}                # BatchNorms of the tiny backbones: 2 a DsCnnBlock, 3 a TCNBlock
 
 
 def _module(c, cls):
@@ -114,25 +109,6 @@ def test_only_the_gradients_asked_for_and_what_raises():
         batchnorm.batch_norm_act(x, None, None, None, None, None, False, 0.1, bm.EPS)          # eval without buffers
     with pytest.raises(ValueError):
         batchnorm.batch_norm_act(x.cpu(), None, None, None, None, None, True, 0.1, bm.EPS)     # no CPU fallback
-
-
-def _grad_errors(model, ref, names):
-    """Per tensor of `names` (parameters' gradients, then buffers), the worst |a - ref| in units of U max|ref|; a reference
-    that is all zeros demands zeros (inf otherwise)."""
-    out = {}
-    pa, pr = dict(model.named_parameters()), dict(ref.named_parameters())
-    ba, brf = dict(model.named_buffers()), dict(ref.named_buffers())
-    for n in names:
-        a, r = (pa[n].grad, pr[n].grad) if n in pa else (ba[n], brf[n])
-        a, r = a.detach().double().cpu().numpy(), r.detach().double().cpu().numpy()
-        scale = U * np.abs(r).max()
-        assert np.isfinite(a).all(), n
-        out[n] = float(np.abs(a - r).max() / scale) if scale > 0 else (float("inf") if np.any(a) else 0.0)
-    return out
-
-
-def _bound(ref_units):
-    return pow2_at_or_above(4 * ref_units) if 0 < ref_units < float("inf") else ref_units
 
 
 @pytest.mark.parametrize("kind", sorted(BACKBONES))

@@ -7,74 +7,13 @@ import copy
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
-import torch.nn.functional as F
 
 from tests import depthwise_conv_matrix as dm
-from tests.helpers import pow2_at_or_above
-from tests.test_hip_optim import HYPER, _Counter
-from tests.test_hip_parity import tol_for
-from wekws_amd.model import depthwise, mdtc, tcn
+from tests.helpers import pow2_at_or_above, tol_for
+from tests.train_step import ARGS, BACKBONES, HDIM, HYPER, IDIM, ODIM, Kws, TorchConv1d, _Counter, _distances, _Float64, _loader, torch_convs
+from wekws_amd.model import depthwise
 
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -24
-IDIM, HDIM, ODIM = 20, 8, 2
-BACKBONES = {
-    "ds_tcn": (lambda: tcn.TCN(2, HDIM, 3, dropout=0.0, block_class=tcn.DsCnnBlock),
-               dict(type="tcn", ds=True, num_layers=2, kernel_size=3, dropout=0.0)),
-    # (the tiny MDTC is square -- the reference's MDTC.forward concatenates caches of in_channels and of res_channels, so it
-    # runs only where the two are equal, as init_model builds it)
-    "mdtc": (lambda: mdtc.MDTC(2, 2, HDIM, HDIM, 3, True),
-             dict(type="mdtc", num_stack=2, stack_size=2, kernel_size=3, hidden_dim=HDIM, causal=True)),
-}
-
-
-class TorchConv1d(nn.Conv1d):
-    """A depthwise convolution that is not the package's: the parameters of ``conv`` under torch's own statement, whatever the
-    device.  use_device_depthwise_convs sees an nn.Conv1d like any other."""
-
-    def __init__(self, conv):
-        super().__init__(conv.in_channels, conv.out_channels, conv.kernel_size[0], dilation=conv.dilation[0], groups=conv.groups,
-                         bias=conv.bias is not None)
-        self.weight, self.bias = conv.weight, conv.bias
-
-    def forward(self, x, left_pad=0):
-        return super().forward(F.pad(x, (left_pad, 0), value=0.0))
-
-
-def torch_convs(model):
-    """Every DepthwiseConv1d of ``model`` replaced by a TorchConv1d over the same parameters."""
-    for parent in list(model.modules()):
-        for name, child in list(parent.named_children()):
-            if isinstance(child, depthwise.DepthwiseConv1d):
-                setattr(parent, name, TorchConv1d(child))
-    return model
-
-
-class _Prep(nn.Module):
-    def __init__(self):
-        super().__init__()
-        self.out = nn.Sequential(nn.Linear(IDIM, HDIM), nn.ReLU())
-
-
-class _Head(nn.Module):
-    def __init__(self):
-        super().__init__()
-        self.linear = nn.Linear(HDIM, ODIM)
-
-
-class Kws(nn.Module):
-    """The reference's KWSModel for a keyword recipe, as far as training goes: a Linear + ReLU in front of the backbone, a Linear
-    classifier and a sigmoid behind it, under the reference's state-dict keys."""
-
-    def __init__(self, backbone):
-        super().__init__()
-        self.preprocessing, self.backbone, self.classifier = _Prep(), backbone, _Head()
-
-    def forward(self, x, cache=None):
-        y, cache = self.backbone(self.preprocessing.out(x), cache)
-        return torch.sigmoid(self.classifier.linear(y)), cache
 
 
 def _conv(c, cls=depthwise.DepthwiseConv1d):
@@ -147,46 +86,6 @@ def test_only_the_gradients_asked_for():
     for bad in (dict(dilation=0), dict(left_pad=8), dict(left_pad=-1)):
         with pytest.raises(ValueError):
             depthwise.depthwise_conv1d(t(c["x"]), t(c["w"]), None, **{**dict(dilation=1, left_pad=0), **bad})
-
-
-def _loader(sizes, T, seed):
-    rng = np.random.default_rng(seed)
-    out = []
-    for i, n in enumerate(sizes):
-        feats = rng.standard_normal((n, T, IDIM)).astype(np.float32)
-        lengths = rng.integers(T // 2, T + 1, n).astype(np.int32)
-        lengths[0] = T
-        target = rng.integers(-1, ODIM, (n, 1)).astype(np.int64)
-        out.append(dict(keys=[f"utt{i}_{j}" for j in range(n)], feats=torch.from_numpy(feats), target=torch.from_numpy(target),
-                        feats_lengths=torch.from_numpy(lengths), target_lengths=torch.ones(n, dtype=torch.int32)))
-    return out
-
-
-class _Float64(nn.Module):
-    """A float64 model behind the float32 interface of the device criterion."""
-
-    def __init__(self, model):
-        super().__init__()
-        self.model = model.double()
-
-    def forward(self, x):
-        y, c = self.model(x.double())
-        return y.float(), c
-
-
-ARGS = {"criterion": "max_pooling", "grad_clip": 5.0, "log_interval": 100}
-
-
-def _distances(a, b, start, ref):
-    """Per parameter tensor, the worst |a - b| in units of U (|start| + |ref - start|): the scale of tests/optim_matrix.py's p'."""
-    out = []
-    for pa, pb, ps, pr in zip(a, b, start, ref):
-        pa, pb, ps, pr = (t.detach().double().cpu().numpy() for t in (pa, pb, ps, pr))
-        den = U * (np.abs(ps) + np.abs(pr - ps))
-        err = np.abs(pa - pb)
-        assert np.isfinite(err).all() and not np.any(err[den == 0])
-        out.append(float((err[den > 0] / den[den > 0]).max()) if (den > 0).any() else 0.0)
-    return out
 
 
 @pytest.mark.parametrize("kind", sorted(BACKBONES))

@@ -8,9 +8,8 @@ import pytest
 import torch
 
 from tests import fsmn_memory_matrix as fm
-from tests.helpers import pow2_at_or_above
-from tests.test_hip_optim import HYPER, _Counter
-from tests.test_hip_parity import tol_for
+from tests.helpers import pow2_at_or_above, tol_for
+from tests.train_step import HYPER, _Counter
 from wekws_amd.model import fsmn
 
 pytestmark = pytest.mark.gpu

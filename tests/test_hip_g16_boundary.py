@@ -12,8 +12,8 @@ import pytest
 import torch
 
 from oracle import kws_oracle
-from tests.helpers import max_abs
-from tests.test_hip_parity import POSTERIOR_TOL, build, run, tol_for
+from tests.helpers import POSTERIOR_TOL, max_abs, tol_for
+from tests.test_hip_parity import build, run
 from wekws_amd import pack
 from wekws_amd.utils import synth
 

@@ -16,8 +16,8 @@ import torch
 
 from oracle import kws_oracle
 from tests.golden.cases import GENERIC_CASES, shape_case_config
-from tests.helpers import CASES, case_in_cache, case_input, case_weights, max_abs, oracle64
-from tests.test_hip_parity import build, check_tight, run, tol_for
+from tests.helpers import CASES, case_in_cache, case_input, case_weights, max_abs, oracle64, tol_for
+from tests.test_hip_parity import build, check_tight, run
 from wekws_amd.utils import synth
 
 pytestmark = pytest.mark.gpu

@@ -8,10 +8,8 @@ import pytest
 import torch
 import torch.nn as nn
 
-from tests.helpers import pow2_at_or_above
-from tests.test_hip_conv_train import ARGS, _distances, _Float64, _loader
-from tests.test_hip_optim import HYPER, _Counter
-from tests.test_hip_parity import tol_for
+from tests.helpers import pow2_at_or_above, tol_for
+from tests.train_step import ARGS, HYPER, _Counter, _distances, _Float64, _loader
 from wekws_amd.model import gru as dg
 
 pytestmark = pytest.mark.gpu

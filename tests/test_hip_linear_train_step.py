@@ -16,12 +16,10 @@ import torch
 
 from tests import test_hip_fsmn_train as tf
 from tests import test_hip_gru_train_step as tg
-from tests.helpers import pow2_at_or_above
-from tests.test_hip_conv_train import ARGS as MAXPOOL_ARGS
-from tests.test_hip_conv_train import _distances
-from tests.test_hip_conv_train import _loader as maxpool_loader
-from tests.test_hip_optim import HYPER, _Counter
-from tests.test_hip_parity import tol_for
+from tests.helpers import pow2_at_or_above, tol_for
+from tests.train_step import ARGS as MAXPOOL_ARGS
+from tests.train_step import HYPER, _Counter, _distances
+from tests.train_step import _loader as maxpool_loader
 from wekws_amd.model import fsmn
 from wekws_amd.model import gru as dg
 from wekws_amd.model import linear as dl

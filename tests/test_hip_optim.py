@@ -13,6 +13,7 @@ import torch
 from tests import optim_matrix as om
 from tests import optim_ref
 from tests.test_hip_tenants import tenant  # noqa: F401  (the MFMA tenants of the second stream)
+from tests.train_step import HYPER, _Counter
 
 pytestmark = pytest.mark.gpu
 
@@ -257,9 +258,6 @@ def _p_units(got, want, before):
     return worst
 
 
-HYPER = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4)
-
-
 def test_clip_adam_against_torchs_three_statements():
     from wekws_amd.optim import ClipAdam
     torch.manual_seed(3)
@@ -293,20 +291,6 @@ def test_clip_adam_against_torchs_three_statements():
         assert u <= 2 * om.BARS["p"]
         assert (i == 1) == all(torch.equal(p, b) for p, b in zip(model.parameters(), before))   # only the skipped batch leaves p alone
     assert int(opt.skipped_steps) == 1 and int(opt.steps) == len(loader) - 1
-
-
-class _Counter:
-    def __init__(self, monkeypatch):
-        self.calls = []
-        for owner, name in ((torch.cuda, "synchronize"), (torch.Tensor, "item"), (torch.Tensor, "tolist"), (torch.Tensor, "__bool__"),
-                            (torch.Tensor, "__float__"), (torch.Tensor, "__int__"), (torch.Tensor, "cpu"), (torch.Tensor, "numpy")):
-            monkeypatch.setattr(owner, name, self._wrap(getattr(owner, name), name))
-
-    def _wrap(self, fn, name):
-        def counted(*a, **k):
-            self.calls.append(name)
-            return fn(*a, **k)
-        return counted
 
 
 def test_train_executor_reads_nothing_on_the_host(monkeypatch):

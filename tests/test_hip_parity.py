@@ -14,18 +14,12 @@ import torch
 from oracle import kws_oracle
 from tests.golden.cases import (GRU_INPUT_CASES, HETERO_CASES, SCALE_CASES, SHAPE_CASES, hetero_case_weights,
                                 scaled_case_weights, shape_case_config)
-from tests.helpers import (CASES, TIGHT_K, case_in_cache, case_input, case_weights, max_abs, oracle64, random_model_config as _random_model_config,
-                           tight_errors)
+from tests.helpers import (CASES, POSTERIOR_TOL, TIGHT_K, case_in_cache, case_input, case_weights, max_abs, oracle64,
+                           random_model_config as _random_model_config, tight_errors, tol_for)
 from wekws_amd.model.kws_model import init_model
 from wekws_amd.utils import synth
 
 pytestmark = pytest.mark.gpu
-
-POSTERIOR_TOL = 1e-4
-
-
-def tol_for(ref):
-    return POSTERIOR_TOL * max(1.0, float(np.abs(ref).max()))
 
 
 def check_tight(error_report, key, cfg, y, c, ry, rc, softmax=False, y32=None, c32=None):

@@ -12,12 +12,10 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import pow2_at_or_above
-from tests.test_hip_batchnorm_train import SWAPPED as BN_SWAPPED
-from tests.test_hip_batchnorm_train import _bound, _grad_errors
-from tests.test_hip_conv_train import ARGS, BACKBONES, HDIM, IDIM, ODIM, Kws, _distances, _Float64, _loader, torch_convs
-from tests.test_hip_optim import HYPER, _Counter
-from tests.test_hip_parity import tol_for
+from tests.helpers import pow2_at_or_above, tol_for
+from tests.train_step import SWAPPED as BN_SWAPPED
+from tests.train_step import (ARGS, BACKBONES, HDIM, HYPER, IDIM, ODIM, Kws, _bound, _Counter, _distances, _Float64, _grad_errors, _loader,
+                              torch_convs)
 from wekws_amd.model import batchnorm, depthwise, pointwise
 
 pytestmark = pytest.mark.gpu

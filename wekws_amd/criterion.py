@@ -20,12 +20,11 @@ a ``ce`` target outside [0, D) and a CTC label outside [1, V) make that row's lo
 raises; an unknown ``type`` raises ValueError where the reference calls ``exit(1)``."""
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
-from wekws_amd import _capi
+from wekws_amd import _capi, _device
 
 _Function = torch.autograd.Function
 
@@ -74,10 +73,6 @@ def _i32(v, n: int, dev: torch.device, what: str) -> torch.Tensor:
     return t
 
 
-def _stream(dev: torch.device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _scalar(v: int, dev: torch.device) -> torch.Tensor:
     """A float64 device scalar to divide by: tensor / tensor is a true division, whereas tensor / Python number is evaluated on
     the device as a product with the reciprocal (200 / 300 would come out one ulp above Python's)."""
@@ -118,7 +113,7 @@ def max_pooling_grad_device(logits: torch.Tensor, target: torch.Tensor, lengths:
     grad = torch.empty((B, T, K), dtype=torch.float32, device=dev)
     _capi.check(_capi.load().wekws_hip_criterion_max_pooling_grad(
         x.data_ptr(), B, T, K, tg.data_ptr(), ln.data_ptr() if ln is not None else None, int(min_duration),
-        up.data_ptr() if up is not None else None, _divisor(divisor, B), grad.data_ptr(), _stream(dev)),
+        up.data_ptr() if up is not None else None, _divisor(divisor, B), grad.data_ptr(), _device.stream(dev)),
         "wekws_hip_criterion_max_pooling_grad")
     return grad
 
@@ -133,7 +128,7 @@ def cross_entropy_grad_device(logits: torch.Tensor, target: torch.Tensor, upstre
     up = _upstream(upstream, dev)
     grad = torch.empty((B, D), dtype=torch.float32, device=dev)
     _capi.check(_capi.load().wekws_hip_criterion_ce_grad(x.data_ptr(), B, D, tg.data_ptr(), up.data_ptr() if up is not None else None,
-                                                         _divisor(divisor, B), grad.data_ptr(), _stream(dev)),
+                                                         _divisor(divisor, B), grad.data_ptr(), _device.stream(dev)),
                 "wekws_hip_criterion_ce_grad")
     return grad
 
@@ -160,7 +155,7 @@ def ctc_loss_grad_device(logits: torch.Tensor, target: torch.Tensor, logits_leng
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     _capi.check(lib.wekws_hip_ctc_loss_grad(x.data_ptr(), B, T, V, tg.data_ptr() if Lmax else None, Lmax, ll.data_ptr(), tl.data_ptr(),
                                             up.data_ptr() if up is not None else None, _divisor(divisor, B), rows.data_ptr(),
-                                            loss.data_ptr(), grad.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)),
+                                            loss.data_ptr(), grad.data_ptr(), ws.data_ptr(), nbytes, _device.stream(dev)),
                 "wekws_hip_ctc_loss_grad")
     return grad, rows, loss
 
@@ -254,7 +249,7 @@ def _max_pooling_forward(logits: torch.Tensor, target: torch.Tensor, lengths: Op
     num = torch.empty((), dtype=torch.int32, device=dev)
     _capi.check(_capi.load().wekws_hip_criterion_max_pooling(
         x.data_ptr(), B, T, K, tg.data_ptr(), ln.data_ptr() if ln is not None else None, int(min_duration), pooled.data_ptr(),
-        terms.data_ptr(), correct.data_ptr(), loss.data_ptr(), num.data_ptr(), _stream(dev)), "wekws_hip_criterion_max_pooling")
+        terms.data_ptr(), correct.data_ptr(), loss.data_ptr(), num.data_ptr(), _device.stream(dev)), "wekws_hip_criterion_max_pooling")
     return MaxPoolingResult(loss, num.to(torch.float64) / _scalar(B, dev), pooled, terms, correct, num)
 
 
@@ -269,7 +264,7 @@ def _cross_entropy_forward(logits: torch.Tensor, target: torch.Tensor) -> CrossE
     loss = torch.empty((), dtype=torch.float32, device=dev)
     num = torch.empty((), dtype=torch.int32, device=dev)
     _capi.check(_capi.load().wekws_hip_criterion_ce(x.data_ptr(), B, D, tg.data_ptr(), rows.data_ptr(), pred.data_ptr(),
-                                                    correct.data_ptr(), loss.data_ptr(), num.data_ptr(), _stream(dev)),
+                                                    correct.data_ptr(), loss.data_ptr(), num.data_ptr(), _device.stream(dev)),
                 "wekws_hip_criterion_ce")
     return CrossEntropyResult(loss, num.to(torch.float64) * 100.0 / _scalar(B, dev), rows, pred, correct, num)
 
@@ -305,7 +300,7 @@ def _ctc_loss_forward(logits: torch.Tensor, target: torch.Tensor, logits_lengths
     probs = torch.empty_like(x) if need_acc else None           # the posteriors of the decode, from the same read of the logits
     _capi.check(lib.wekws_hip_ctc_loss(x.data_ptr(), B, T, V, tg.data_ptr() if Lmax else None, Lmax, ll.data_ptr(), tl.data_ptr(),
                                        rows.data_ptr(), loss.data_ptr(), probs.data_ptr() if need_acc else None, ws.data_ptr(),
-                                       nbytes, _stream(dev)), "wekws_hip_ctc_loss")
+                                       nbytes, _device.stream(dev)), "wekws_hip_ctc_loss")
     if not need_acc:
         return CtcResult(loss, torch.zeros((), dtype=torch.float64, device=dev), rows, None, None)
     dist, totals = _utterance_distances(probs, tg, ll, tl)
@@ -325,12 +320,12 @@ def _utterance_distances(probs: torch.Tensor, tg: torch.Tensor, ll: torch.Tensor
     beams = torch.empty((B, hd.beam_bytes(T)), dtype=torch.uint8, device=dev)
     beams[:, :8].zero_()                  # a row whose search fails keeps no record: count 0, the empty hypothesis
     _capi.check(lib.wekws_hip_ctc_kws_search(hd.h, probs.data_ptr(), B, T, ll.clamp(0, T).data_ptr(), res.data_ptr(),
-                                             beams.data_ptr(), _stream(dev)), "wekws_hip_ctc_kws_search")
+                                             beams.data_ptr(), _device.stream(dev)), "wekws_hip_ctc_kws_search")
     dist = torch.empty((B,), dtype=torch.int32, device=dev)
     totals = torch.empty((2,), dtype=torch.int32, device=dev)
     Lmax = int(tg.size(1))
     _capi.check(lib.wekws_hip_ctc_edit_distance(beams.data_ptr(), _PATH_BEAM, T, B, tg.data_ptr() if Lmax else None, Lmax,
-                                                tl.data_ptr(), dist.data_ptr(), totals.data_ptr(), _stream(dev)),
+                                                tl.data_ptr(), dist.data_ptr(), totals.data_ptr(), _device.stream(dev)),
                 "wekws_hip_ctc_edit_distance")
     return dist, totals
 

@@ -7,8 +7,6 @@ namespace {
 
 using wekws::BatchNormArgs;
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 BatchNormArgs make_args(int B, int C, int T) {
   BatchNormArgs a{};
   a.rows = int64_t(B) * C;
@@ -25,13 +23,9 @@ int check_shape(const char* what, int B, int C, int T, int batch_stats) {
   return WEKWS_HIP_OK;
 }
 
-int check_workspace(const char* what, int B, int C, int T, const void* workspace, size_t workspace_bytes) {
-  if (!workspace) return fail(WEKWS_HIP_EINVAL, "%s: this call needs a workspace", what);
-  if (!aligned16(workspace)) return fail(WEKWS_HIP_EINVAL, "%s: the workspace must be 16-byte aligned", what);
-  const size_t need = size_t(wekws::batchnorm_workspace_bytes(B, C, T));
-  if (workspace_bytes < need)
-    return fail(WEKWS_HIP_EINVAL, "%s: workspace of %zu bytes, need %zu (wekws_hip_batchnorm_workspace_bytes)", what, workspace_bytes, need);
-  return WEKWS_HIP_OK;
+int check_bn_workspace(const char* what, int B, int C, int T, const void* workspace, size_t workspace_bytes) {
+  return check_workspace(what, workspace, workspace_bytes, size_t(wekws::batchnorm_workspace_bytes(B, C, T)),
+                         "wekws_hip_batchnorm_workspace_bytes");
 }
 
 // the parts of the workspace (batchnorm_plan.h)
@@ -98,7 +92,7 @@ int wekws_hip_batchnorm_forward(const float* x, const float* residual, int B, in
   if (batch_stats && running_mean && momentum < 0.0 && !num_batches_tracked)
     return fail(WEKWS_HIP_EINVAL, "%s: a cumulative average needs num_batches_tracked", what);
   if (batch_stats)
-    if (const int rc = check_workspace(what, B, C, T, workspace, workspace_bytes)) return rc;
+    if (const int rc = check_bn_workspace(what, B, C, T, workspace, workspace_bytes)) return rc;
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const BatchNormArgs a = make_args(B, C, T);
   const dim3 grid(unsigned(wekws::batchnorm_tiles(B, C, T))), block(wekws::kBnThreads);
@@ -137,7 +131,7 @@ int wekws_hip_batchnorm_backward(const float* x, const float* y, const float* gr
   if (const int rc = check_shape(what, B, C, T, batch_stats)) return rc;
   const bool sums = grad_weight || grad_bias || (batch_stats && grad_x);
   if (sums)
-    if (const int rc = check_workspace(what, B, C, T, workspace, workspace_bytes)) return rc;
+    if (const int rc = check_bn_workspace(what, B, C, T, workspace, workspace_bytes)) return rc;
   const hipStream_t s = static_cast<hipStream_t>(stream);
   const BatchNormArgs a = make_args(B, C, T);
   const dim3 grid(unsigned(wekws::batchnorm_tiles(B, C, T))), block(wekws::kBnThreads);

@@ -7,8 +7,6 @@ namespace {
 
 using wekws::DepthwiseConvArgs;
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // the shape and the tap table as the kernels read them.  sign +1: a tile's LDS columns start P frames before it and a tap
 // reads halo - delay columns on (forward, tap gradient); -1: they start P - halo frames after it and a tap reads delay columns
 // on (the input gradient, which reads rows of Tout frames and writes rows of Tin)
@@ -74,14 +72,11 @@ int wekws_hip_depthwise_conv1d_backward(const float* x, const float* grad_y, int
   if (!x || !grad_y || !w) return fail(WEKWS_HIP_EINVAL, "depthwise_conv1d_backward: NULL argument");
   if (const int rc = check_shape("depthwise_conv1d_backward", B, C, Tin, K, dilation, left_pad)) return rc;
   const int Tout = int(wekws::depthwise_conv_tout(Tin, K, dilation, left_pad));
-  if (grad_w || grad_bias) {
-    if (!workspace) return fail(WEKWS_HIP_EINVAL, "depthwise_conv1d_backward: the tap and bias gradients need a workspace");
-    if (!aligned16(workspace)) return fail(WEKWS_HIP_EINVAL, "depthwise_conv1d_backward: the workspace must be 16-byte aligned");
-    const size_t need = size_t(wekws::depthwise_conv_workspace_bytes(B, C, Tout, K));
-    if (workspace_bytes < need)
-      return fail(WEKWS_HIP_EINVAL, "depthwise_conv1d_backward: workspace of %zu bytes, need %zu (wekws_hip_depthwise_conv1d_workspace_bytes)",
-                  workspace_bytes, need);
-  }
+  if (grad_w || grad_bias)                                          // the tap and bias gradients' partial sums
+    if (const int rc = check_workspace("depthwise_conv1d_backward", workspace, workspace_bytes,
+                                       size_t(wekws::depthwise_conv_workspace_bytes(B, C, Tout, K)),
+                                       "wekws_hip_depthwise_conv1d_workspace_bytes"))
+      return rc;
   const hipStream_t s = static_cast<hipStream_t>(stream);
   bool bad = false;
   if (grad_x) {

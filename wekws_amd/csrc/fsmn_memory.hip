@@ -7,8 +7,6 @@ namespace {
 
 using wekws::FsmnMemArgs;
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // the shape and the tap table as the kernels read them; sign +1: rows are frames t0 - halo ... and a tap reads halo - delay
 // rows on (forward, tap gradient); -1: rows are frames t0 ... and a tap reads delay rows on (the input gradient)
 FsmnMemArgs make_args(int T, int D, int lorder, int lstride, int rorder, int rstride, int sign, int tile) {
@@ -79,14 +77,11 @@ int wekws_hip_fsmn_memory_backward(const float* x, const float* grad_y, int B, i
   if (const int rc = check_shape("fsmn_memory_backward", B, T, D, lorder, lstride, rorder, rstride)) return rc;
   if ((grad_w_left == nullptr) != (grad_w_right == nullptr))
     return fail(WEKWS_HIP_EINVAL, "fsmn_memory_backward: grad_w_left and grad_w_right are wanted together or not at all");
-  if (grad_w_left) {
-    if (!workspace) return fail(WEKWS_HIP_EINVAL, "fsmn_memory_backward: the tap gradient needs a workspace");
-    if (!aligned16(workspace)) return fail(WEKWS_HIP_EINVAL, "fsmn_memory_backward: the workspace must be 16-byte aligned");
-    const size_t need = size_t(wekws::fsmn_memory_workspace_bytes(B, T, D, lorder, rorder));
-    if (workspace_bytes < need)
-      return fail(WEKWS_HIP_EINVAL, "fsmn_memory_backward: workspace of %zu bytes, need %zu (wekws_hip_fsmn_memory_workspace_bytes)",
-                  workspace_bytes, need);
-  }
+  if (grad_w_left)                                                  // the tap gradient's partial sums
+    if (const int rc = check_workspace("fsmn_memory_backward", workspace, workspace_bytes,
+                                       size_t(wekws::fsmn_memory_workspace_bytes(B, T, D, lorder, rorder)),
+                                       "wekws_hip_fsmn_memory_workspace_bytes"))
+      return rc;
   const hipStream_t s = static_cast<hipStream_t>(stream);
   bool bad = false;
   if (grad_x) {

@@ -5,8 +5,6 @@
 
 namespace {
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int check_shape(const char* what, int B, int T, int H) {
   if (const char* why = wekws::gru_scan_check(B, T, H)) return fail(WEKWS_HIP_EINVAL, "%s: %s (B=%d T=%d H=%d)", what, why, B, T, H);
   return WEKWS_HIP_OK;

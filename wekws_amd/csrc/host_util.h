@@ -1,9 +1,11 @@
-// Host helpers every unit with C entry points shares: the thread's error text, HIP error codes, the device guard.
+// Host helpers every unit with C entry points shares: the thread's error text, HIP error codes, the device guard, the
+// alignment and workspace checks.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 
 #include "../../include/wekws_hip.h"
@@ -54,6 +56,20 @@ struct WEKWS_LOCAL DeviceGuard {
   DeviceGuard(const DeviceGuard&) = delete;
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
+
+// does `p` (NULL included) start on a 16-byte boundary, as the kernels' 16-byte accesses and double workspaces need?
+static inline __attribute__((unused)) bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The caller's workspace for the call `what`: present, 16-byte aligned and of at least `need` bytes, the figure `sizer_name`
+// (the exported wekws_hip_*_workspace_bytes) gives for the shape.
+static inline __attribute__((unused)) int check_workspace(const char* what, const void* workspace, size_t workspace_bytes, size_t need,
+                                                          const char* sizer_name) {
+  if (!workspace) return fail(WEKWS_HIP_EINVAL, "%s: this call needs a workspace", what);
+  if (!aligned16(workspace)) return fail(WEKWS_HIP_EINVAL, "%s: the workspace must be 16-byte aligned", what);
+  if (workspace_bytes < need)
+    return fail(WEKWS_HIP_EINVAL, "%s: workspace of %zu bytes, need %zu (%s)", what, workspace_bytes, need, sizer_name);
+  return WEKWS_HIP_OK;
+}
 
 // is `stream` being captured into a HIP graph?  (a capture admits no synchronisation and no allocation)
 static inline __attribute__((unused)) bool stream_is_capturing(hipStream_t stream) {

@@ -6,8 +6,6 @@
 
 namespace {
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 template <bool VEC, bool BCT>
 bool launch_partial(const float* x, const float* g, int64_t R, int O, int I, int64_t T, bool want_w, double* ws_w, double* ws_b,
                     hipStream_t s) {

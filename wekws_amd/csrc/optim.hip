@@ -9,8 +9,6 @@ namespace {
 
 using wekws::OptimState;
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // [a, a + bytes) and [b, b + bytes) share a byte
 bool overlap(const void* a, const void* b, size_t bytes) {
   const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);

@@ -6,8 +6,6 @@
 
 namespace {
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 template <bool TRANS, bool BIAS, bool VECX, bool VECW>
 bool launch_mm4(const float* x, const float* w, const float* bias, float* y, int B, int K, int M, int T, int ldw, hipStream_t s) {
   const int tiles_m = int(wekws::wgrad_ceil_div(M, wekws::kPwTile)), tiles_t = int(wekws::wgrad_ceil_div(T, wekws::kPwTile));

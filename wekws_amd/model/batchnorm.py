@@ -12,58 +12,19 @@ package's own blocks to the fused calls.
 """
 from __future__ import annotations
 
-import contextlib
-import ctypes
-from typing import Dict, Optional, Tuple
+from typing import Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from wekws_amd import _capi
-
-_workspaces: Dict[torch.device, torch.Tensor] = {}
-
-
-def _workspace(device: torch.device, nbytes: int) -> torch.Tensor:
-    """One workspace a device, grown on demand.  Calls on one stream are ordered, so they may share it; a caller that runs the
-    op on several streams at once serialises them itself."""
-    ws = _workspaces.get(device)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-        _workspaces[device] = ws
-    return ws
-
-
-_workspace_bytes: Dict[Tuple[int, int, int], int] = {}
+from wekws_amd import _capi, _device
 
 
 def _workspace_for(device: torch.device, B: int, C: int, T: int) -> torch.Tensor:
-    """The workspace for a shape; the size comes from the library once a shape."""
-    nbytes = _workspace_bytes.get((B, C, T))
-    if nbytes is None:
-        nbytes = int(_capi.load().wekws_hip_batchnorm_workspace_bytes(B, C, T))
-        if nbytes == 0:
-            raise ValueError(f"wekws_hip_batchnorm_workspace_bytes: {_capi.last_error()}")
-        _workspace_bytes[(B, C, T)] = nbytes
-    return _workspace(device, nbytes)
-
-
-_NO_GUARD = contextlib.nullcontext()
-
-
-def _on(device: torch.device):
-    """The device made current for a call, when it is not already (the step's hot path: one comparison)."""
-    return _NO_GUARD if torch.cuda.current_device() == device.index else torch.cuda.device(device)
-
-
-def _stream(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
+    """The workspace for a shape."""
+    return _device.workspace(device, _device.library_bytes("wekws_hip_batchnorm_workspace_bytes", (B, C, T), ValueError))
 
 
 def _check(rc: int, what: str) -> None:
@@ -89,12 +50,13 @@ class _BatchNormAct(torch.autograd.Function):
         stats = torch.empty(2, C, dtype=x.dtype, device=x.device)          # save_mean, save_invstd
         ws = _workspace_for(x.device, B, C, T)
         update = batch_stats and running_mean is not None
-        with _on(x.device):
+        ptr = _device.ptr
+        with _device.on(x.device):
             _check(lib.wekws_hip_batchnorm_forward(
-                x.data_ptr(), _ptr(r), B, C, T, _ptr(w), _ptr(b), _ptr(running_mean) if update or not batch_stats else None,
-                _ptr(running_var) if update or not batch_stats else None, _ptr(num_batches_tracked) if update else None,
+                x.data_ptr(), ptr(r), B, C, T, ptr(w), ptr(b), ptr(running_mean) if update or not batch_stats else None,
+                ptr(running_var) if update or not batch_stats else None, ptr(num_batches_tracked) if update else None,
                 int(batch_stats), -1.0 if momentum is None else float(momentum), float(eps), int(relu), y.data_ptr(), stats.data_ptr(),
-                stats.data_ptr() + 4 * C, ws.data_ptr(), ws.numel(), _stream(x.device)), "wekws_hip_batchnorm_forward")
+                stats.data_ptr() + 4 * C, ws.data_ptr(), ws.numel(), _device.stream(x.device)), "wekws_hip_batchnorm_forward")
         ctx.save_for_backward(x, w, stats, y if relu else None)
         ctx.conf = (B, C, T, bool(batch_stats), bool(relu), weight is not None, bias is not None, residual is not None)
         return y
@@ -121,10 +83,11 @@ class _BatchNormAct(torch.autograd.Function):
         dw = torch.empty(C, dtype=x.dtype, device=x.device) if want_w else None
         db = torch.empty(C, dtype=x.dtype, device=x.device) if want_b else None
         ws = _workspace_for(x.device, B, C, T)
-        with _on(x.device):
+        ptr = _device.ptr
+        with _device.on(x.device):
             _check(lib.wekws_hip_batchnorm_backward(
-                x.data_ptr(), _ptr(y), g.data_ptr(), B, C, T, _ptr(w), stats.data_ptr(), stats.data_ptr() + 4 * C, int(batch_stats), int(relu),
-                _ptr(dx), _ptr(dres) if want_r else None, _ptr(dw), _ptr(db), ws.data_ptr(), ws.numel(), _stream(x.device)),
+                x.data_ptr(), ptr(y), g.data_ptr(), B, C, T, ptr(w), stats.data_ptr(), stats.data_ptr() + 4 * C, int(batch_stats), int(relu),
+                ptr(dx), ptr(dres) if want_r else None, ptr(dw), ptr(db), ws.data_ptr(), ws.numel(), _device.stream(x.device)),
                 "wekws_hip_batchnorm_backward")
         return (dx, dw, db, dres) + none
 
@@ -141,13 +104,7 @@ def batch_norm_act(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Option
     fallback: anything else raises ``ValueError``."""
     tensors = (("x", x), ("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var),
                ("residual", residual))
-    for name, t in tensors:
-        if t is None and name != "x":
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise ValueError(f"batch_norm_act: {name} must be a float32 tensor on a ROCm device (no CPU fallback)")
-        if t.device != x.device:
-            raise ValueError(f"batch_norm_act: tensors on one device, got {x.device} and {t.device}")
+    _device.require_float32("batch_norm_act", x, [(name, t) for name, t in tensors if t is not None or name == "x"])
     if x.dim() not in (2, 3) or min(x.shape) < 1:
         raise ValueError(f"batch_norm_act: x must be (B, C, T) or (B, C) with no empty dimension, got {tuple(x.shape)}")
     C = x.shape[1]
@@ -220,13 +177,9 @@ def use_device_batchnorms(module: nn.Module) -> int:
     own ``DsCnnBlock``, ``DSDilatedConv1d`` and ``TCNBlock``, which then hand their ReLU and residual add to the
     normalisation's call.  Modules that are ``DeviceBatchNorm1d``s already are left alone.  Returns the number swapped."""
     from wekws_amd.model import mdtc, tcn
-    swapped = 0
-    for parent in list(module.modules()):
-        for name, child in list(parent.named_children()):
-            if isinstance(child, DeviceBatchNorm1d) or not isinstance(child, nn.BatchNorm1d):
-                continue
-            setattr(parent, name, DeviceBatchNorm1d.sharing(child))
-            swapped += 1
-        if isinstance(parent, (tcn.DsCnnBlock, mdtc.DSDilatedConv1d, mdtc.TCNBlock)):
-            parent.fused_norm = True
+    swapped = _device.swap_children(
+        module, lambda child: not isinstance(child, DeviceBatchNorm1d) and isinstance(child, nn.BatchNorm1d), DeviceBatchNorm1d.sharing)
+    for block in module.modules():
+        if isinstance(block, (tcn.DsCnnBlock, mdtc.DSDilatedConv1d, mdtc.TCNBlock)):
+            block.fused_norm = True
     return swapped

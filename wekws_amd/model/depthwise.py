@@ -10,15 +10,14 @@ reference's own ``TCN`` or ``MDTC`` included -- for ``DepthwiseConv1d``s that sh
 """
 from __future__ import annotations
 
-import ctypes
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from wekws_amd import _capi
+from wekws_amd import _capi, _device
 
 MAX_TAPS = 32          # K                                        (csrc/depthwise_conv_plan.h)
 MAX_WINDOW = 256       # (K - 1) * dilation + 1
@@ -33,23 +32,6 @@ def in_device_limits(kernel_size, dilation) -> bool:
     return 1 <= kernel_size <= MAX_TAPS and dilation >= 1 and (kernel_size - 1) * dilation + 1 <= MAX_WINDOW
 
 
-_workspaces: Dict[torch.device, torch.Tensor] = {}
-
-
-def _workspace(device: torch.device, nbytes: int) -> torch.Tensor:
-    """One workspace a device, grown on demand.  Calls on one stream are ordered, so they may share it; a caller that
-    differentiates on several streams at once serialises them itself."""
-    ws = _workspaces.get(device)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-        _workspaces[device] = ws
-    return ws
-
-
-def _stream(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 class _DepthwiseConv1d(torch.autograd.Function):
 
     @staticmethod
@@ -59,10 +41,9 @@ class _DepthwiseConv1d(torch.autograd.Function):
         x, w = x.contiguous(), weight.contiguous()
         b = bias.contiguous() if bias is not None else None
         y = torch.empty(B, C, Tin + left_pad - (K - 1) * dilation, dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            _capi.check(_capi.load().wekws_hip_depthwise_conv1d_forward(x.data_ptr(), B, C, Tin, w.data_ptr(),
-                                                                        b.data_ptr() if b is not None else None, K, dilation, left_pad,
-                                                                        y.data_ptr(), _stream(x.device)),
+        with _device.on(x.device):
+            _capi.check(_capi.load().wekws_hip_depthwise_conv1d_forward(x.data_ptr(), B, C, Tin, w.data_ptr(), _device.ptr(b), K, dilation,
+                                                                        left_pad, y.data_ptr(), _device.stream(x.device)),
                         "wekws_hip_depthwise_conv1d_forward")
         ctx.save_for_backward(x, w)
         ctx.conf = (dilation, left_pad, weight.shape, bias is not None)
@@ -86,15 +67,13 @@ class _DepthwiseConv1d(torch.autograd.Function):
         db = torch.empty(C, dtype=x.dtype, device=x.device) if want_b else None
         ws, ws_bytes = None, 0
         if want_w or want_b:
-            ws_bytes = int(lib.wekws_hip_depthwise_conv1d_workspace_bytes(B, C, Tin, K, dilation, left_pad))
-            if ws_bytes == 0:
-                raise _capi.HipLibraryError(f"wekws_hip_depthwise_conv1d_workspace_bytes: {_capi.last_error()}")
-            ws = _workspace(x.device, ws_bytes)
-        with torch.cuda.device(x.device):
+            ws_bytes = _device.library_bytes("wekws_hip_depthwise_conv1d_workspace_bytes", (B, C, Tin, K, dilation, left_pad),
+                                             _capi.HipLibraryError)
+            ws = _device.workspace(x.device, ws_bytes)
+        with _device.on(x.device):
             _capi.check(lib.wekws_hip_depthwise_conv1d_backward(
-                x.data_ptr(), g.data_ptr(), B, C, Tin, w.data_ptr(), K, dilation, left_pad, dx.data_ptr() if want_x else None,
-                dw.data_ptr() if want_w else None, db.data_ptr() if want_b else None, ws.data_ptr() if ws is not None else None,
-                ws_bytes, _stream(x.device)), "wekws_hip_depthwise_conv1d_backward")
+                x.data_ptr(), g.data_ptr(), B, C, Tin, w.data_ptr(), K, dilation, left_pad, _device.ptr(dx), _device.ptr(dw),
+                _device.ptr(db), _device.ptr(ws), ws_bytes, _device.stream(x.device)), "wekws_hip_depthwise_conv1d_backward")
         return dx, dw.view(w_shape) if want_w else None, db, None, None
 
 
@@ -105,11 +84,7 @@ def depthwise_conv1d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
     None, ``0 <= left_pad <= (K - 1) * dilation``.  Returns y (B, C, Tin + left_pad - (K - 1) * dilation).  The padding is not
     materialised.  Non-contiguous inputs are made contiguous; the call runs on the current stream and reads nothing on the
     host.  No CPU fallback: anything else raises."""
-    for name, t in (("x", x), ("weight", weight)) + ((("bias", bias),) if bias is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise ValueError(f"depthwise_conv1d: {name} must be a float32 tensor on a ROCm device (no CPU fallback)")
-        if t.device != x.device:
-            raise ValueError(f"depthwise_conv1d: tensors on one device, got {x.device} and {t.device}")
+    _device.require_float32("depthwise_conv1d", x, (("x", x), ("weight", weight)) + ((("bias", bias),) if bias is not None else ()))
     if x.dim() != 3 or min(x.shape) < 1:
         raise ValueError(f"depthwise_conv1d: x must be (B, C, T) with no empty dimension, got {tuple(x.shape)}")
     C = x.shape[1]
@@ -170,11 +145,6 @@ def use_device_depthwise_convs(module: nn.Module) -> int:
     no padding of its own, ``padding_mode == "zeros"`` and lies inside the kernels' limits by a ``DepthwiseConv1d`` that shares
     its parameter objects, so optimisers built before the swap and state dicts stay valid.  Everything else is left alone, and
     so are convolutions that are ``DepthwiseConv1d``s already.  Returns the number swapped."""
-    swapped = 0
-    for parent in list(module.modules()):
-        for name, child in list(parent.named_children()):
-            if isinstance(child, DepthwiseConv1d) or not isinstance(child, nn.Conv1d) or not _is_depthwise(child):
-                continue
-            setattr(parent, name, DepthwiseConv1d.sharing(child))
-            swapped += 1
-    return swapped
+    return _device.swap_children(
+        module, lambda child: not isinstance(child, DepthwiseConv1d) and isinstance(child, nn.Conv1d) and _is_depthwise(child),
+        DepthwiseConv1d.sharing)

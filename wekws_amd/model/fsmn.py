@@ -12,15 +12,14 @@ cache (streaming), CPU tensors and other dtypes take torch's own ops, statement 
 """
 from __future__ import annotations
 
-import ctypes
-from typing import Dict, Tuple
+from typing import Tuple
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from wekws_amd import _capi
+from wekws_amd import _capi, _device
 
 MAX_TAPS = 32          # lorder + rorder                         (csrc/fsmn_memory_plan.h)
 MAX_WINDOW = 256       # rorder * rstride + (lorder - 1) * lstride + 1
@@ -36,23 +35,6 @@ def in_device_limits(lorder, rorder, lstride, rstride) -> bool:
             and rorder * rstride + (lorder - 1) * lstride + 1 <= MAX_WINDOW)
 
 
-_workspaces: Dict[torch.device, torch.Tensor] = {}
-
-
-def _workspace(device: torch.device, nbytes: int) -> torch.Tensor:
-    """One workspace a device, grown on demand.  Calls on one stream are ordered, so they may share it; a caller that
-    differentiates on several streams at once serialises them itself."""
-    ws = _workspaces.get(device)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
-        _workspaces[device] = ws
-    return ws
-
-
-def _stream(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 class _FsmnMemory(torch.autograd.Function):
 
     @staticmethod
@@ -61,9 +43,9 @@ class _FsmnMemory(torch.autograd.Function):
         lorder, rorder = w_left.numel() // D, w_right.numel() // D
         x, wl, wr = x.contiguous(), w_left.contiguous(), w_right.contiguous()
         y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
+        with _device.on(x.device):
             _capi.check(_capi.load().wekws_hip_fsmn_memory_forward(x.data_ptr(), B, T, D, wl.data_ptr(), lorder, lstride, wr.data_ptr(),
-                                                                   rorder, rstride, y.data_ptr(), _stream(x.device)),
+                                                                   rorder, rstride, y.data_ptr(), _device.stream(x.device)),
                         "wekws_hip_fsmn_memory_forward")
         ctx.save_for_backward(x, wl, wr)
         ctx.strides = (lstride, rstride)
@@ -88,15 +70,13 @@ class _FsmnMemory(torch.autograd.Function):
         dwr = torch.empty_like(wr) if want_w else None
         ws, ws_bytes = None, 0
         if want_w:
-            ws_bytes = int(lib.wekws_hip_fsmn_memory_workspace_bytes(B, T, D, lorder, rorder))
-            if ws_bytes == 0:
-                raise _capi.HipLibraryError(f"wekws_hip_fsmn_memory_workspace_bytes: {_capi.last_error()}")
-            ws = _workspace(x.device, ws_bytes)
-        with torch.cuda.device(x.device):
+            ws_bytes = _device.library_bytes("wekws_hip_fsmn_memory_workspace_bytes", (B, T, D, lorder, rorder), _capi.HipLibraryError)
+            ws = _device.workspace(x.device, ws_bytes)
+        with _device.on(x.device):
             _capi.check(lib.wekws_hip_fsmn_memory_backward(
                 x.data_ptr(), g.data_ptr(), B, T, D, wl.data_ptr(), lorder, lstride, wr.data_ptr(), rorder, rstride,
-                dx.data_ptr() if want_x else None, dwl.data_ptr() if want_w else None, dwr.data_ptr() if want_w else None,
-                ws.data_ptr() if want_w else None, ws_bytes, _stream(x.device)), "wekws_hip_fsmn_memory_backward")
+                _device.ptr(dx), _device.ptr(dwl), _device.ptr(dwr), _device.ptr(ws), ws_bytes, _device.stream(x.device)),
+                "wekws_hip_fsmn_memory_backward")
         lshape, rshape = ctx.w_shapes
         return (dx, dwl.view(lshape) if ctx.needs_input_grad[1] else None, dwr.view(rshape) if ctx.needs_input_grad[2] else None,
                 None, None)
@@ -107,11 +87,7 @@ def fsmn_memory(x: torch.Tensor, w_left: torch.Tensor, w_right: torch.Tensor, ls
     of D * lorder elements laid out (D, lorder) -- ``conv_left.weight`` (D, 1, lorder, 1) as it is -- and ``w_right`` likewise.
     Returns y (B, T, D): the reference block's output for an empty cache.  Non-contiguous inputs are made contiguous; the call
     runs on the current stream and reads nothing on the host.  No CPU fallback: anything else raises."""
-    for name, t in (("x", x), ("w_left", w_left), ("w_right", w_right)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise ValueError(f"fsmn_memory: {name} must be a float32 tensor on a ROCm device (no CPU fallback)")
-        if t.device != x.device:
-            raise ValueError(f"fsmn_memory: tensors on one device, got {x.device} and {t.device}")
+    _device.require_float32("fsmn_memory", x, (("x", x), ("w_left", w_left), ("w_right", w_right)))
     if x.dim() != 3 or min(x.shape) < 1:
         raise ValueError(f"fsmn_memory: x must be (B, T, D) with no empty dimension, got {tuple(x.shape)}")
     D = x.shape[2]
@@ -297,13 +273,10 @@ def use_device_memory_blocks(module: nn.Module) -> int:
     lstride, rstride -- by an ``FSMNBlock`` that shares its parameter objects, so optimisers built before the swap and state
     dicts stay valid.  Blocks without a right context (``rorder == 0``, which the reference cannot run either) or outside the
     kernels' limits are left alone, and so are blocks that are ``FSMNBlock``s already.  Returns the number swapped."""
-    swapped = 0
-    for parent in list(module.modules()):
-        for name, child in list(parent.named_children()):
-            if isinstance(child, FSMNBlock) or not _is_memory_block(child):
-                continue
-            if child.conv_right is None or not in_device_limits(child.lorder, child.rorder, child.lstride, child.rstride):
-                continue
-            setattr(parent, name, FSMNBlock.sharing(child))
-            swapped += 1
-    return swapped
+
+    def wanted(child: nn.Module) -> bool:
+        if isinstance(child, FSMNBlock) or not _is_memory_block(child):
+            return False
+        return child.conv_right is not None and in_device_limits(child.lorder, child.rorder, child.lstride, child.rstride)
+
+    return _device.swap_children(module, wanted, FSMNBlock.sharing)

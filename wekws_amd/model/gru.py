@@ -13,14 +13,13 @@ kernels are built for; everything else -- CPU tensors, other dtypes, packed sequ
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from wekws_amd import _capi
+from wekws_amd import _capi, _device
 
 MIN_HIDDEN = 16        # csrc/gru_train_plan.h: the built hidden sizes are the multiples of 16 up to 128
 MAX_HIDDEN = 128
@@ -33,14 +32,6 @@ def in_device_limits(hidden_size) -> bool:
     except (TypeError, ValueError):
         return False
     return hidden_size % 16 == 0 and MIN_HIDDEN <= hidden_size <= MAX_HIDDEN
-
-
-def _stream(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 class _GruScan(torch.autograd.Function):
@@ -57,9 +48,10 @@ class _GruScan(torch.autograd.Function):
         y = torch.empty((B, T, H), dtype=gi.dtype, device=gi.device)
         hn = torch.empty((B, H), dtype=gi.dtype, device=gi.device)
         reserve = torch.empty((B, T, 4 * H), dtype=gi.dtype, device=gi.device) if wanted else None
-        with torch.cuda.device(gi.device):
-            _capi.check(_capi.load().wekws_hip_gru_scan_forward(gi.data_ptr(), w.data_ptr(), _ptr(b), _ptr(h), B, T, H, y.data_ptr(),
-                                                                hn.data_ptr(), _ptr(reserve), _stream(gi.device)),
+        ptr = _device.ptr
+        with _device.on(gi.device):
+            _capi.check(_capi.load().wekws_hip_gru_scan_forward(gi.data_ptr(), w.data_ptr(), ptr(b), ptr(h), B, T, H, y.data_ptr(),
+                                                                hn.data_ptr(), ptr(reserve), _device.stream(gi.device)),
                         "wekws_hip_gru_scan_forward")
         if wanted:
             ctx.save_for_backward(y, reserve, w, h)
@@ -79,10 +71,11 @@ class _GruScan(torch.autograd.Function):
         dgi = torch.empty((B, T, 3 * H), dtype=y.dtype, device=y.device)
         dgh = torch.empty_like(dgi)
         dh0 = torch.empty((B, H), dtype=y.dtype, device=y.device) if (want_h0 and h0 is not None) else None
-        with torch.cuda.device(y.device):
-            _capi.check(_capi.load().wekws_hip_gru_scan_backward(_ptr(gy), _ptr(ghn), y.data_ptr(), _ptr(h0), reserve.data_ptr(),
-                                                                 w.data_ptr(), B, T, H, dgi.data_ptr(), dgh.data_ptr(), _ptr(dh0),
-                                                                 _stream(y.device)), "wekws_hip_gru_scan_backward")
+        ptr = _device.ptr
+        with _device.on(y.device):
+            _capi.check(_capi.load().wekws_hip_gru_scan_backward(ptr(gy), ptr(ghn), y.data_ptr(), ptr(h0), reserve.data_ptr(),
+                                                                 w.data_ptr(), B, T, H, dgi.data_ptr(), dgh.data_ptr(), ptr(dh0),
+                                                                 _device.stream(y.device)), "wekws_hip_gru_scan_backward")
         dw = db = None
         if ctx.device_weight_grads and (want_w or want_b):
             from wekws_amd.model.linear import _weight_grad
@@ -121,11 +114,7 @@ def gru_scan(gi: torch.Tensor, w_hh: torch.Tensor, b_hh: Optional[torch.Tensor],
     ``w_hh`` and ``b_hh`` are torch's ``mm`` and ``sum`` over the scan's ``dgh``; with ``device_weight_grads`` they are
     ``wekws_amd.model.linear``'s split-K kernels.  No CPU fallback: anything else raises."""
     tensors = [("gi", gi), ("w_hh", w_hh)] + ([("b_hh", b_hh)] if b_hh is not None else []) + ([("h0", h0)] if h0 is not None else [])
-    for name, t in tensors:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise ValueError(f"gru_scan: {name} must be a float32 tensor on a ROCm device (no CPU fallback)")
-        if t.device != gi.device:
-            raise ValueError(f"gru_scan: tensors on one device, got {gi.device} and {t.device}")
+    _device.require_float32("gru_scan", gi, tensors)
     if gi.dim() != 3 or min(gi.shape) < 1 or gi.shape[2] % 3:
         raise ValueError(f"gru_scan: gi must be (B, T, 3H) with no empty dimension, got {tuple(gi.shape)}")
     B, _, H3 = gi.shape
@@ -210,11 +199,5 @@ def use_device_grus(module: nn.Module) -> int:
     """Replace every eligible ``nn.GRU`` child below ``module`` -- ``batch_first``, one direction, no dropout, a hidden size the
     kernels are built for -- by a ``DeviceGRU`` that shares its Parameter objects, so optimisers built before the swap and state
     dicts stay valid.  Other GRUs, and ``DeviceGRU``s, are left alone.  Returns the number swapped."""
-    swapped = 0
-    for parent in list(module.modules()):
-        for name, child in list(parent.named_children()):
-            if isinstance(child, DeviceGRU) or not isinstance(child, nn.GRU) or not _eligible(child):
-                continue
-            setattr(parent, name, DeviceGRU.sharing(child))
-            swapped += 1
-    return swapped
+    return _device.swap_children(
+        module, lambda child: not isinstance(child, DeviceGRU) and isinstance(child, nn.GRU) and _eligible(child), DeviceGRU.sharing)

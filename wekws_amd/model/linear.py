@@ -12,7 +12,6 @@ The device path runs for float32 tensors on a ROCm device with at least one row;
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional, Tuple
 
 import torch
@@ -20,39 +19,27 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from wekws_amd import _capi
+from wekws_amd import _capi, _device
 
 MAX_FEATURES = 65535        # csrc/linear_wgrad_plan.h: O and I
-
-
-def _stream(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _weight_grad(x2: torch.Tensor, g2: torch.Tensor, want_w: bool, want_b: bool):
     """x2 (R, I), g2 (R, O): float32, contiguous, on one ROCm device; at least one of the two is wanted."""
     R, I = x2.shape
     O = g2.shape[1]
-    lib = _capi.load()
-    nbytes = lib.wekws_hip_linear_wgrad_workspace_bytes(R, O, I)
-    if nbytes == 0:
-        raise ValueError(f"linear_weight_grad: {_capi.last_error()}")
+    nbytes = _device.library_bytes("wekws_hip_linear_wgrad_workspace_bytes", (R, O, I), ValueError, "linear_weight_grad")
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x2.device)
     dw = torch.empty((O, I), dtype=torch.float32, device=x2.device) if want_w else None
     db = torch.empty((O,), dtype=torch.float32, device=x2.device) if want_b else None
-    with torch.cuda.device(x2.device):
-        _capi.check(lib.wekws_hip_linear_wgrad(x2.data_ptr(), g2.data_ptr(), R, O, I, None if dw is None else dw.data_ptr(),
-                                               None if db is None else db.data_ptr(), ws.data_ptr(), nbytes, _stream(x2.device)),
-                    "wekws_hip_linear_wgrad")
+    with _device.on(x2.device):
+        _capi.check(_capi.load().wekws_hip_linear_wgrad(x2.data_ptr(), g2.data_ptr(), R, O, I, _device.ptr(dw), _device.ptr(db),
+                                                        ws.data_ptr(), nbytes, _device.stream(x2.device)), "wekws_hip_linear_wgrad")
     return dw, db
 
 
 def _check_pair(x, g):
-    for name, t in (("x", x), ("g", g)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise ValueError(f"linear_weight_grad: {name} must be a float32 tensor on a ROCm device (no CPU fallback)")
-    if x.device != g.device:
-        raise ValueError(f"linear_weight_grad: tensors on one device, got {x.device} and {g.device}")
+    _device.require_float32("linear_weight_grad", x, (("x", x), ("g", g)))
     if x.dim() < 1 or g.dim() != x.dim() or x.shape[:-1] != g.shape[:-1]:
         raise ValueError(f"linear_weight_grad: x (..., I) and g (..., O) with the same leading dimensions, got {tuple(x.shape)} "
                          f"and {tuple(g.shape)}")
@@ -98,11 +85,7 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     ``F.linear`` and the input gradient ``g.matmul(weight)``, both torch's bit for bit; only the gradients autograd asks for are
     computed.  No CPU fallback: anything else raises."""
     tensors = [("x", x), ("weight", weight)] + ([("bias", bias)] if bias is not None else [])
-    for name, t in tensors:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise ValueError(f"linear: {name} must be a float32 tensor on a ROCm device (no CPU fallback)")
-        if t.device != x.device:
-            raise ValueError(f"linear: tensors on one device, got {x.device} and {t.device}")
+    _device.require_float32("linear", x, tensors)
     if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight.shape[1] or x.numel() == 0:
         raise ValueError(f"linear: x (..., I) with at least one row and weight (O, I), got {tuple(x.shape)} and {tuple(weight.shape)}")
     if bias is not None and tuple(bias.shape) != (weight.shape[0],):
@@ -144,15 +127,8 @@ def use_device_weight_grads(module: nn.Module) -> int:
     ``device_weight_grads`` on for every ``DeviceGRU``, so optimisers built before the swap and state dicts stay valid.
     Idempotent: what is changed already is left alone.  Returns the number of modules changed."""
     from wekws_amd.model.gru import DeviceGRU
-    changed = 0
-    for parent in list(module.modules()):
-        for name, child in list(parent.named_children()):
-            if type(child) is DeviceLinear or not isinstance(child, nn.Linear):
-                continue
-            if type(child) is not nn.Linear:
-                continue                                   # a subclass with a forward of its own keeps it
-            setattr(parent, name, DeviceLinear.sharing(child))
-            changed += 1
+    # (exactly nn.Linear: a subclass with a forward of its own keeps it)
+    changed = _device.swap_children(module, lambda child: type(child) is nn.Linear, DeviceLinear.sharing)
     for m in module.modules():
         if isinstance(m, DeviceGRU) and not m.device_weight_grads:
             m.device_weight_grads = True

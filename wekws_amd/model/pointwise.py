@@ -15,30 +15,15 @@ The device path runs for contiguous 3-D float32 tensors on a ROCm device with at
 """
 from __future__ import annotations
 
-import ctypes
-import functools
 from typing import Optional
 
 import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
-from wekws_amd import _capi
+from wekws_amd import _capi, _device
 
 MAX_CHANNELS = 65535        # csrc/pointwise_conv_plan.h: Ci and Co
-
-
-def _stream(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-@functools.lru_cache(maxsize=None)
-def _workspace_bytes(B: int, Ci: int, T: int, Co: int) -> int:
-    """Asked of the library once per shape."""
-    nbytes = int(_capi.load().wekws_hip_pointwise_conv1d_workspace_bytes(B, Ci, T, Co))
-    if nbytes == 0:
-        raise ValueError(f"pointwise_conv1d: {_capi.last_error()}")
-    return nbytes
 
 
 class _PointwiseConv1d(torch.autograd.Function):
@@ -50,10 +35,9 @@ class _PointwiseConv1d(torch.autograd.Function):
         x, w = x.contiguous(), weight.contiguous()
         b = bias.contiguous() if bias is not None else None
         y = torch.empty(B, Co, T, dtype=x.dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            _capi.check(_capi.load().wekws_hip_pointwise_conv1d_forward(x.data_ptr(), B, Ci, T, w.data_ptr(),
-                                                                        b.data_ptr() if b is not None else None, Co, y.data_ptr(),
-                                                                        _stream(x.device)),
+        with _device.on(x.device):
+            _capi.check(_capi.load().wekws_hip_pointwise_conv1d_forward(x.data_ptr(), B, Ci, T, w.data_ptr(), _device.ptr(b), Co,
+                                                                        y.data_ptr(), _device.stream(x.device)),
                         "wekws_hip_pointwise_conv1d_forward")
         ctx.save_for_backward(x, w)
         ctx.conf = (weight.shape, bias is not None)
@@ -76,13 +60,12 @@ class _PointwiseConv1d(torch.autograd.Function):
         db = torch.empty(Co, dtype=x.dtype, device=x.device) if want_b else None
         ws, ws_bytes = None, 0
         if want_w or want_b:
-            ws_bytes = _workspace_bytes(B, Ci, T, Co)
+            ws_bytes = _device.library_bytes("wekws_hip_pointwise_conv1d_workspace_bytes", (B, Ci, T, Co), ValueError, "pointwise_conv1d")
             ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=x.device)
-        with torch.cuda.device(x.device):
+        with _device.on(x.device):
             _capi.check(_capi.load().wekws_hip_pointwise_conv1d_backward(
-                x.data_ptr(), g.data_ptr(), B, Ci, T, w.data_ptr(), Co, dx.data_ptr() if want_x else None,
-                dw.data_ptr() if want_w else None, db.data_ptr() if want_b else None, ws.data_ptr() if ws is not None else None,
-                ws_bytes, _stream(x.device)), "wekws_hip_pointwise_conv1d_backward")
+                x.data_ptr(), g.data_ptr(), B, Ci, T, w.data_ptr(), Co, _device.ptr(dx), _device.ptr(dw), _device.ptr(db), _device.ptr(ws),
+                ws_bytes, _device.stream(x.device)), "wekws_hip_pointwise_conv1d_backward")
         return dx, dw.view(w_shape) if want_w else None, db
 
 
@@ -91,11 +74,7 @@ def pointwise_conv1d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch
     ROCm device, ``weight`` (Co, Ci, 1) -- ``conv.weight`` as it is -- or (Co, Ci), ``bias`` (Co) or None.  Returns y (B, Co, T).
     Only the gradients autograd asks for are computed.  Non-contiguous inputs are made contiguous; the call runs on the current
     stream and reads nothing on the host.  No CPU fallback: anything else raises."""
-    for name, t in (("x", x), ("weight", weight)) + ((("bias", bias),) if bias is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise ValueError(f"pointwise_conv1d: {name} must be a float32 tensor on a ROCm device (no CPU fallback)")
-        if t.device != x.device:
-            raise ValueError(f"pointwise_conv1d: tensors on one device, got {x.device} and {t.device}")
+    _device.require_float32("pointwise_conv1d", x, (("x", x), ("weight", weight)) + ((("bias", bias),) if bias is not None else ()))
     if x.dim() != 3 or min(x.shape) < 1:
         raise ValueError(f"pointwise_conv1d: x must be (B, Ci, T) with no empty dimension, got {tuple(x.shape)}")
     Ci = x.shape[1]
@@ -151,11 +130,4 @@ def use_device_pointwise_convs(module: nn.Module) -> int:
     stride 1, padding 0, dilation 1, groups 1, zeros padding mode) by a ``PointwiseConv1d`` that shares its Parameter objects, so
     optimisers built before the swap, state dicts and the other ``use_device_*`` swaps stay valid in any order.  Idempotent: what
     is swapped already is left alone.  Returns the number swapped."""
-    swapped = 0
-    for parent in list(module.modules()):
-        for name, child in list(parent.named_children()):
-            if type(child) is not nn.Conv1d or not _is_pointwise(child):
-                continue
-            setattr(parent, name, PointwiseConv1d.sharing(child))
-            swapped += 1
-    return swapped
+    return _device.swap_children(module, lambda child: type(child) is nn.Conv1d and _is_pointwise(child), PointwiseConv1d.sharing)
