@@ -1271,6 +1271,43 @@ int wekws_hip_pointwise_conv1d_backward(const float* x, const float* grad_y, int
                                         float* grad_x /* NULL: not wanted */, float* grad_w /* NULL: not wanted */,
                                         float* grad_bias /* NULL: not wanted */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The dense (groups 1) dilated Conv1d of the TCN's CnnBlock, forward and backward:
+ * F.conv1d(F.pad(x, (left_pad, 0)), w, bias, dilation=dilation) for x (B, Ci, Tin), y and grad_y (B, Co, Tout) with
+ * Tout = Tin + left_pad - (K - 1) dilation, float32, contiguous; w (Co, Ci, K) as nn.Conv1d holds it; bias (Co) or none.  The
+ * padding's zeros are supplied by the kernels (xp[n < 0] = 0); the padded copy is never made.  The arithmetic:
+ *     forward   y[b][o][t]: acc = +0; k ascending and, inside it, i ascending, acc = fmaf(w[o][i][k], xp[b][i][t + k d - left_pad], acc);
+ *               then one float32 addition of bias[o] (none without a bias) -- the exact-float32 matrix instruction from a zeroed
+ *               accumulator with the reduction index k Ci + i.  The padding's zeros are real operands: an infinite weight over
+ *               them is NaN, as in the padded convolution.
+ *     grad_x    grad_x[b][i][n]: the same chain over k ascending and, inside it, o ascending,
+ *               fmaf(w[o][i][k], grad_y[b][o][n + left_pad - k d], acc), grad_y a zero outside [0, Tout); non-finite weights are
+ *               outside the contract here
+ *     grad_w, grad_bias   grad_w[:, :, k] is wekws_hip_linear_wgrad's contract, unchanged, with rows r = b Tout + t, R = B Tout,
+ *               O = Co, I = Ci and x's row r = xp[b][:, t + k d - left_pad]: the bits of wekws_hip_linear_wgrad on the shifted,
+ *               zero-padded, transposed copies, which are not made.  grad_bias is that contract's, computed once.
+ * A (b, t) column of y and a (b, n) column of grad_x depend on batch row b alone.  Stateless calls, device pointers, no
+ * floating-point atomics, no waits between workgroups; no call synchronises, allocates or reads on the host; every element of
+ * every requested output is written.  One launch for the forward; one for grad_x and two for grad_w / grad_bias, whatever K: the
+ * taps are a grid dimension.  Operands may have any 4-byte alignment.
+ *
+ * Limits (WEKWS_HIP_EINVAL, before any launch, outputs untouched): B, Tin >= 1;  1 <= Ci, Co <= 65535;  1 <= K <= 32;
+ * dilation >= 1;  (K - 1) dilation + 1 <= 256;  0 <= left_pad <= (K - 1) dilation;  Tout >= 1;  every grid within 2^31 - 1;  no NULL
+ * operand;  at least one of the three gradients;  where grad_w or grad_bias is wanted, a workspace that is not NULL, 16-byte
+ * aligned and at least wekws_hip_dense_conv1d_workspace_bytes(...) large (grad_x alone needs none).
+ * ------------------------------------------------------------------------------------------*/
+/* Without a device: out = {rows a chain, chains, slices, workgroups a tap of the weight gradient's partial launch, workspace
+ * bytes, workgroups of the forward, workgroups of grad_x, taps (the second grid dimension of the partial and the fold launch),
+ * workgroups a tap of the fold launch, Tout}; the first four are wekws_hip_linear_wgrad_plan(B Tout, Co, Ci)'s. */
+int wekws_hip_dense_conv1d_plan(int B, int Ci, int Tin, int Co, int K, int dilation, int left_pad, int64_t out[10]);
+/* Without a device: K x wekws_hip_linear_wgrad_workspace_bytes(B Tout, Co, Ci).  0 on bad arguments. */
+size_t wekws_hip_dense_conv1d_workspace_bytes(int B, int Ci, int Tin, int Co, int K, int dilation, int left_pad);
+int wekws_hip_dense_conv1d_forward(const float* x, int B, int Ci, int Tin, const float* w, const float* bias /* NULL: none */, int Co, int K,
+                                   int dilation, int left_pad, float* y, void* stream);
+int wekws_hip_dense_conv1d_backward(const float* x, const float* grad_y, int B, int Ci, int Tin, const float* w, int Co, int K, int dilation,
+                                    int left_pad, float* grad_x /* NULL: not wanted */, float* grad_w /* NULL: not wanted */,
+                                    float* grad_bias /* NULL: not wanted */, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,15 +6,33 @@
 
 namespace {
 
-template <bool VEC, bool BCT>
+// the taps of a dense Conv1d (TAP): the second grid dimension of the partial launch
+struct Taps {
+  int taps = 1, dil = 0, pad = 0;
+  int64_t Tx = 0, stride = 0;                   // frames of a batch row of x; doubles between two taps' partials
+};
+
+template <bool VEC, bool BCT, bool TAP = false>
 bool launch_partial(const float* x, const float* g, int64_t R, int O, int I, int64_t T, bool want_w, double* ws_w, double* ws_b,
-                    hipStream_t s) {
+                    hipStream_t s, const Taps& t = Taps()) {
   const int64_t grid = want_w ? wekws::linear_wgrad_grid(R, O, I) : wekws::linear_wgrad_bias_grid(R, O, I);
   const int tiles_i = want_w ? int(wekws::wgrad_ceil_div(I, wekws::kWgradTile)) : 1;
-  hipLaunchKernelGGL((wekws::linear_wgrad_partial<VEC, BCT>), dim3(unsigned(grid)), dim3(wekws::kWgradThreads), 0, s, x, g, R, O, I, tiles_i,
-                     wekws::linear_wgrad_chains_per_slice(R, O, I), wekws::linear_wgrad_padded(O), wekws::linear_wgrad_padded(I),
-                     want_w ? ws_w : nullptr, ws_b, T);
+  hipLaunchKernelGGL((wekws::linear_wgrad_partial<VEC, BCT, TAP>), dim3(unsigned(grid), unsigned(want_w ? t.taps : 1)),
+                     dim3(wekws::kWgradThreads), 0, s, x, g, R, O, I, tiles_i, wekws::linear_wgrad_chains_per_slice(R, O, I),
+                     wekws::linear_wgrad_padded(O), wekws::linear_wgrad_padded(I), want_w ? ws_w : nullptr, ws_b, T, t.Tx, t.dil, t.pad,
+                     t.stride);
   return hipGetLastError() == hipSuccess;
+}
+
+// the fold of `taps` taps whose partials lie tap_stride doubles apart, for arguments already checked
+const char* launch_fold(double* ws, int64_t R, int O, int I, float* grad_w, float* grad_bias, int taps, int64_t tap_stride, hipStream_t s) {
+  const int64_t n_w = int64_t(O) * I;
+  const int64_t first = grad_w ? 0 : n_w, last = grad_bias ? n_w + O : n_w;
+  hipLaunchKernelGGL(wekws::linear_wgrad_fold, dim3(unsigned(wekws::wgrad_ceil_div(last - first, wekws::kWgradFoldThreads)),
+                                                    unsigned(grad_w ? taps : 1)),
+                     dim3(wekws::kWgradFoldThreads), 0, s, ws, O, I, wekws::linear_wgrad_slices(R, O, I), wekws::linear_wgrad_padded(O),
+                     wekws::linear_wgrad_padded(I), wekws::linear_wgrad_bias_offset(R, O, I), first, last, grad_w, grad_bias, tap_stride);
+  return hipGetLastError() == hipSuccess ? nullptr : "the fold launch failed";
 }
 
 }  // namespace
@@ -39,13 +57,23 @@ const char* linear_wgrad_launch(const float* x, const float* g, int64_t R, int O
              : launch_partial<false, false>(x, g, R, O, I, 0, want_w, ws, ws_b, s);
   }
   if (!ok) return "the partial launch failed";
-  const int64_t n_w = int64_t(O) * I;
-  const int64_t first = grad_w ? 0 : n_w, last = grad_bias ? n_w + O : n_w;
-  hipLaunchKernelGGL(linear_wgrad_fold, dim3(unsigned(wgrad_ceil_div(last - first, kWgradFoldThreads))), dim3(kWgradFoldThreads), 0, s, ws,
-                     O, I, linear_wgrad_slices(R, O, I), linear_wgrad_padded(O), linear_wgrad_padded(I), bias_offset, first, last, grad_w,
-                     grad_bias);
-  if (hipGetLastError() != hipSuccess) return "the fold launch failed";
-  return nullptr;
+  return launch_fold(ws, R, O, I, grad_w, grad_bias, 1, 0, s);
+}
+
+const char* linear_wgrad_launch_taps(const float* x, const float* g, int64_t B, int64_t Tin, int64_t Tout, int O, int I, int K, int dilation,
+                                     int left_pad, float* grad_w, float* grad_bias, void* workspace, void* stream) {
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  double* const ws = static_cast<double*>(workspace);
+  const int64_t R = B * Tout;
+  double* const ws_b = grad_bias ? ws + linear_wgrad_bias_offset(R, O, I) : nullptr;
+  Taps t;
+  t.taps = K, t.dil = dilation, t.pad = left_pad, t.Tx = Tin;
+  t.stride = linear_wgrad_workspace_bytes(R, O, I) / int64_t(sizeof(double));
+  const bool vec = Tout % 4 == 0 && aligned16(g);               // of the g fetch; a tap's x fetch is scalar
+  const bool ok = vec ? launch_partial<true, true, true>(x, g, R, O, I, Tout, grad_w != nullptr, ws, ws_b, s, t)
+                      : launch_partial<false, true, true>(x, g, R, O, I, Tout, grad_w != nullptr, ws, ws_b, s, t);
+  if (!ok) return "the partial launch failed";
+  return launch_fold(ws, R, O, I, grad_w, grad_bias, K, t.stride, s);
 }
 
 }  // namespace wekws

@@ -74,12 +74,40 @@ __device__ inline float4 wgrad_fetch_bct(const float* __restrict__ base, int64_t
   return v;
 }
 
-// T: frames of a batch row of the (B, C, T) operands (BCT); unused otherwise
-template <bool VEC, bool BCT = false>
+// The x operand of a tap of a dense Conv1d (dense_conv_plan.h): rows row .. row + 3 of column col, row = b T + t, are
+// x[b][col][t + shift] of x (B, cols, Tx), zeros where t + shift is outside [0, Tx).  Scalar loads.
+__device__ inline float4 wgrad_fetch_tap(const float* __restrict__ base, int64_t row, int64_t row_end, int64_t b, int64_t t, int64_t T,
+                                         int64_t Tx, int64_t shift, int col, int cols) {
+  float e[4] = {0.f, 0.f, 0.f, 0.f};
+  if (col < cols && row < row_end) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t n = t + shift;
+      if (row + u < row_end && n >= 0 && n < Tx) e[u] = base[(b * cols + col) * Tx + n];
+      if (++t == T) {
+        t = 0;
+        ++b;
+      }
+    }
+  }
+  return make_float4(e[0], e[1], e[2], e[3]);
+}
+
+// T: frames of a batch row of the (B, C, T) operands (BCT); unused otherwise.  TAP (with BCT): blockIdx.y is a tap of a dense
+// Conv1d -- g is (B, O, T), x is (B, I, Tx) read at the frame shift tap * dil - pad (wgrad_fetch_tap), the tap's partials go
+// tap * tap_stride doubles further into ws_w, and tap 0 alone sums the bias.  Everything after the fetch is unchanged.
+template <bool VEC, bool BCT = false, bool TAP = false>
 __global__ __launch_bounds__(kWgradThreads) void linear_wgrad_partial(const float* __restrict__ x, const float* __restrict__ g,
                                                                       int64_t R, int O, int I, int tiles_i, int64_t chains_per_slice,
                                                                       int64_t o_pad, int64_t i_pad, double* __restrict__ ws_w,
-                                                                      double* __restrict__ ws_b, int64_t T) {
+                                                                      double* __restrict__ ws_b, int64_t T, int64_t Tx, int dil, int pad,
+                                                                      int64_t tap_stride) {
+  static_assert(BCT || !TAP, "the per-tap fetch is a (B, C, T) fetch");
+  const int64_t shift = TAP ? int64_t(blockIdx.y) * dil - pad : 0;
+  if (TAP) {
+    if (ws_w) ws_w += blockIdx.y * tap_stride;
+    if (blockIdx.y) ws_b = nullptr;
+  }
   constexpr int S = kWgradStride, ST = kWgradStage, BUF = kWgradStage * kWgradStride;
   constexpr int kStagesPerChain = kWgradChain / kWgradStage;
   __shared__ __attribute__((aligned(16))) float lds[2 * 2 * BUF];      // [buffer][g, x][row][S]
@@ -118,8 +146,9 @@ __global__ __launch_bounds__(kWgradThreads) void linear_wgrad_partial(const floa
     for (int j = 0; j < 2; ++j) {
       if (BCT) {
         gq[j] = wgrad_fetch_bct<VEC>(g, r0 + 16 * j, r_end, fb[j], ft[j], T, o_base + fcol, O);
-        xq[j] = want_w ? wgrad_fetch_bct<VEC>(x, r0 + 16 * j, r_end, fb[j], ft[j], T, i_base + fcol, I)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
+        xq[j] = !want_w ? make_float4(0.f, 0.f, 0.f, 0.f)
+                : TAP   ? wgrad_fetch_tap(x, r0 + 16 * j, r_end, fb[j], ft[j], T, Tx, shift, i_base + fcol, I)
+                        : wgrad_fetch_bct<VEC>(x, r0 + 16 * j, r_end, fb[j], ft[j], T, i_base + fcol, I);
         ft[j] += ST;                                         // the same rows of the next stage
         while (ft[j] >= T) {
           ft[j] -= T;
@@ -214,14 +243,19 @@ __global__ __launch_bounds__(kWgradThreads) void linear_wgrad_partial(const floa
   if (want_b && wave == 0 && o_base + lane < O) ws_b[slice * o_pad + o_base + lane] = bsum;
 }
 
-// element e of [first, first + count): e < O I is grad_w[e], the rest grad_bias[e - O I]
+// element e of [first, first + count): e < O I is grad_w[e], the rest grad_bias[e - O I].  blockIdx.y is a tap of a dense Conv1d
+// (one tap, stride 0, everywhere else): its partials lie tap * tap_stride doubles further, its element e of grad_w is
+// grad_w[e * taps + tap] -- (O, I, taps), taps contiguous -- and tap 0 alone folds the bias.
 __global__ __launch_bounds__(kWgradFoldThreads) void linear_wgrad_fold(const double* __restrict__ ws, int O, int I, int64_t slices,
                                                                        int64_t o_pad, int64_t i_pad, int64_t bias_offset,
                                                                        int64_t first, int64_t last, float* __restrict__ grad_w,
-                                                                       float* __restrict__ grad_bias) {
+                                                                       float* __restrict__ grad_bias, int64_t tap_stride) {
   const int64_t e = first + int64_t(blockIdx.x) * kWgradFoldThreads + threadIdx.x;
   if (e >= last) return;
   const int64_t n_w = int64_t(O) * I;
+  const int64_t tap = blockIdx.y, taps = gridDim.y;
+  if (e >= n_w && tap) return;
+  ws += tap * tap_stride;
   const double* p;
   int64_t stride;
   float* out;
@@ -229,7 +263,7 @@ __global__ __launch_bounds__(kWgradFoldThreads) void linear_wgrad_fold(const dou
     const int64_t o = e / I, i = e - o * I;
     p = ws + o * i_pad + i;
     stride = o_pad * i_pad;
-    out = grad_w + e;
+    out = grad_w + e * taps + tap;
   } else {
     p = ws + bias_offset + (e - n_w);
     stride = o_pad;

@@ -96,5 +96,10 @@ inline const char* linear_wgrad_check(const void* x, const void* g, int64_t R, i
 // frames > 0: x (B, I, frames) and g (B, O, frames) with R = B frames (pointwise_conv_plan.h).  0, or which launch failed.
 const char* linear_wgrad_launch(const float* x, const float* g, int64_t R, int O, int I, int64_t frames, float* grad_w, float* grad_bias,
                                 void* workspace, void* stream);
+// The same for the K taps of a dense Conv1d (dense_conv_plan.h) in one partial and one fold launch: x (B, I, Tin), g (B, O, Tout),
+// R = B Tout, tap k reads x at the frame shift k dilation - left_pad with zeros outside [0, Tin); grad_w is (O, I, K); the workspace
+// is K times linear_wgrad_workspace_bytes(R, O, I).
+const char* linear_wgrad_launch_taps(const float* x, const float* g, int64_t B, int64_t Tin, int64_t Tout, int O, int I, int K, int dilation,
+                                     int left_pad, float* grad_w, float* grad_bias, void* workspace, void* stream);
 
 }  // namespace wekws

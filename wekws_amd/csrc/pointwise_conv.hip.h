@@ -62,6 +62,40 @@ __device__ inline float4 pw_fetch_col(const float* __restrict__ w, int m, int M,
   return v;
 }
 
+// One stage of a wave's quadrant (dense_conv.hip.h uses it too): ap and bp are the lane's first elements of the weight and the x
+// stage, [k][kPwStride]; the four accumulators take the stage's 32 k in ascending order.
+__device__ inline void pw_stage_product(const float* __restrict__ ap, const float* __restrict__ bp, pw_f32x4 (&acc)[2][2]) {
+  constexpr int S = kPwStride;
+#pragma unroll
+  for (int kk = 0; kk < kPwStage / 4; ++kk) {
+    const float a0 = ap[kk * 4 * S], a1 = ap[kk * 4 * S + 16];
+    const float b0 = bp[kk * 4 * S], b1 = bp[kk * 4 * S + 16];
+    acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
+    acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
+    acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
+    acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
+  }
+}
+
+// A wave's quadrant to yb (M, T): the lane's rows o0 + 16 m + j and columns t0 + 16 n; BIAS: one float32 addition at the store.
+template <bool BIAS>
+__device__ inline void pw_store_quadrant(const pw_f32x4 (&acc)[2][2], float* __restrict__ yb, const float* __restrict__ bias, int o0, int M,
+                                         int64_t t0, int64_t T) {
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int o = o0 + 16 * m + j;
+      if (o >= M) continue;
+      const float add = BIAS ? bias[o] : 0.f;
+#pragma unroll
+      for (int n = 0; n < 2; ++n) {
+        const int64_t t = t0 + 16 * n;
+        if (t < T) yb[int64_t(o) * T + t] = BIAS ? acc[m][n][j] + add : acc[m][n][j];
+      }
+    }
+}
+
 // ldw: the row length of w, Ci
 template <bool TRANS, bool BIAS, bool VECX, bool VECW>
 __global__ __launch_bounds__(kPwThreads) void pointwise_conv_mm(const float* __restrict__ x, const float* __restrict__ w,
@@ -122,34 +156,12 @@ __global__ __launch_bounds__(kPwThreads) void pointwise_conv_mm(const float* __r
   for (int s = 0; s < stages; ++s) {
     if (s + 1 < stages) fetch(s + 1);
     const float* const bw = lds + (s & 1) * 2 * BUF;
-    const float* const ap = bw + lq * S + wm + l15;
-    const float* const bp = bw + BUF + lq * S + wt + l15;
-#pragma unroll
-    for (int kk = 0; kk < ST / 4; ++kk) {
-      const float a0 = ap[kk * 4 * S], a1 = ap[kk * 4 * S + 16];
-      const float b0 = bp[kk * 4 * S], b1 = bp[kk * 4 * S + 16];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
+    pw_stage_product(bw + lq * S + wm + l15, bw + BUF + lq * S + wt + l15, acc);
     if (s + 1 < stages) stash(s + 1);
     __syncthreads();
   }
 
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int o = m_base + wm + 16 * m + 4 * lq + j;
-      if (o >= M) continue;
-      const float add = BIAS ? bias[o] : 0.f;
-#pragma unroll
-      for (int n = 0; n < 2; ++n) {
-        const int64_t t = t_base + wt + 16 * n + l15;
-        if (t < T) yb[int64_t(o) * T + t] = BIAS ? acc[m][n][j] + add : acc[m][n][j];
-      }
-    }
+  pw_store_quadrant<BIAS>(acc, yb, bias, m_base + wm + 4 * lq, M, t_base + wt + l15, T);
 }
 
 }  // namespace wekws

@@ -8,7 +8,9 @@ called with ``left_pad = padding``, so the block's ``F.pad`` copy is not made an
 run.  With a non-empty cache (streaming) the block does what the reference does: ``torch.cat``, then the
 convolution.  The pointwise convolution of a ``DsCnnBlock`` is constructed as an ``nn.Conv1d`` and stays torch's unless
 ``wekws_amd.model.pointwise.use_device_pointwise_convs`` has swapped it for a ``PointwiseConv1d``.  The dense
-convolution of a ``CnnBlock`` and dropout stay torch's; so do BatchNorm and ReLU unless
+convolution of a ``CnnBlock`` is constructed as an ``nn.Conv1d`` behind the block's ``F.pad`` and stays torch's unless
+``wekws_amd.model.dense.use_device_dense_convs`` has swapped it for a ``DenseConv1d``: then it is called with
+``left_pad`` and the ``F.pad`` copy is not made.  Dropout stays torch's; so do BatchNorm and ReLU unless
 ``wekws_amd.model.batchnorm.use_device_batchnorms`` has set a ``DsCnnBlock``'s ``fused_norm``: then each BatchNorm is a
 ``DeviceBatchNorm1d`` that is called with ``relu=True`` and the ReLU modules are skipped.
 """
@@ -20,6 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from wekws_amd.model.dense import DenseConv1d
 from wekws_amd.model.depthwise import DepthwiseConv1d
 
 
@@ -74,6 +77,11 @@ class CnnBlock(Block):
         )
 
     def _convolve(self, y, left_pad):
+        if isinstance(self.cnn[0], DenseConv1d):       # swapped by use_device_dense_convs: it supplies the padding's zeros itself
+            y = self.cnn[0](y, left_pad)
+            for layer in list(self.cnn)[1:]:
+                y = layer(y)
+            return y
         if left_pad:
             y = F.pad(y, (left_pad, 0), value=0.0)
         return self.cnn(y)
